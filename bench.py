@@ -1,7 +1,7 @@
 """Benchmark of the hot path (BASELINE.json metric): frames/s for association + triangulation + IK
 on synthetic (F frames x C views x P people x 25 joints) keypoints, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--frames F --views C --people P --workload full]
+    python bench.py [--gpus N --steps K --warmup W] [--frames F --views C --people P --workload full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the whole hot path over this rank's F frames (inputs resident in HBM before
@@ -22,17 +22,6 @@ import json
 import os
 import sys
 import time
-
-# HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), and kernels of different streams that share a queue
-# run in order.  This program keeps three (since round 6: six) steps in flight on streams of their own beside a communication stream, a check stream and
-# the default stream: with four queues a step's pack kernel sat behind another step's chain kernel (1.55 ms per tail against 0.85 ms)
-# and config 4 ran at 532 k frames/s instead of 548 k (same box, three runs each; 6, 8, 12, 16, 24 queues: the same 547 - 550 k).
-# Read when the HIP runtime library is loaded, hence set before torch is imported; the environment overrides it.
-# Only for the chain workloads (the default): the single-stream workloads keep the runtime's default (config 2 at BASELINE's literal
-# 10 k frames, a 38 us launch, is slower with eight queues: 145 M against 266 M frames/s).
-_wl = [a for i, a in enumerate(sys.argv) if a.startswith("--workload=") or (i and sys.argv[i - 1] == "--workload")]
-if not _wl or _wl[-1].split("=")[-1] == "full":
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 import torch
@@ -242,6 +231,40 @@ def carries_against_ground_truth(out, data, L, Pn):
             "carried_to_the_right_person": right}
 
 
+DUMP_BYTES_MAX = 64_000_000      # --dump-outputs: all files together, headers included
+DUMP_PER_FRAME = ("params", "joints", "meta", "n_tracks", "labels", "pts3d")
+DUMP_PER_CHAIN = ("n_dead", "next_id")
+DUMP_STITCH = ("gid", "match")
+
+
+def _as_dump_array(a) -> np.ndarray:
+    """float32 / float64 stay as they are; integer and boolean tables become float64 (exact)."""
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+
+def dump_outputs(out_dir, per_frame: dict, whole: dict, n_frames: int) -> None:
+    """--dump-outputs: the last timed step's results as <name>.npy (float32 / float64), at most DUMP_BYTES_MAX in all.  `whole` is
+    written as it is; `per_frame` (first axis = the step's frames, or frames x k) is written for every frame when it fits, otherwise
+    for a fixed sample of frames (numpy seed 0, ascending).  frame_index.npy holds the frames written."""
+    per_frame = {k: v.reshape((n_frames, -1) + tuple(v.shape[1:])) if v.shape[0] != n_frames else v for k, v in per_frame.items()}
+    header = 128
+    fixed = sum(_as_dump_array(v).nbytes + header for v in whole.values()) + header * (len(per_frame) + 1)
+    row = 8 + sum((v[0].numel() * (v.element_size() if v.dtype in (torch.float32, torch.float64) else 8)) for v in per_frame.values())
+    n_keep = min(n_frames, (DUMP_BYTES_MAX - fixed) // row)
+    if n_keep < 1:
+        raise SystemExit(f"--dump-outputs: the step's outputs do not fit {DUMP_BYTES_MAX} bytes")
+    idx = np.arange(n_frames) if n_keep == n_frames else np.sort(np.random.default_rng(0).choice(n_frames, n_keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: _as_dump_array(v) for k, v in whole.items()}
+    if per_frame:
+        arrays["frame_index"] = idx.astype(np.float64)
+    for k, v in per_frame.items():
+        arrays[k] = _as_dump_array(v if n_keep == n_frames else v.index_select(0, torch.from_numpy(idx).to(v.device)))
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def _cabi_build_info():
     from multiview_motion_capture_amd import _cabi
     return _cabi.build_info()
@@ -341,7 +364,7 @@ def shelf_line(args, d):
             tracker.update_4d(k + 1, fr, None)
         return tracker
 
-    steps, warm = min(args.steps, 5), min(args.warmup, 1)
+    steps, warm = args.steps, min(args.warmup, 1)
     for _ in range(warm):
         one_pass()
     torch.cuda.synchronize()
@@ -350,6 +373,16 @@ def shelf_line(args, d):
         tr = one_pass()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # what the driver loop's caller holds after the last timed pass: every tracklet (live and dead, by id) and its per-frame poses
+        tracks = sorted(tr.tracklets + tr.dead_tracklets, key=lambda t: t.track_id)
+        rows = [(t.track_id, fi, pp, pose) for t in tracks for fi, pp, pose in t.poses]
+        dump_outputs(args.dump_outputs, {}, {
+            "tracklets": np.array([[t.track_id, t.state.value, t.hits, len(t)] for t in tracks], dtype=np.float64).reshape(-1, 4),
+            "pose_frames": np.array([[tid, fi] for tid, fi, _, _ in rows], dtype=np.float64).reshape(-1, 2),
+            "pose_params": np.array([np.concatenate([pp.root, pp.euler_angles.ravel(), pp.bone_lens]) for _, _, pp, _ in rows],
+                                    dtype=np.float64).reshape(-1, 68),
+            "pose_joints": np.array([pose.keypoints for _, _, _, pose in rows], dtype=np.float64).reshape(-1, 18, 3)}, n_frames)
     bpf = 12 * 5 * 8 * 25 + 4 * 5 * 8 + 16 * 4 * 25 + 488 * 4
     return {"metric": "frames/s (assoc+triangulate+IK), Shelf sequence frame by frame through MvTracker.update_4d",
             "value": n_frames * steps / dt, "unit": "frames/s", "n_gpus": 1, "steps": steps, "warmup": warm,
@@ -460,7 +493,12 @@ def main():
                          "+ triangulation, 10 steps) and config 2 (C5 P1, triangulation only, 2 M frames, 20 launches) as child runs of this script and report them under "
                          "'other_configs' (default: on for the default headline command at N = 1)")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float32 or "
+                         "float64, at most 64 MB in all (a fixed sample of frames, frame_index.npy, when the step's outputs are larger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.scaling = "weak"
     if args.frames_total:
         if args.frames_total % (args.gpus * args.chain_len):
@@ -539,7 +577,7 @@ def main():
             # synchronize bracket and max over ranks; the single-GPU configurations (1, 2, 3) are in the N = 1 line
             a5 = argparse.Namespace(**vars(args))
             a5.views, a5.people, a5.frames, a5.seed, a5.steps, a5.warmup, a5.sustain, a5.cpu_frames = 8, 8, 25008, 20260104, 3, 1, 0, 0
-            a5.host_io = 0
+            a5.host_io, a5.dump_outputs = 0, None
             t5 = time.perf_counter()
             r5 = run_workload(a5, rank, world, d)
             if rank == 0:
@@ -800,6 +838,11 @@ def run_workload(args, rank, world, d):
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        st = out.get("stitch") or {}
+        dump_outputs(args.dump_outputs, {k: out[k] for k in DUMP_PER_FRAME if isinstance(out.get(k), torch.Tensor)},
+                     {**{k: out[k] for k in DUMP_PER_CHAIN if isinstance(out.get(k), torch.Tensor)},
+                      **{"stitch_" + k: st[k] for k in DUMP_STITCH if isinstance(st.get(k), torch.Tensor)}}, F)
     per_rank_ms = [dt / args.steps * 1e3]
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=d if args.backend == "nccl" else "cpu")

@@ -47,3 +47,34 @@ def test_als_histogram_and_the_defaults_of_the_command_line():
     assert r.returncode != 0 and "--frames-total" in r.stderr
     assert bench.OTHER_CONFIGS[-1][1][-2:] == ["--dlt-out", "f64"]           # config 2 with the reference's output dtype rides along
     assert bench.DEFAULT_NCCL_MAX_NCHANNELS == "4" and bench.OTHER_CONFIGS[1][1][:6] == ["--views", "8", "--people", "8", "--frames", "25008"]
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every file float32 / float64, integer tables exact, and a step larger than the budget written as a fixed, seeded
+    sample of frames (the same frames on every run) that keeps the files under DUMP_BYTES_MAX."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    F = 640
+    per_frame = {"joints": torch.arange(F * 8 * 54, dtype=torch.float64).reshape(F, 8, 18, 3),
+                 "meta": torch.arange(F * 8 * 4, dtype=torch.int32).reshape(F, 8, 4),
+                 "pts3d": torch.ones((F * 2, 17, 4), dtype=torch.float32)}                 # (frames x people first: reshaped per frame)
+    whole = {"next_id": torch.arange(F // 16, dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), per_frame, whole, F)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").iterdir()}
+    assert set(got) == {"joints", "meta", "pts3d", "next_id", "frame_index"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["meta"], per_frame["meta"].numpy()) and got["pts3d"].shape == (F, 2, 17, 4)
+    assert np.array_equal(got["frame_index"], np.arange(F))
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 1_000_000)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), per_frame, whole, F)
+    size = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    a, b = ({p.stem: np.load(p) for p in (tmp_path / r).iterdir()} for r in ("a", "b"))
+    idx = a["frame_index"].astype(np.int64)
+    assert size <= 1_000_000 and 0 < len(idx) < F and np.all(np.diff(idx) > 0)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["joints"], per_frame["joints"].numpy()[idx])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
