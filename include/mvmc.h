@@ -385,9 +385,9 @@ typedef struct mvmcChainBuffers {
     /* inputs */
     const double* kps17;        /* (F,C,P,17,3) after mvmc_ingest */
     const int32_t* counts;      /* (F,C) */
-    const double* Pmats;        /* (C,3,4) */
-    const float* Fmats;         /* (C,C,3,3) from mvmc_fmats */
-    const double* F2;           /* (C,C,3,3) from mvmc_fmats_from_projections */
+    const double* Pmats;        /* (C,3,4); mvmc_chain_run_rigs: (R,C,3,4), R = n_rigs */
+    const float* Fmats;         /* (C,C,3,3) from mvmc_fmats; mvmc_chain_run_rigs: (R,C,C,3,3) */
+    const double* F2;           /* (C,C,3,3) from mvmc_fmats_from_projections; mvmc_chain_run_rigs: (R,C,C,3,3) */
     const double* seed_table;   /* mvmc_als_seed_table, on the device */
     /* tracker state, in/out (zero-initialised for fresh chains) */
     double* params;             /* (B,T,68) */
@@ -429,13 +429,22 @@ typedef struct mvmcChainBuffers {
                                    too large for the kernel's ALS variant, flags[B + 2] != 0 = a capacity was exceeded in some chain
                                    (bit 0: a cluster, a member or a view block dropped, bit 1: more than t_max tracklets),
                                    flags[B + 4 + b] = the void word of chain b (bits 0, 1 as before, bit 2 = graph too large, bit 3 =
-                                   internal: a meeting of two IK waves timed out, builds with -DMVMC_WITH_IK_PAIR only): a
+                                   internal: a meeting of two IK waves timed out, builds with -DMVMC_WITH_IK_PAIR only, bit 4 =
+                                   mvmc_chain_run_rigs: the chain's rig index is outside [0, n_rigs) -- no calibration was read,
+                                   its frames are empty tables, out_n_tracks = 0; also raised in flags[B + 2]): a
                                    non-zero word voids the chain's results (all chains' after a time-out); from 2 B + 4 on: the
                                    ticket counter (hand_over 1, 2), the ready queue's tail and ring (hand_over == 1) */
     double* out_phase_cycles;   /* (B,8) diagnostic: shader cycles of each chain by phase {graph, ALS, assignment, IK, commit,
                                    outputs, whole chain, 0}, or NULL */
 } mvmcChainBuffers;
 int mvmc_chain_run(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buffers, mvmcStream_t stream);
+
+/* mvmc_chain_run with a calibration per chain: buffers->Pmats, Fmats and F2 hold n_rigs rigs of n_views cameras each
+ * ((R,C,3,4), (R,C,C,3,3), (R,C,C,3,3)), and chain b uses rig rig_of_chain[b] ((n_chains) i32 device, or NULL: rig 0 for every
+ * chain).  A chain whose index lies outside [0, n_rigs) reads no calibration: bit 4 of its void word, empty tables.  n_rigs < 1, or
+ * rig_of_chain == NULL with n_rigs != 1: MVMC_ERR_ARG.  mvmc_chain_run(s, b, st) is mvmc_chain_run_rigs(s, b, NULL, 1, st). */
+int mvmc_chain_run_rigs(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buffers, const int32_t* rig_of_chain, int n_rigs,
+                        mvmcStream_t stream);
 
 #ifdef __cplusplus
 }

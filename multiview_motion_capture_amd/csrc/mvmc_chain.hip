@@ -43,9 +43,9 @@ struct MvmcChainArgs {
     // inputs
     const double* kps17;      // (F,C,P,17,3), F = n_chains * L, chain b owns frames [b L, (b+1) L)
     const int32_t* counts;    // (F,C)
-    const double* Pm;         // (C,3,4)
-    const float* Fm;          // (C,C,3,3) f32 (match_spatial)
-    const double* F2;         // (C,C,3,3) f64 (match_spatial_time)
+    const double* Pm;         // (R,C,3,4)        R = n_rigs calibrations; chain b uses rig[b] (rig 0 when rig is NULL)
+    const float* Fm;          // (R,C,C,3,3) f32 (match_spatial)
+    const double* F2;         // (R,C,C,3,3) f64 (match_spatial_time)
     const double* seed;       // RandomState(0).rand() table
     int seed_len;
     int n_chains, L, C, P, T, K, V, nfev_cold, nfev_warm, n_inits;
@@ -91,10 +91,13 @@ struct MvmcChainArgs {
                               // 2: a workgroup draws a ticket when it starts and (part, chain) = ticket, as in 0
     unsigned* flags;          // (2 B + 4): [0,B) parts completed per chain; [B] time-out, [B+1] graph too large, [B+2] capacity word of
                               // the launch; [B+4+b] the void word of chain b (bit 0 views / clusters, bit 1 tracklet table, bit 2 graph
-                              // too large for the layout's association variant); [2B+4] ticket counter, [2B+5] ring tail,
+                              // too large for the layout's association variant, bit 4 rig index outside [0, n_rigs): the chain's
+                              // frames are left as empty tables); [2B+4] ticket counter, [2B+5] ring tail,
                               // [2B+6 ...) ready ring of B * (parts - 1) entries (queue mode).  Zeroed by the launcher
     int self_zero;            // 1: ONE chain run by ONE workgroup of the latency build zeroes the words itself (no memset in front of
                               // the launch: a device operation less per frame of MvTracker.update_4d)
+    const int32_t* rig;       // (B) calibration of each chain, in [0, n_rigs), or NULL: rig 0 for every chain
+    int n_rigs;
 };
 
 
@@ -106,6 +109,22 @@ using ChainArgs = MvmcChainArgs;
 // copy the 368-byte struct to the stack of every lane at kernel entry (24 sixteen-byte scratch stores per lane: 98 KB per workgroup,
 // i.e. per frame -- 1 GB per launch) and read every field back from scratch.
 using ChainArgsK = const __attribute__((address_space(4))) MvmcChainArgs;
+
+// A chain's calibration: the base pointers of its rig in the (R, ...) arrays, wave-uniform.  An index outside [0, n_rigs) is never
+// dereferenced: ok = false and the pointers stay at rig 0 (the kernel then runs no frame of the chain and sets bit 4 of its void word).
+struct ChainRig { const double* Pm; const float* Fm; const double* F2; bool ok; };
+__device__ __forceinline__ ChainRig chain_rig(ChainArgsK& A, int b) {
+    ChainRig g{A.Pm, A.Fm, A.F2, true};
+    if (A.rig) {
+        const int r = uni(mvmc_ld_i32(A.rig + b));
+        g.ok = r >= 0 && r < A.n_rigs;
+        if (g.ok && r > 0) {
+            const size_t C = (size_t)A.C;
+            g.Pm += (size_t)r * C * 12; g.Fm += (size_t)r * C * C * 9; g.F2 += (size_t)r * C * C * 9;
+        }
+    }
+    return g;
+}
 
 // Two layouts.  SMALL (configs 1-4: N = C P <= 40 nodes, <= 6 views per person): the rank-8 workgroup ALS variants, 52 KB of LDS,
 // three workgroups per CU.  BIG (config 5, C8 P8: N <= 64, N + T <= 72, <= 8 views per person): the generic workgroup ALS (rank
@@ -158,18 +177,22 @@ static_assert(sizeof(ChainArena<true>) <= 150 * 1024, "BIG: one workgroup per CU
 // functions -- with it each phase saved and restored, per call and per lane, every callee-saved vector register it touches (58 for the
 // IK phase), whether the kernel had anything live there or not.
 template <bool BIG>
-__device__ __noinline__ void chain_graph_spatial(ChainArena<BIG>& arena_in, ChainArgsK& A, int b, int f, int* done) {
+__device__ __noinline__ void chain_graph_spatial(ChainArena<BIG>& arena_in, ChainArgsK& A, int b, int f, const float* Fm_in, int* done) {
     ChainArena<BIG>& arena = *uni(&arena_in);
     MVMC_ASSUME_LDS(&arena);
     const int C = A.C, P = A.P, N = C * P;
     float* S = A.S_sp + (size_t)b * N * N;
-    if ((threadIdx.x >> 6) == 0) affinity_wave(arena.graph, A.kps17, A.counts, A.Fm, C, P, f, nullptr, S);
+    const float* Fm = uni(Fm_in);
+    if ((threadIdx.x >> 6) == 0) affinity_wave(arena.graph, A.kps17, A.counts, Fm, C, P, f, nullptr, S);
     *done = 0;
 }
 template <bool BIG>
-__device__ __noinline__ void chain_graph_temporal(ChainArena<BIG>& arena_in, ChainArgsK& A, int b, int f, bool pairs_ready, int* done) {
+__device__ __noinline__ void chain_graph_temporal(ChainArena<BIG>& arena_in, ChainArgsK& A, int b, int f, bool pairs_ready, const double* Pm_in,
+                                          const double* F2_in, int* done) {
     ChainArena<BIG>& arena = *uni(&arena_in);
     MVMC_ASSUME_LDS(&arena);
+    const double* Pm = uni(Pm_in);
+    const double* F2 = uni(F2_in);
     const int C = A.C, P = A.P, T = A.T, NS = T + C * P;
     double* W = A.W_st + (size_t)b * NS * NS;
     // BIG: the frame's keypoints through LDS (config 5: + 0.7 %).  SMALL keeps reading them from global memory: its pose-pair block is
@@ -181,19 +204,19 @@ __device__ __noinline__ void chain_graph_temporal(ChainArena<BIG>& arena_in, Cha
         st_stage_keypoints(kf, A.kps17, f, C, P);
         __syncthreads();
         if (2 * 4 * P * 68 <= CH_KOFF_BIG && C * P <= 64) {       // the pair errors by line tables (config 5: P = 8)
-            st_pose_pairs_lines<ChainCfg<BIG>::NT>(arena.graph + CH_EOFF_BIG, arena.graph, kf, A.counts, f, A.F2, C, P, 0.1);
+            st_pose_pairs_lines<ChainCfg<BIG>::NT>(arena.graph + CH_EOFF_BIG, arena.graph, kf, A.counts, f, F2, C, P, 0.1);
             Epre = arena.graph + CH_EOFF_BIG;
         }
     }
-    st_affinity_wave<ChainCfg<BIG>::NT>(arena.graph, A.kps17, A.counts, 0, f, A.joints + (size_t)b * T * 54, A.n_tracks + b, A.Pm, A.F2, C, P,
+    st_affinity_wave<ChainCfg<BIG>::NT>(arena.graph, A.kps17, A.counts, 0, f, A.joints + (size_t)b * T * 54, A.n_tracks + b, Pm, F2, C, P,
                            T, 0.1, W, nullptr, A.gc + (size_t)b * (C + 1), Epre, C * P, kf);
     *done = 0;
 }
 // the frame's 2-D / 2-D distances, made while the workgroup waits for its predecessor (they do not depend on the tracklets)
-__device__ __noinline__ void chain_pose_pairs(ChainArena<false>& arena_in, ChainArgsK& A, int f, int* done) {
+__device__ __noinline__ void chain_pose_pairs(ChainArena<false>& arena_in, ChainArgsK& A, int f, const double* F2_in, int* done) {
     ChainArena<false>& arena = *uni(&arena_in);
     MVMC_ASSUME_LDS(&arena);
-    st_pose_pairs(arena.graph + CH_EOFF, A.kps17, A.counts, f, A.F2, A.C, A.P, 0.1);
+    st_pose_pairs(arena.graph + CH_EOFF, A.kps17, A.counts, f, uni(F2_in), A.C, A.P, 0.1);
     *done = 0;
 }
 template <bool BIG>
@@ -244,8 +267,9 @@ __device__ __noinline__ void chain_commit(ChainArgsK& A, int b, int* done) {
     *done = 0;
 }
 template <bool BIG>
-__device__ __noinline__ void chain_ik(ChainArena<BIG>& arena_in, const Ik1Tables& tables, ChainArgsK& A, int b, int* done) {
+__device__ __noinline__ void chain_ik(ChainArena<BIG>& arena_in, const Ik1Tables& tables, ChainArgsK& A, int b, const double* Pm_in, int* done) {
     ChainArena<BIG>& arena = *uni(&arena_in);
+    const double* Pm = uni(Pm_in);
     MVMC_ASSUME_LDS(&arena);
     MVMC_ASSUME_LDS(&tables);
     constexpr int NW = ChainCfg<BIG>::NT / 64, POOL = ChainCfg<BIG>::POOL;
@@ -273,7 +297,7 @@ __device__ __noinline__ void chain_ik(ChainArena<BIG>& arena_in, const Ik1Tables
         const int p = b * NP + s;
         const int base = uni(__shfl(excl, s, 64)), n_valid = uni(__shfl(cnt, s, 64));
         const int room = base < POOL ? POOL - base : 0;     // (a frame with more poses than POOL: the problem is cut short and flagged)
-        ik1_solve(arena.ikp.ik[wave], arena.ikp.mq + (base < POOL ? base : 0), arena.ikp.mc + (base < POOL ? base : 0), room, tables, A.kps17, A.Pm, A.members,
+        ik1_solve(arena.ikp.ik[wave], arena.ikp.mq + (base < POOL ? base : 0), arena.ikp.mc + (base < POOL ? base : 0), room, tables, A.kps17, Pm, A.members,
                   p, A.V, A.C, A.P, A.init, A.cold, A.nfev_cold, A.nfev_warm, A.ik_params, A.ik_joints, A.ik_info,
                   A.ik_scratch + (ptrdiff_t)(b * NW + wave - p) * MVMC_IK_SCRATCH_DOUBLES, 3, nullptr,
                   reinterpret_cast<int32_t*>(A.flags + A.n_chains + 4 + b), n_valid, pair_dS, pair_dhh, wave & 1);
@@ -350,12 +374,14 @@ chain_kernel(Ik1Tables tables_arg, ChainArgs A_by_value) {
     }
     int b, part;
     int done = 0;   // the phases' report word (see above)
+    ChainRig rig{A.Pm, A.Fm, A.F2, true};   // the chain's calibration, read once the chain is known
     if (!queue) {
         const int idx = by_ticket ? uni(s_nt) : (int)blockIdx.x;
         b = idx % A.n_chains; part = idx / A.n_chains;
+        rig = chain_rig(A, b);
         // work that does not depend on the chain's state comes before the hand-over: for a workgroup that has a predecessor, the
         // pose-pair block of its first frame's graph
-        if constexpr (!BIG) { if (part > 0) chain_pose_pairs(arena, A, b * A.L + part * A.L / A.parts, &done); }
+        if constexpr (!BIG) { if (part > 0 && rig.ok) chain_pose_pairs(arena, A, b * A.L + part * A.L / A.parts, rig.F2, &done); }
     }
     if (queue || part > 0) {
         // consumer side of the hand-off (cdna_hip_programming.md Guideline 16): one lane polls ONE word relaxed (the chain's flag, or
@@ -400,10 +426,19 @@ chain_kernel(Ik1Tables tables_arg, ChainArgs A_by_value) {
         const int task = uni(s_task);
         if (task < 0) return;
         b = task & 0xFFFFF; part = task >> 20;
-        if constexpr (!BIG) { if (queue && part > 0) chain_pose_pairs(arena, A, b * A.L + part * A.L / A.parts, &done); }
+        if (queue) {
+            rig = chain_rig(A, b);
+            if constexpr (!BIG) { if (part > 0 && rig.ok) chain_pose_pairs(arena, A, b * A.L + part * A.L / A.parts, rig.F2, &done); }
+        }
     }
     const int T = A.T, NP = T + A.K;
-    const int t_lo = part * A.L / A.parts, t_hi = (part + 1) * A.L / A.parts;
+    const int t_lo = part * A.L / A.parts;
+    int t_hi = (part + 1) * A.L / A.parts;
+    if (!rig.ok) {   // a rig index outside [0, n_rigs): bit 4 of the void word, the part's frames left as empty tables, nothing run
+        for (int t = t_lo + tid; t < t_hi; t += ChainCfg<BIG>::NT) A.out_n[b * A.L + t] = 0;
+        if (tid == 0) atomicOr(A.flags + A.n_chains + 4 + b, 16u);
+        t_hi = t_lo;
+    }
     __syncthreads();
     long long cyc[6] = {0, 0, 0, 0, 0, 0}, t_prev = clock64();
     const long long t_start = t_prev;
@@ -418,12 +453,12 @@ chain_kernel(Ik1Tables tables_arg, ChainArgs A_by_value) {
         if constexpr (!BIG) __builtin_amdgcn_s_setprio(MVMC_PRIO_ALS);
 #endif
         if (nt <= 0) {   // no live tracklets: match_spatial (motion_capture.py:597-631), f32 affinity
-            chain_graph_spatial<BIG>(arena, A, b, f, &done);
+            chain_graph_spatial<BIG>(arena, A, b, f, rig.Fm, &done);
             __syncthreads();
             lap(0);
             chain_als_spatial<BIG>(arena, A, b, f, &done);
         } else {
-            chain_graph_temporal<BIG>(arena, A, b, f, part > 0 && t == t_lo, &done);   // (the pose-pair block of a part's first frame is ready)
+            chain_graph_temporal<BIG>(arena, A, b, f, part > 0 && t == t_lo, rig.Pm, rig.F2, &done);   // (the pose-pair block of a part's first frame is ready)
             __syncthreads();
             lap(0);
             chain_als_temporal<BIG>(arena, A, b, &done);
@@ -445,7 +480,7 @@ chain_kernel(Ik1Tables tables_arg, ChainArgs A_by_value) {
 #ifdef MVMC_PRIO_REST
         if constexpr (!BIG) __builtin_amdgcn_s_setprio(0);
 #endif
-        chain_ik<BIG>(arena, tables, A, b, &done);
+        chain_ik<BIG>(arena, tables, A, b, rig.Pm, &done);
 #ifdef MVMC_PRIO_REST
         if constexpr (!BIG) __builtin_amdgcn_s_setprio(MVMC_PRIO_REST);
 #endif
@@ -469,7 +504,7 @@ chain_kernel(Ik1Tables tables_arg, ChainArgs A_by_value) {
     }
     // the chain's void word (assignment, IK pool, commit) into the launch's capacity word
     if (tid == 0) {
-        const unsigned v = __hip_atomic_load(A.flags + A.n_chains + 4 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xBu;   // (bit 3: mvmc_ik_pair.h's net)
+        const unsigned v = __hip_atomic_load(A.flags + A.n_chains + 4 + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0x1Bu;   // (bit 3: mvmc_ik_pair.h's net)
         if (v) atomicOr(A.flags + A.n_chains + 2, v);
     }
     if (done != 0) return;   // (never: the phases write 0)
@@ -531,7 +566,13 @@ int mvmc_chain_launch_big(const void* tables_host, const MvmcChainArgs& A, int n
 }
 #else
 extern "C" int mvmc_chain_run(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buf, mvmcStream_t stream) {
+    return mvmc_chain_run_rigs(skel_host, buf, nullptr, 1, stream);
+}
+
+extern "C" int mvmc_chain_run_rigs(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buf, const int32_t* rig_of_chain, int n_rigs,
+                                   mvmcStream_t stream) {
     if (!skel_host || !buf) return MVMC_ERR_ARG;
+    if (n_rigs < 1 || (!rig_of_chain && n_rigs != 1)) return MVMC_ERR_ARG;
     const mvmcChainBuffers& B = *buf;
     if (B.n_chains < 0 || B.chain_len <= 0 || B.n_views <= 0 || B.p_max <= 0 || B.t_max <= 0 || B.k_max <= 0 || B.v_max <= 0)
         return MVMC_ERR_ARG;
@@ -577,6 +618,7 @@ extern "C" int mvmc_chain_run(const mvmcSkeleton* skel_host, const mvmcChainBuff
     if (B.n_chains >= (1 << 20) || A.parts >= (1 << 10)) return MVMC_ERR_UNSUPPORTED;   // (a ring entry is part << 20 | chain)
     A.flags = B.flags;
     A.self_zero = 0;
+    A.rig = rig_of_chain; A.n_rigs = n_rigs;
     // Few workgroups (a frame at a time, short sequences): the 256-register build of the same kernel (mvmc_chain_lat.hip), see below
     bool lat = false;
     if (small) {

@@ -453,3 +453,44 @@ def run_main(video_dir: Optional[Path], pose_dir: Path, out_dir: Path, n_test: i
     with open(f'{out_dir}/tracklets.pkl', 'wb') as fh:
         pickle.dump(file=fh, obj={"tracklets": all_tlets})
     return all_tlets
+
+
+def run_main_batched(pose_dirs: List[Path], out_dirs: List[Path], n_test: int = 300, chain_len: int = 16):
+    """run_main for several sequences in one call, through the batched path (sequences.track_sequences): for every pose_dir the same
+    frames as run_main (the per-frame pickles frm_idx = 1 .. n_test), filter_bad_pose(0.01, 4, 5), then ONE chain-kernel launch per
+    camera count for all sequences, each with its own calibration (the first selected frame's).  Each sequence's tracklets -- longest
+    first -- go to its out_dir/tracklets.pkl as {"tracklets": [...]}; returns the lists.  These are the batched semantics (chains of
+    chain_len frames that cold-start, identities carried across chain boundaries by the stitch), not frame-by-frame update_4d:
+    INTEGRATION.md, section C."""
+    from .sequences import track_sequences
+    if len(pose_dirs) != len(out_dirs):
+        raise ValueError("run_main_batched: one out_dir per pose_dir")
+    seqs = []
+    for pose_dir in pose_dirs:
+        paths = sorted(Path(pose_dir).glob('*.pkl'), key=lambda path: int(path.stem))
+        last = min(len(paths) - 1, n_test)        # run_main's loop: frm_idx = 1 .. min(n_test, files - 1)
+        frames = []
+        for frm_idx in range(1, last + 1):
+            d_frames = load_pickle(paths[frm_idx], 'rb')
+            frames.append([filter_bad_pose(frm, min_valid_kps_score=0.01, n_min_valid_kps=4, min_valib_bb_size=5) for frm in d_frames])
+        if not frames:
+            raise ValueError(f"run_main_batched: {pose_dir} has no frame after the first")
+        C = len(frames[0])
+        P = max(1, max(len(frm.poses) for fr in frames for frm in fr))
+        kps = np.zeros((len(frames), C, P, 17, 3))
+        cnt = np.zeros((len(frames), C), dtype=np.int32)
+        for f, fr in enumerate(frames):
+            if len(fr) != C:
+                raise ValueError(f"run_main_batched: {pose_dir}: frame {f + 1} has {len(fr)} views, the first {C}")
+            for c, frm in enumerate(fr):
+                cnt[f, c] = len(frm.poses)
+                for k, pose in enumerate(frm.poses.values()):
+                    kps[f, c, k, :, :2] = pose.keypoints
+                    kps[f, c, k, :, 2] = np.asarray(pose.keypoints_score).ravel()
+        seqs.append((kps, cnt, [frm.calib for frm in frames[0]]))
+    results = track_sequences(seqs, chain_len=chain_len, frame_idx0=1)
+    for out_dir, tlets in zip(out_dirs, results):
+        os.makedirs(out_dir, exist_ok=True)
+        with open(f'{out_dir}/tracklets.pkl', 'wb') as fh:
+            pickle.dump(file=fh, obj={"tracklets": tlets})
+    return results

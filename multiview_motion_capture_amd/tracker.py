@@ -9,7 +9,7 @@ associate_tracking does (motion_capture.py:829-835).
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import torch
@@ -374,7 +374,7 @@ def run_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor], c
 def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor], chain_len: int, t_max: Optional[int] = None,
                      nfev_cold=50, nfev_warm=5, want_info=False, k_max: Optional[int] = None, v_max: Optional[int] = None,
                      parts: Optional[int] = None, kernel_events: Optional[list] = None, force_big: bool = False,
-                     hand_over: Optional[str] = None):
+                     hand_over: Optional[str] = None, rigs: Optional[Sequence[HotPath]] = None, rig_of_chain=None):
     """run_chains in ONE launch (mvmc_chain_run): a persistent workgroup per chain runs graph -> ALS -> assignment ->
     IK -> commit for the chain's frames, so every chain advances at its own pace instead of waiting, stage by stage,
     for the slowest member of every launch.  Same device code and the same results as run_chains.
@@ -385,7 +385,10 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
     hand_over: "ticket" (default: a workgroup draws a ticket when it starts, ticket = part * n_chains + chain; a part's predecessor
     holds a lower ticket, so it has started: no assumption about the order of dispatch), "static" (the same mapping by block index:
     relies on in-order dispatch, bounded wait) or "queue" (ready queue: a freed slot goes to the chain that has been ready longest;
-    no assumption either, ~3 % slower).  Same results bit for bit."""
+    no assumption either, ~3 % slower).  Same results bit for bit.
+    rigs / rig_of_chain: a calibration per chain (mvmc_chain_run_rigs) -- ``rigs`` is a sequence of HotPath, one per rig, all with the
+    cameras of ``kps``; chain b uses rigs[rig_of_chain[b]] (a host integer array of length B, checked here).  ``hp`` still supplies the
+    skeleton.  With rigs=None the call is exactly the one-rig launch (mvmc_chain_run)."""
     import ctypes as C
     from . import _cabi
     F, Cn, P = kps.shape[:3]
@@ -393,6 +396,9 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
     if F % L:
         raise ValueError("run_chains_fused: the frame count must be a multiple of the chain length")
     B = F // L
+    if rigs is None and rig_of_chain is not None:
+        raise ValueError("run_chains_fused: rig_of_chain needs rigs")
+    roc = None if rigs is None else check_rig_of_chain(rig_of_chain, B, len(rigs))
     if parts is None:
         parts = L   # one workgroup per chain-frame: the finest hand-over, the best balance
     # tracklet slots: 8 on the SMALL layout (views x people <= 40: its association variants hold rank 16), 16 on the BIG one (C8 P8),
@@ -404,13 +410,16 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
     N, NS, NP = Cn * P, T + Cn * P, T + K
     kps17, cnt = dev.ingest(kps, counts)
     d = kps.device
-    F2 = dev.fmats_from_projections(hp.P)
+    if rigs is None:
+        Pm, Fm, F2 = hp.P, hp.F, dev.fmats_from_projections(hp.P)
+    else:
+        Pm, Fm, F2 = stack_rigs(rigs, Cn)
     seed = dev.als_seed_table(_cabi.MAX_NODES * _cabi.MAX_NODES, d)
     f64, i32 = torch.float64, torch.int32
     z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)
     e = lambda shape, dt: torch.empty(shape, dtype=dt, device=d)
     t = dict(
-        kps17=kps17, counts=cnt, Pmats=hp.P, Fmats=hp.F, F2=F2, seed_table=seed,
+        kps17=kps17, counts=cnt, Pmats=Pm, Fmats=Fm, F2=F2, seed_table=seed,
         params=z((B, T, 68), f64), joints=z((B, T, 18, 3), f64), meta=z((B, T, 4), i32), n_tracks=z((B,), i32),
         next_id=z((B,), i32), n_dead=z((B,), i32), slot_src=torch.full((B, T), -1, dtype=i32, device=d),
         S_sp=e((B, N, N), torch.float32), W_st=e((B, NS, NS), f64), group_counts=e((B, Cn + 1), i32),
@@ -436,11 +445,17 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
         setattr(buf, name, int(val))
     for name, ten in t.items():
         setattr(buf, name, None if ten is None else ten.data_ptr())
+    rig_dev = None if roc is None else torch.from_numpy(roc).to(d)
     if kernel_events is not None:
         k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         k0.record()
-    _cabi.check(_cabi.load().mvmc_chain_run(C.byref(hp.skeleton), C.byref(buf),
-                                            C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "mvmc_chain_run")
+    stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+    if rigs is None:
+        _cabi.check(_cabi.load().mvmc_chain_run(C.byref(hp.skeleton), C.byref(buf), stream), "mvmc_chain_run")
+    else:
+        _cabi.check(_cabi.load().mvmc_chain_run_rigs(C.byref(hp.skeleton), C.byref(buf), C.c_void_p(rig_dev.data_ptr()), len(rigs),
+                                                     stream), "mvmc_chain_run_rigs")
+        t["rig_of_chain"] = rig_dev
     if kernel_events is not None:
         k1.record()
         kernel_events.append((k0, k1))
@@ -450,11 +465,46 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
     res = dict(params=t["out_params"], joints=t["out_joints"], meta=t["out_meta"], n_tracks=t["out_n_tracks"],
                n_dead=t["n_dead"], next_id=t["next_id"], flags=t["flags"], void=t["flags"][B + 4:2 * B + 4],
                void_words=t["flags"][B:B + 3], n_chains=B, chain_len=L, _keepalive=t)
+    if rigs is not None:
+        res["rigs"], res["rig_of_chain"] = list(rigs), roc
     if want_info:
         res["ik_info"] = t["out_info"].view(B, L, NP, 8)
         res["als_iters"] = t["out_als_iters"].view(B, L)
         res["phase_cycles"] = t["out_phase_cycles"]
     return res
+
+
+def check_rig_of_chain(rig_of_chain, n_chains: int, n_rigs: int) -> np.ndarray:
+    """rig_of_chain as the int32 array mvmc_chain_run_rigs reads, checked on the host: length n_chains, every index in [0, n_rigs)."""
+    if n_rigs < 1:
+        raise ValueError("rigs: at least one rig")
+    if rig_of_chain is None:
+        if n_rigs != 1:
+            raise ValueError("rig_of_chain: needed with more than one rig")
+        return np.zeros(n_chains, dtype=np.int32)
+    if isinstance(rig_of_chain, torch.Tensor):
+        rig_of_chain = rig_of_chain.cpu().numpy()
+    a = np.asarray(rig_of_chain)
+    if a.ndim != 1 or a.shape[0] != n_chains:
+        raise ValueError(f"rig_of_chain: {a.shape} for {n_chains} chains")
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"rig_of_chain: integer indices, not {a.dtype}")
+    if a.size and (a.min() < 0 or a.max() >= n_rigs):
+        raise ValueError(f"rig_of_chain: indices in [{a.min()}, {a.max()}], the call has {n_rigs} rig(s)")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def stack_rigs(rigs: Sequence[HotPath], n_views: int):
+    """(P (R,C,3,4) f64, F (R,C,C,3,3) f32, F2 (R,C,C,3,3) f64) of R HotPaths of n_views cameras each: mvmc_chain_run_rigs' tables."""
+    if len(rigs) == 0:
+        raise ValueError("rigs: at least one rig")
+    for r, h in enumerate(rigs):
+        if h.P.shape[0] != n_views:
+            raise ValueError(f"rigs[{r}] has {h.P.shape[0]} cameras, the keypoints {n_views} views")
+    Pm = torch.stack([h.P for h in rigs]).contiguous()
+    Fm = torch.stack([h.F for h in rigs]).contiguous()
+    F2 = torch.stack([dev.fmats_from_projections(h.P) for h in rigs]).contiguous()
+    return Pm, Fm, F2
 
 
 def check_chain_flags(res) -> None:
@@ -475,6 +525,9 @@ def check_chain_flags(res) -> None:
     ov = int(void.max()) if B else 0
     if ov & 8:
         raise RuntimeError("mvmc_chain_run: a meeting of two IK waves timed out (mvmc_ik_pair.h); results are void")
+    if ov & 16:
+        raise ValueError(f"mvmc_chain_run_rigs: the rig index of {int(((void & 16) != 0).sum())} chain(s) is outside [0, n_rigs): "
+                         "no calibration was read, their tables are empty")
     if ov & 4:
         raise ValueError("mvmc_chain_run: a frame's graph has more nodes than the chain kernel's layout supports (small layout: 24 "
                          "without, 32 with tracklets); repair_chains / run_chains take such data")
@@ -490,19 +543,25 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
     points with t_wide tracklet slots (association on up to 80 nodes, rank 32), and their rows of ``res`` (run_chains_fused's result,
     same kps / counts) are replaced; the per-frame tables are widened to the slots the repaired chains need.  Synchronises (it reads
     the void words); returns the number of chains repaired.  Raises if a hand-over timed out or a chain exceeds the repair tier too.
-    big_first: chains voided by the SMALL layout go through the chain kernel's BIG layout first (one launch), see below."""
+    big_first: chains voided by the SMALL layout go through the chain kernel's BIG layout first (one launch), see below.
+    A result of several rigs (run_chains_fused(..., rigs, rig_of_chain)) is repaired with each chain's own calibration; a chain whose
+    rig index was out of range (void bit 4) has nothing to repair: raises."""
     B, L = res["n_chains"], res["chain_len"]
     fl = res["flags"][B:B + 4].cpu().tolist()
     if fl[0]:
         raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
     if fl[2] & 8:
         raise RuntimeError("mvmc_chain_run: a meeting of two IK waves timed out (mvmc_ik_pair.h); results are void")
+    if fl[2] & 16:
+        raise ValueError("mvmc_chain_run_rigs: a chain's rig index is outside [0, n_rigs); such a chain is not repaired")
     if not (fl[1] or fl[2]):
         return 0
     idx = torch.nonzero(res["void"]).flatten()
     n = int(idx.numel())
     if n == 0:
         return 0
+    rigs = res.get("rigs")
+    roc = None if rigs is None else res["rig_of_chain"][idx.cpu().numpy()]
     C, P = kps.shape[1:3]
     k5 = kps.view(B, L, *kps.shape[1:])[idx].reshape(n * L, *kps.shape[1:]).contiguous()
     c5 = None if counts is None else counts.view(B, L, C)[idx].reshape(n * L, C).contiguous()
@@ -513,13 +572,17 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
         # 16 slots, 8 views): the same persistent kernel in its 512-thread form takes all of them in ONE launch (bit-identical to the
         # per-stage path, tests/test_gpu_chain_fused.py), which matters when a geometry voids EVERY chain (C5 P6 with everybody in view:
         # measured in tests/test_gpu_capacity_flags.py).  What is beyond that too falls through to the per-stage entry points below.
-        big = run_chains_fused(hp, k5, c5, L, t_max=t_wide, nfev_cold=nfev_cold, nfev_warm=nfev_warm, force_big=True)
+        big = run_chains_fused(hp, k5, c5, L, t_max=t_wide, nfev_cold=nfev_cold, nfev_warm=nfev_warm, force_big=True, rigs=rigs,
+                               rig_of_chain=roc)
         bfl = big["flags"][n:n + 4].cpu().tolist()
         if not bfl[0] and int(big["void"].max()) == 0:
             sub = dict(params=big["params"], joints=big["joints"], meta=big["meta"], n_tracks=big["n_tracks"], n_dead=big["n_dead"],
                        next_id=big["next_id"])
     if sub is None:
-        sub = run_chains(hp, k5, c5, L, t_max=t_wide, nfev_cold=nfev_cold, nfev_warm=nfev_warm)
+        if rigs is None:
+            sub = run_chains(hp, k5, c5, L, t_max=t_wide, nfev_cold=nfev_cold, nfev_warm=nfev_warm)
+        else:
+            sub = _run_chains_by_rig(rigs, roc, k5, c5, L, t_wide, nfev_cold, nfev_warm)
         ov = int(sub["overflow"].max())
         if ov:
             raise ValueError(f"repair_chains: a chain exceeds the repair tier as well (word {ov}: 2 = more than {t_wide} live tracklets, "
@@ -545,6 +608,32 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
     return n
 
 
+def _run_chains_by_rig(rigs, roc: np.ndarray, kps: torch.Tensor, counts: Optional[torch.Tensor], L: int, t_max: int, nfev_cold, nfev_warm):
+    """run_chains over chains of several rigs: the chains of each rig as one group with that rig's HotPath, the results in chain order."""
+    n = len(roc)
+    C = kps.shape[1]
+    k4 = kps.view(n, L, *kps.shape[1:])
+    c4 = None if counts is None else counts.view(n, L, C)
+    out = None
+    for r in np.unique(roc):
+        sel = np.nonzero(roc == r)[0]
+        at = torch.from_numpy(sel).to(kps.device)
+        m = len(sel)
+        part = run_chains(rigs[int(r)], k4[at].reshape(m * L, *kps.shape[1:]).contiguous(),
+                          None if c4 is None else c4[at].reshape(m * L, C).contiguous(), L, t_max=t_max, nfev_cold=nfev_cold,
+                          nfev_warm=nfev_warm)
+        if out is None:
+            out = {k: torch.empty((n * (L if k in _PER_FRAME else 1),) + v.shape[1:], dtype=v.dtype, device=v.device)
+                   for k, v in part.items()}
+        for k, v in part.items():
+            if k in _PER_FRAME:
+                out[k].view(n, L, *v.shape[1:])[at] = v.view(m, L, *v.shape[1:])
+            else:
+                out[k][at] = v
+    return out
+
+
+_PER_FRAME = ("params", "joints", "meta", "n_tracks")
 _CHAIN_SCRATCH = {}
 
 
