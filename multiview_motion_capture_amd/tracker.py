@@ -202,6 +202,9 @@ class ChainTracker:
             B = self.B
             fl = self._fused["flags"][B:B + 4].cpu().tolist()
             self._fused["flags"][B:B + 4].zero_()
+            if self._void_pending:      # (step_fused(fold_void=False) left the frame's void words where the launch wrote them)
+                ov |= int(np.bitwise_or.reduce(self._fused["flags"][B + 4:2 * B + 4].cpu().numpy())) if B else 0
+                self._void_pending = False
             if fl[0]:
                 raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
         self.overflow.zero_()
