@@ -446,6 +446,15 @@ int mvmc_chain_run(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buffer
 int mvmc_chain_run_rigs(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buffers, const int32_t* rig_of_chain, int n_rigs,
                         mvmcStream_t stream);
 
+/* mvmc_chain_run_rigs with chains that sit the launch out: active ((n_chains) u8 device, or NULL: every chain runs).  A chain with
+ * active[b] == 0 writes nothing -- not its state, not its out_* rows or out_phase_cycles row, not its void word, not flags[B + 1],
+ * flags[B + 2] -- and its rig index is not read, so an out-of-range index raises no bit 4.  The per-frame driver of many live rigs
+ * (multiview_motion_capture_amd/live.py) steps, in one launch of chain_len 1, the sessions that have a frame this tick.
+ * active != NULL with n_parts > 1: MVMC_ERR_ARG (an idle chain's first part would never hand over to its successors).
+ * mvmc_chain_run_rigs(s, b, r, n, st) is mvmc_chain_run_sessions(s, b, r, n, NULL, st). */
+int mvmc_chain_run_sessions(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buffers, const int32_t* rig_of_chain, int n_rigs,
+                            const uint8_t* active, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,7 @@ SYMBOLS = (
     "mvmc_affinity", "mvmc_als_associate", "mvmc_closure_labels", "mvmc_cluster_members", "mvmc_dlt", "mvmc_triangulate_postopt", "mvmc_fk", "mvmc_ik_solve",
     "mvmc_fmats_from_projections", "mvmc_st_affinity", "mvmc_track_assign", "mvmc_track_commit", "mvmc_debug_eigh",
     "mvmc_debug_trstep", "mvmc_ik_solve_stages", "mvmc_chain_run", "mvmc_svt_associate", "mvmc_debug_ik_solve_fd", "mvmc_debug_ik_model_step", "mvmc_ingest_dlt", "mvmc_ingest_dlt_f32", "mvmc_pack_message_words", "mvmc_pack_work_words", "mvmc_stitch_work_words", "mvmc_pack_tracks", "mvmc_stitch_chains",
-    "mvmc_chain_run_rigs",
+    "mvmc_chain_run_rigs", "mvmc_chain_run_sessions",
 )
 
 
@@ -122,6 +122,7 @@ def load():
         "mvmc_debug_trstep": [vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp],
         "mvmc_chain_run": [SK, C.POINTER(MvmcChainBuffers), vp],
         "mvmc_chain_run_rigs": [SK, C.POINTER(MvmcChainBuffers), vp, i32, vp],
+        "mvmc_chain_run_sessions": [SK, C.POINTER(MvmcChainBuffers), vp, i32, vp, vp],
         "mvmc_ik_solve_stages": [SK, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
         "mvmc_debug_ik_solve_fd": [SK, vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp],
         "mvmc_debug_ik_model_step": [SK, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp],

@@ -98,6 +98,7 @@ struct MvmcChainArgs {
                               // the launch: a device operation less per frame of MvTracker.update_4d)
     const int32_t* rig;       // (B) calibration of each chain, in [0, n_rigs), or NULL: rig 0 for every chain
     int n_rigs;
+    const uint8_t* active;    // (B) 0: the chain sits the launch out and writes nothing; NULL: every chain runs (parts == 1 when set)
 };
 
 
@@ -431,6 +432,10 @@ chain_kernel(Ik1Tables tables_arg, ChainArgs A_by_value) {
             if constexpr (!BIG) { if (part > 0 && rig.ok) chain_pose_pairs(arena, A, b * A.L + part * A.L / A.parts, rig.F2, &done); }
         }
     }
+    // an idle chain (mvmc_chain_run_sessions): the whole workgroup leaves before anything of the chain is written -- no state, no
+    // out_* row, no void or launch word; its rig index, read above, is not judged (no bit 4).  Wave-uniform: one byte per chain.
+    // (The launcher refuses `active` with parts > 1, so no successor waits for a flag this workgroup would have raised.)
+    if (A.active && uni((int)A.active[b]) == 0) return;
     const int T = A.T, NP = T + A.K;
     const int t_lo = part * A.L / A.parts;
     int t_hi = (part + 1) * A.L / A.parts;
@@ -571,9 +576,16 @@ extern "C" int mvmc_chain_run(const mvmcSkeleton* skel_host, const mvmcChainBuff
 
 extern "C" int mvmc_chain_run_rigs(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buf, const int32_t* rig_of_chain, int n_rigs,
                                    mvmcStream_t stream) {
+    return mvmc_chain_run_sessions(skel_host, buf, rig_of_chain, n_rigs, nullptr, stream);
+}
+
+extern "C" int mvmc_chain_run_sessions(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buf, const int32_t* rig_of_chain, int n_rigs,
+                                       const uint8_t* active, mvmcStream_t stream) {
     if (!skel_host || !buf) return MVMC_ERR_ARG;
     if (n_rigs < 1 || (!rig_of_chain && n_rigs != 1)) return MVMC_ERR_ARG;
     const mvmcChainBuffers& B = *buf;
+    // an idle chain's part 0 raises no hand-over flag: its later parts would wait out the time-out and void the launch
+    if (active && B.n_parts > 1) return MVMC_ERR_ARG;
     if (B.n_chains < 0 || B.chain_len <= 0 || B.n_views <= 0 || B.p_max <= 0 || B.t_max <= 0 || B.k_max <= 0 || B.v_max <= 0)
         return MVMC_ERR_ARG;
     if (B.max_nfev_cold < 1 || B.max_nfev_warm < 1) return MVMC_ERR_ARG;
@@ -619,6 +631,7 @@ extern "C" int mvmc_chain_run_rigs(const mvmcSkeleton* skel_host, const mvmcChai
     A.flags = B.flags;
     A.self_zero = 0;
     A.rig = rig_of_chain; A.n_rigs = n_rigs;
+    A.active = active;
     // Few workgroups (a frame at a time, short sequences): the 256-register build of the same kernel (mvmc_chain_lat.hip), see below
     bool lat = false;
     if (small) {

@@ -268,27 +268,16 @@ class MvTracker:
     def update_4d(self, frm_idx: int, d_frames: List[FrameData], debug_view_imgs=None):
         self._ensure(d_frames)
         ch = self._chain
-        C, P = len(d_frames), self._p_max
+        P = self._p_max
         # (the frame's inputs are written straight into the tracker's pinned staging buffer: one asynchronous copy to the device)
         inp = ch.frame_inputs()
-        kps, cnt = inp["kps_np"], inp["cnt_np"]
-        kps.fill(0.0)
-        cnt.fill(0)
-        for c, frm in enumerate(d_frames):
-            if len(frm.poses) > P:
-                raise ValueError(f"update_4d: more than p_max={P} people in view {c}")
-            for k, pose in enumerate(frm.poses.values()):
-                kps[0, c, k, :, :2] = pose.keypoints
-                kps[0, c, k, :, 2] = np.asarray(pose.keypoints_score).ravel()
-            cnt[0, c] = len(frm.poses)
+        n_nodes = pack_frame(inp["kps_np"], inp["cnt_np"], 0, d_frames, P)
         ch.upload_inputs()
         k_d, c_d = inp["kps_d"], inp["cnt_d"]
-        n_nodes = int(cnt.sum())
         # the state in front of the frame, should the frame have to be redone: the host mirror the last frame's read_back() left
         # (restore_previous), or -- first frame of a tracker, or after a frame that did not end in read_back -- a device snapshot
         snap = None if ch.has_previous else ch.snapshot()
-        # one launch per frame (the chain kernel) when the frame's graph fits its association variants, seven otherwise
-        one_launch = ch.fused_ok and (C * P > 40 or (n_nodes <= 24 and n_nodes + len(self.tracklets) <= 32))
+        one_launch = takes_one_launch(ch, n_nodes, len(self.tracklets))
         if one_launch:
             ch.step_fused(k_d, c_d, fold_void=False)      # (read_back() below reads the launch's void words itself)
         else:
@@ -316,10 +305,7 @@ class MvTracker:
                 raise
             self._chain = ch = wide
         # (only now, the frame having gone through: a frame that raises leaves the tracker -- host side included -- as it was)
-        for t in self.tracklets:
-            t.time_since_update += 1
         n = int(host["n_tracks"][0])
-        meta, params, joints = host["meta"][0, :n], host["params"][0, :n], host["joints"][0, :n]   # (views of a buffer the next frame overwrites: copied below)
         if ch.T > self._t_max:
             # the crowd has thinned out: back to the tables of the SMALL layout (a wide tracker's frame is one launch too, but of the BIG
             # layout -- a 512-thread workgroup with 129 KB of LDS, ~2 x the latency of the SMALL one's frame)
@@ -329,28 +315,58 @@ class MvTracker:
             if self._calm >= 8:
                 self._chain = ch = ch.narrowed(self._t_max)
                 self._calm = 0
-        alive = []
-        for k in range(n):
-            tid, state, hits, length = (int(v) for v in meta[k])
-            x = params[k]
-            pparam = PoseShapeParam(x[:3].copy(), x[3:57].reshape(18, 3).copy(), x[57:].copy())
-            pose = Pose(KpsFormat.BASIC_18, joints[k].copy(), np.ones((18, 1)), None)
-            t = self._by_id.get(tid)
-            if t is None:
-                t = MvTracklet(tid, frm_idx, pparam, pose)
-                self._by_id[tid] = t
-            elif hits > t.hits:
-                t.frame_idxs.append(frm_idx)
-                t.poses.append((frm_idx, pparam, pose))
-                t.time_since_update = 0
-            t.hits, t.state = hits, TrackState(state)
-            alive.append(t)
-        ids = {t.track_id for t in alive}
-        for t in self.tracklets:
-            if t.track_id not in ids:
-                t.state = TrackState.Dead
-                self.dead_tracklets.append(t)
-        self.tracklets = alive
+        commit_tables(self, frm_idx, host["meta"][0, :n], host["params"][0, :n], host["joints"][0, :n])
+
+
+def pack_frame(kps: np.ndarray, cnt: np.ndarray, row: int, d_frames: List[FrameData], p_max: int) -> int:
+    """A frame's 2-D poses into row ``row`` of a pinned staging buffer (kps (B,C,P,17,3), cnt (B,C)), zero padded; returns the frame's
+    graph nodes (poses).  More than p_max people in a view raises before anything is written."""
+    for c, frm in enumerate(d_frames):
+        if len(frm.poses) > p_max:
+            raise ValueError(f"update_4d: more than p_max={p_max} people in view {c}")
+    kps[row].fill(0.0)
+    cnt[row].fill(0)
+    for c, frm in enumerate(d_frames):
+        for k, pose in enumerate(frm.poses.values()):
+            kps[row, c, k, :, :2] = pose.keypoints
+            kps[row, c, k, :, 2] = np.asarray(pose.keypoints_score).ravel()
+        cnt[row, c] = len(frm.poses)
+    return int(cnt[row].sum())
+
+
+def takes_one_launch(ch, n_nodes: int, n_tracklets: int) -> bool:
+    """update_4d's route: one launch per frame (the chain kernel) when the tracker's tables fit it and the frame's graph fits its
+    association variants, the per-stage launches otherwise."""
+    return ch.fused_ok and (ch.C * ch.P > 40 or (n_nodes <= 24 and n_nodes + n_tracklets <= 32))
+
+
+def commit_tables(trk, frm_idx: int, meta: np.ndarray, params: np.ndarray, joints: np.ndarray) -> None:
+    """update_4d's tail: a committed frame's tracklet table (meta (n,4), params (n,68), joints (n,18,3) of the live tracklets) into the
+    host-side records of ``trk`` (tracklets, _by_id, dead_tracklets) -- one rule for MvTracker and the live session pool."""
+    for t in trk.tracklets:
+        t.time_since_update += 1
+    alive = []
+    for k in range(len(meta)):
+        tid, state, hits, length = (int(v) for v in meta[k])
+        x = params[k]
+        pparam = PoseShapeParam(x[:3].copy(), x[3:57].reshape(18, 3).copy(), x[57:].copy())
+        pose = Pose(KpsFormat.BASIC_18, joints[k].copy(), np.ones((18, 1)), None)
+        t = trk._by_id.get(tid)
+        if t is None:
+            t = MvTracklet(tid, frm_idx, pparam, pose)
+            trk._by_id[tid] = t
+        elif hits > t.hits:
+            t.frame_idxs.append(frm_idx)
+            t.poses.append((frm_idx, pparam, pose))
+            t.time_since_update = 0
+        t.hits, t.state = hits, TrackState(state)
+        alive.append(t)
+    ids = {t.track_id for t in alive}
+    for t in trk.tracklets:
+        if t.track_id not in ids:
+            t.state = TrackState.Dead
+            trk.dead_tracklets.append(t)
+    trk.tracklets = alive
 
 
 # ----------------------------------------------------------------------------------------------------

@@ -30,7 +30,10 @@ def default_caps(n_views: int, p_max: int):
 
 class ChainTracker:
     def __init__(self, hp: HotPath, n_chains: int, p_max: int, t_max: int = 8, k_max: Optional[int] = None,
-                 v_max: Optional[int] = None, nfev_cold=50, nfev_warm=5):
+                 v_max: Optional[int] = None, nfev_cold=50, nfev_warm=5, rigs: Optional[Sequence[HotPath]] = None):
+        """rigs: one HotPath per chain (all with hp's cameras) -- a calibration per chain, held as a rig stack that set_rig() rewrites row
+        by row, and a per-chain `active` byte word: step_fused() then runs mvmc_chain_run_sessions (the live session pool, live.py).
+        hp still supplies the skeleton.  Without rigs the tracker is the one-calibration tracker it always was."""
         d = hp.device
         self.hp, self.B, self.P, self.T = hp, n_chains, p_max, t_max
         C = hp.K.shape[0]
@@ -74,6 +77,26 @@ class ChainTracker:
         self.events = None  # set to a list to collect (start, end) CUDA events around every IK launch
         self.als_events = None  # same for the association (ALS) launches of the spatio-temporal graph
         self.assoc_done = None
+        self.rig_stack = None     # (P (B,C,3,4), F (B,C,C,3,3) f32, F2 (B,C,C,3,3)) with rigs: chain b runs on row b
+        self.rig_of_chain = None
+        self.active = None        # (B) u8 device with rigs: 0 = the chain sits step_fused's launch out
+        if rigs is not None:
+            if len(rigs) != n_chains:
+                raise ValueError(f"ChainTracker: {len(rigs)} rigs for {n_chains} chains (one per chain)")
+            self.rig_stack = stack_rigs(rigs, C)
+            self.rig_of_chain = torch.from_numpy(check_rig_of_chain(np.arange(B), B, B)).to(d)
+            self.active = torch.ones((B,), dtype=torch.uint8, device=d)
+
+    def set_rig(self, b: int, hp: HotPath) -> None:
+        """Row b of the rig stack := hp's calibration (a live session opening on chain b)."""
+        if self.rig_stack is None:
+            raise ValueError("ChainTracker.set_rig: the tracker was built without rigs")
+        if hp.P.shape[0] != self.C:
+            raise ValueError(f"ChainTracker.set_rig: {hp.P.shape[0]} cameras, the tracker has {self.C}")
+        Pm, Fm, F2 = self.rig_stack
+        Pm[b].copy_(hp.P)
+        Fm[b].copy_(hp.F)
+        F2[b].copy_(dev.fmats_from_projections(hp.P))
 
     def step(self, kps17: torch.Tensor, counts: torch.Tensor, want_debug=False):
         """kps17 (B,C,P,17,3) f64 + counts (B,C) i32 of the current frame of every chain."""
@@ -127,7 +150,8 @@ class ChainTracker:
         if self._in is None:
             B, C, P = self.B, self.C, self.P
             nk, nc = B * C * P * 17 * 3 * 8, B * C * 4
-            total = nk + ((nc + 15) & ~15)
+            na = B if self.active is not None else 0     # (with rigs: the chains' active bytes travel with the frame, `act_np` / `act_d`)
+            total = nk + ((nc + 15) & ~15) + ((na + 15) & ~15)
             host = torch.empty((total,), dtype=torch.uint8).pin_memory()
             devb = torch.empty((total,), dtype=torch.uint8, device=self._flat.device)
             self._in = dict(host=host, dev=devb,
@@ -135,17 +159,22 @@ class ChainTracker:
                             cnt_np=host[nk:nk + nc].view(torch.int32).view(B, C).numpy(),
                             kps_d=devb[:nk].view(torch.float64).view(B, C, P, 17, 3),
                             cnt_d=devb[nk:nk + nc].view(torch.int32).view(B, C))
+            if na:
+                a0 = nk + ((nc + 15) & ~15)
+                self._in.update(act_h=host[a0:a0 + na], act_np=host[a0:a0 + na].numpy(), act_d=devb[a0:a0 + na])
         return self._in
 
     def upload_inputs(self) -> None:
         self._in["dev"].copy_(self._in["host"], non_blocking=True)
 
-    def step_fused(self, kps17: torch.Tensor, counts: torch.Tensor, fold_void: bool = True):
+    def step_fused(self, kps17: torch.Tensor, counts: torch.Tensor, fold_void: bool = True, active: Optional[torch.Tensor] = None):
         """The same frame update as step() in ONE launch (mvmc_chain_run with chain_len 1 on this tracker's state): what
         the per-frame call surface (MvTracker.update_4d) uses.  Sizes outside the chain kernel's arena, or a frame whose graph
         is too large for it, are the caller's to route to step() (ChainTracker.fused_ok, check_chain_flags).
         fold_void=False: the launch's per-chain void words are NOT folded into the tracker's own (one small kernel less per frame) --
-        for a caller that ends the frame with read_back(), which then reads them where the launch left them."""
+        for a caller that ends the frame with read_back(), which then reads them where the launch left them.
+        A tracker with rigs runs mvmc_chain_run_sessions: chain b on rig row b, and only the chains whose byte in ``active`` ((B) u8 device,
+        default: the tracker's own `active`) is non-zero -- an idle chain's state and words are left as they were."""
         import ctypes as C
         from . import _cabi
         B, Cn, P, T, K, V = self.B, self.C, self.P, self.T, self.K, self.V
@@ -168,9 +197,14 @@ class ChainTracker:
         w = self._fused
         # the argument struct: every pointer in it but the frame's inputs belongs to this tracker, and the per-frame driver hands in
         # the same input buffers every frame (frame_inputs()) -- built once, rebuilt when an input pointer changes
-        key = (kps17.data_ptr(), counts.data_ptr(), self.nfev_cold, self.nfev_warm)
+        sessions = self.rig_stack is not None or active is not None
+        if sessions and active is None:
+            active = self.active
+        Pm, Fm, F2 = self.rig_stack if self.rig_stack is not None else (self.hp.P, self.hp.F, self.F2)
+        key = (kps17.data_ptr(), counts.data_ptr(), self.nfev_cold, self.nfev_warm, Pm.data_ptr(), Fm.data_ptr(), F2.data_ptr(),
+               None if active is None else active.data_ptr())
         if self._fused_args is None or self._fused_args[0] != key:
-            t = dict(w, kps17=kps17, counts=counts, Pmats=self.hp.P, Fmats=self.hp.F, F2=self.F2, params=self.params,
+            t = dict(w, kps17=kps17, counts=counts, Pmats=Pm, Fmats=Fm, F2=F2, params=self.params,
                      joints=self.joints, meta=self.meta, n_tracks=self.n_tracks, next_id=self.next_id, n_dead=self.n_dead,
                      slot_src=self.slot_src, out_info=None, out_als_iters=None, out_phase_cycles=None)
             buf = _cabi.MvmcChainBuffers()
@@ -183,8 +217,15 @@ class ChainTracker:
                 setattr(buf, name, None if ten is None else ten.data_ptr())
             self._fused_args = (key, buf)
         buf = self._fused_args[1]
-        _cabi.check(_cabi.load().mvmc_chain_run(C.byref(self.hp.skeleton), C.byref(buf),
-                                                C.c_void_p(torch.cuda.current_stream(d).cuda_stream)), "mvmc_chain_run")
+        stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+        if sessions:
+            if active.dtype != torch.uint8 or active.numel() != B or active.device != d:
+                raise ValueError(f"ChainTracker.step_fused: active must be ({B},) uint8 on {d}")
+            rig, n_rigs = (None, 1) if self.rig_of_chain is None else (self.rig_of_chain.data_ptr(), B)
+            _cabi.check(_cabi.load().mvmc_chain_run_sessions(C.byref(self.hp.skeleton), C.byref(buf), C.c_void_p(rig), n_rigs,
+                                                             C.c_void_p(active.data_ptr()), stream), "mvmc_chain_run_sessions")
+        else:
+            _cabi.check(_cabi.load().mvmc_chain_run(C.byref(self.hp.skeleton), C.byref(buf), stream), "mvmc_chain_run")
         # the launch zeroes its flag words: fold this frame's per-chain void words into the tracker's own (read by check())
         self._void_pending = not fold_void
         if fold_void:
@@ -225,11 +266,14 @@ class ChainTracker:
         self._flat.copy_(snap)
         self.overflow.zero_()
 
-    def read_back(self):
+    def read_back(self, raise_on_void: bool = True):
         """The state on the host after ONE transfer and ONE synchronisation (the per-frame driver's end of frame: check() and four
         tensor reads took six round trips): dict of NumPy views (params, joints, meta, n_tracks, ..., overflow, cflags) of one of two
         pinned buffers (the call after next overwrites it).  Raises like check(); the words that made it raise are cleared on the device
-        (nothing is cleared on a frame that went through: the next launch zeroes its own words)."""
+        (nothing is cleared on a frame that went through: the next launch zeroes its own words).
+        raise_on_void=False (the live session pool): a void chain does not raise -- out["void"] holds every chain's void word (the
+        launch's, or'ed with the tracker's own), the mirror is marked good all the same, and the caller brings the void chains' rows
+        back with restore_rows().  A hand-over time-out still raises."""
         n, B = self._flat.numel(), self.B
         if self._host is None:
             # two pinned mirrors, written alternately: the one NOT written by this call holds the state after the last frame that went
@@ -237,12 +281,26 @@ class ChainTracker:
             self._host = [torch.empty((n,), dtype=torch.uint8).pin_memory() for _ in range(2)]
             self._host_good = -1         # index of the mirror that holds the last good state (-1: none yet)
         cur = 1 - self._host_good if self._host_good >= 0 else 0
+        self._host_prev = self._host_good
         h = self._host[cur]
         h[:n].copy_(self._flat, non_blocking=True)          # (state AND the chain kernel's flag words: `cflags` is part of _flat)
         fl = self.cflags[B:2 * B + 4] if self._fused is not None else None
         torch.cuda.current_stream(self._flat.device).synchronize()
         out = {name: h[o:o + nb].view(dt).view(shape).numpy() for name, (o, nb, shape, dt) in self._layout.items()}
         words = out["cflags"][B:2 * B + 4] if fl is not None else None
+        if not raise_on_void:
+            void = out["overflow"].copy()
+            if words is not None and self._void_pending:
+                void |= words[4:]
+            out["void"] = void
+            self._void_pending = False
+            if void.any():
+                self.overflow.zero_()
+            if words is not None and int(words[0]):
+                fl.zero_()
+                raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
+            self._host_good = cur
+            return out
         ov = int(out["overflow"].max()) if out["overflow"].size else 0
         if words is not None and self._void_pending:
             ov |= int(np.bitwise_or.reduce(words[4:])) if B else 0       # (step_fused(fold_void=False): read where the launch left them)
@@ -273,6 +331,53 @@ class ChainTracker:
         back onto the device, from the pinned mirror (the per-frame driver then needs no device snapshot in front of every frame)."""
         self._flat.copy_(self._host[self._host_good][:self._flat.numel()], non_blocking=True)
         self.overflow.zero_()
+
+    def restore_rows(self, rows, snap: Optional[torch.Tensor] = None) -> None:
+        """Per-chain restore_previous(), for a read_back(raise_on_void=False) that found some chains void: the rows of ``rows`` come back,
+        in every state field, from the host mirror of the read before (or from ``snap``, a device snapshot taken in front of the launch,
+        when there was none) -- on the device AND in the mirror that read_back has just marked good, so that this mirror holds, for every
+        chain, the state after its last committed frame (a void of another chain on the next frame restores from it)."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        if rows.size == 0:
+            return
+        if snap is None and (self._host is None or getattr(self, "_host_prev", -1) < 0):
+            raise ValueError("ChainTracker.restore_rows: no host mirror of an earlier frame and no snapshot")
+        d = self._flat.device
+        rows_d = torch.from_numpy(rows).to(d)
+        good = self._host[self._host_good] if self.has_previous else None
+        for name in self._STATE + ("overflow",):
+            o, nb, shape, dt = self._layout[name]
+            if name == "overflow":
+                src = torch.zeros((rows.size,), dtype=dt)
+            elif snap is not None:
+                src = snap[o:o + nb].view(dt).view(shape)[rows_d].cpu()
+            else:
+                src = self._host[self._host_prev][o:o + nb].view(dt).view(shape)[torch.from_numpy(rows)]
+            getattr(self, name)[rows_d] = src.to(d)
+            if good is not None:
+                good[o:o + nb].view(dt).view(shape)[torch.from_numpy(rows)] = src
+
+    def put_rows(self, rows, state: dict) -> None:
+        """Rows ``rows`` of the state := ``state`` (field -> host array of len(rows) rows; fields not named are reset to a fresh
+        tracker's: zeros, slot_src -1), on the device and in the host mirror marked good, if there is one."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        d = self._flat.device
+        rows_d = torch.from_numpy(rows).to(d)
+        good = self._host[self._host_good] if self.has_previous else None
+        for name in self._STATE + ("overflow",):
+            o, nb, shape, dt = self._layout[name]
+            if name in state:
+                src = torch.as_tensor(np.ascontiguousarray(state[name])).to(dt).reshape((rows.size,) + tuple(shape[1:]))
+            else:
+                src = torch.full((rows.size,) + tuple(shape[1:]), -1 if name == "slot_src" else 0, dtype=dt)
+            getattr(self, name)[rows_d] = src.to(d)
+            if good is not None:
+                good[o:o + nb].view(dt).view(shape)[torch.from_numpy(rows)] = src
+
+    def state_rows(self, rows) -> dict:
+        """Rows ``rows`` of the device state (every field of _STATE) as host arrays (synchronises)."""
+        idx = torch.as_tensor(np.asarray(rows, dtype=np.int64).reshape(-1)).to(self._flat.device)
+        return {name: getattr(self, name)[idx].cpu().numpy() for name in self._STATE}
 
     def widened(self, t_max: int) -> "ChainTracker":
         """A tracker with t_max tracklet slots (> the present number) holding this tracker's state."""
