@@ -87,10 +87,16 @@ def synth_frames(m, data, calibs, f):
     return frames
 
 
-def run_synth_tracker(m, SYNTH=SYNTH, T=8):
-    """The reference tracker over the synthetic subset, one tracker per chain; -> (fixture dict, IK cases).  T = rows of the tables."""
+def run_synth_tracker(m, SYNTH=SYNTH, T=8, data=None, chains=None, with_als_iters=False):
+    """The reference tracker over the synthetic subset, one tracker per chain; -> (fixture dict, IK cases).  T = rows of the tables.
+
+    data: the inputs (default: synth.generate's random walk of SYNTH); chains: the indices of the chains of SYNTH["chain_len"] frames
+    to run (default: all of them).  The per-frame tables hold the selected chains' frames in order (row k L + t = frame chains[k] L + t);
+    ``solve_info``'s first column is the frame's index in ``data``.  with_als_iters adds ``als_iters``, each frame's match_als
+    iteration count (motion_capture.py:758; gen_golden.InvCounter: two inversions per iteration)."""
     from multiview_motion_capture_amd import synth
-    data = synth.generate(SYNTH["n_frames"], SYNTH["n_views"], SYNTH["n_people"], SYNTH["seed"], chain_len=SYNTH["chain_len"])
+    if data is None:
+        data = synth.generate(SYNTH["n_frames"], SYNTH["n_views"], SYNTH["n_people"], SYNTH["seed"], chain_len=SYNTH["chain_len"])
     C = SYNTH["n_views"]
     calibs = []
     for c in range(C):
@@ -114,25 +120,43 @@ def run_synth_tracker(m, SYNTH=SYNTH, T=8):
                           stage=[(r.cost, r.nfev, r.status) for _, r, _ in rec.results]))
         return param, pose
 
+    orig_als = m.mc.match_als
+    als = {"n": 0, "calls": 0}
+
+    def match_als(*a, **kw):
+        with gg.InvCounter() as ic:
+            r = orig_als(*a, **kw)
+        als["n"] += ic.n // 2
+        als["calls"] += 1
+        return r
+
     PoseSolver.solve = solve
+    m.mc.match_als = match_als
     F, L = SYNTH["n_frames"], SYNTH["chain_len"]
-    meta = -np.ones((F, T, 4), dtype=np.int32)
-    params = np.zeros((F, T, 68))
-    joints = np.full((F, T, 18, 3), np.nan)
-    n_tracks = np.zeros(F, dtype=np.int32)
-    n_dead = np.zeros(F, dtype=np.int32)
-    n_solves = np.zeros(F, dtype=np.int32)
+    chains = list(range(F // L)) if chains is None else [int(b) for b in chains]
+    Fs = len(chains) * L
+    meta = -np.ones((Fs, T, 4), dtype=np.int32)
+    params = np.zeros((Fs, T, 68))
+    joints = np.full((Fs, T, 18, 3), np.nan)
+    n_tracks = np.zeros(Fs, dtype=np.int32)
+    n_dead = np.zeros(Fs, dtype=np.int32)
+    n_solves = np.zeros(Fs, dtype=np.int32)
+    als_iters = np.zeros(Fs, dtype=np.int32)
     solve_info = []
     t0 = time.time()
     try:
-        for b in range(F // L):
+        for k, b in enumerate(chains):
             tracker = m.mc.MvTracker(skel)
             ids = {}
             for t in range(L):
                 f = b * L + t
                 cur["frame"] = f
                 n0 = len(cases)
+                als["n"], als["calls"] = 0, 0
                 tracker.update_4d(t + 1, synth_frames(m, data, calibs, f), None)
+                assert als["calls"] == 1
+                als_iters[k * L + t] = als["n"]
+                f = k * L + t
                 for tl in tracker.tracklets + tracker.dead_tracklets:
                     ids.setdefault(id(tl), len(ids))
                 assert len(tracker.tracklets) <= T
@@ -145,15 +169,18 @@ def run_synth_tracker(m, SYNTH=SYNTH, T=8):
                 n_dead[f] = len(tracker.dead_tracklets)
                 n_solves[f] = len(cases) - n0
                 for c in cases[n0:]:
-                    solve_info.append([f, int(c["cold"]), len(c["poses"]), c["stage"][0][1], c["stage"][0][2], c["stage"][1][1], c["stage"][1][2]])
+                    solve_info.append([b * L + t, int(c["cold"]), len(c["poses"]), c["stage"][0][1], c["stage"][0][2], c["stage"][1][1], c["stage"][1][2]])
             print(f"synthetic chain {b}: {len(cases)} solves so far, t={time.time() - t0:.0f}s", flush=True)
     finally:
         PoseSolver.solve = orig_solve
+        m.mc.match_als = orig_als
     fix = dict(seed=np.array(SYNTH["seed"]), n_frames=np.array(F), chain_len=np.array(L), n_views=np.array(C), n_people=np.array(SYNTH["n_people"]),
                kps25_checksum=np.array(float(np.abs(data["kps25"].astype(np.float64)).sum())),
                meta=meta, params=params, joints=joints, n_tracks=n_tracks, n_dead=n_dead, n_solves=n_solves,
                solve_info=np.array(solve_info), solve_joints=np.array([c["joints"] for c in cases]),
                solve_cost=np.array([c["stage"][1][0] for c in cases]))
+    if with_als_iters:
+        fix["als_iters"] = als_iters
     return fix, cases
 
 

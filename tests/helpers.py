@@ -113,3 +113,67 @@ def als_oracle_job(args):
     mm, xb, it = o.match_als(S, dim, return_iters=True)
     return xb, o.cluster_labels(mm, len(S)), it
 
+
+
+def bench_step_data(F, C, P, seed, segment, L=16):
+    """The frames one rank of ``bench.py --walk continuous`` (its default) times: rank ``segment``'s step of F frames, chains of L.
+    Restates bench.py's run_workload for --workload full without occlusion: the scene is cut into k_seg segments of F / k_seg frames
+    (at most 32,768 each, a multiple of L), rank r owning segments r k_seg .. r k_seg + k_seg - 1.  A segment is a function of (seed,
+    index, LENGTH) -- the RNG stream positions depend on the frame count, so a shorter segment is not a prefix of a longer one: always
+    generate the whole step and slice chains out of it."""
+    from multiview_motion_capture_amd import synth
+    if F % L:
+        raise ValueError("bench_step_data: F must be a multiple of L")
+    k_seg = -(-F // 32768)
+    while F % (k_seg * L):
+        k_seg += 1
+    parts = [synth.generate(F // k_seg, C, P, seed, shuffle=True, walk="scene", segment=segment * k_seg + j) for j in range(k_seg)]
+    data = dict(parts[0])
+    if k_seg > 1:
+        for key in ("kps25", "counts", "gt_joints", "gt_order"):
+            data[key] = np.concatenate([p[key] for p in parts], axis=0)
+    return data
+
+
+def closest_pair_root(gt_joints):
+    """(F,) the smallest distance between the roots (joint 0 of the 18-joint skeleton, the mid hip) of two people, per frame: how
+    close together the association and the tracker's matching have to tell people apart."""
+    root = gt_joints[:, :, 0]
+    d = np.linalg.norm(root[:, :, None] - root[:, None, :], axis=-1)
+    P = d.shape[1]
+    d[:, np.arange(P), np.arange(P)] = np.inf
+    return d.min(axis=(1, 2))
+
+
+def oracle_chain_job(args):
+    """(kps25 (L,C,P,25,3), counts (L,C), (K, Rt, P)) -> ([(meta (k,4) int32, [joints (18,3)] * k, ALS iterations) per frame], n_dead,
+    next_id) of the noise-free oracle tracker (tracker_np.OracleTracker driving trf_np.pose_solver_solve_clean) run over one chain from
+    a fresh tracker.  The unit of work of a process pool: workers are SPAWNED, import NumPy only and never touch the GPU."""
+    import tracker_np as tk
+    import trf_np as t
+    kps25, counts, (K, Rt, Pm) = args
+    kps25 = np.asarray(kps25, dtype=np.float64)
+    its = []
+    orig = o.match_als
+
+    def recording(W, dim, return_iters=False):      # the frame's ALS iteration count (OracleTracker calls o.match_als once per frame)
+        mm, xb, it = orig(W, dim, return_iters=True)
+        its.append(it)
+        return (mm, xb, it) if return_iters else (mm, xb)
+    o.match_als = recording
+    try:
+        orc = tk.OracleTracker(K, Rt, Pm, solver=lambda poses, projs, init: t.pose_solver_solve_clean(poses, projs, init))
+        rows = []
+        for tt in range(len(kps25)):
+            views = []
+            for c in range(kps25.shape[1]):
+                poses = [o.openpose25_to_coco17(kps25[tt, c, p]) for p in range(int(counts[tt, c]))]
+                views.append([q for q in poses if o.pose_is_good(q)])
+            n0 = len(its)
+            orc.update(tt, views)
+            assert len(its) == n0 + 1
+            rows.append((np.array([[x.tid, x.state, x.hits, x.length] for x in orc.tracklets], dtype=np.int32).reshape(-1, 4),
+                         [np.array(x.joints) for x in orc.tracklets], its[-1]))
+    finally:
+        o.match_als = orig
+    return rows, orc.n_dead, orc.next_id

@@ -222,12 +222,25 @@ def test_config5_at_full_size_on_the_persistent_kernel():
     mvmc_chain_run's BIG layout: no hand-over / graph-size / table flag, deterministic, shard invariant (two half-shards == the whole: what
     the multi-GPU split relies on), eight tracklets that keep their identity through their chain, 3-D accuracy against the
     generator's ground truth.  (Parity with the oracle is the small-size tests' above; the CPU oracle needs minutes per chain here.)"""
+    check_config5_at_full_size("chains")
+
+
+def test_config5_at_full_size_on_the_persistent_kernel_on_the_bench_scene():
+    """The same on the step bench.py times for config 5 (--walk continuous, rank 0: tests/helpers.bench_step_data)."""
+    check_config5_at_full_size("scene")
+
+
+def check_config5_at_full_size(walk):
     from multiview_motion_capture_amd import synth
     from multiview_motion_capture_amd.pipeline import HotPath
     from multiview_motion_capture_amd.tracker import run_chains, run_chains_fused
     from multiview_motion_capture_amd.tracker import check_chain_flags
+    from helpers import bench_step_data
     Ff = 25008
-    data = synth.generate(Ff, C, P, 20260104, chain_len=L)        # BASELINE.json config 5's seed (SURVEY 8d)
+    if walk == "scene":
+        data = bench_step_data(Ff, C, P, 20260104, 0, L)
+    else:
+        data = synth.generate(Ff, C, P, 20260104, chain_len=L)    # BASELINE.json config 5's seed (SURVEY 8d)
     d = torch.device("cuda:0")
     hp = HotPath(data["K"], data["Rt"], device=d)
     kps, cnt = torch.from_numpy(data["kps25"]).to(d), torch.from_numpy(data["counts"]).to(d)
@@ -264,6 +277,6 @@ def test_config5_at_full_size_on_the_persistent_kernel():
         dist = np.linalg.norm(joints[f, :P, None] - gt[f][None], axis=-1).mean(axis=-1)
         errs.append(dist.min(axis=1))
     errs = np.concatenate(errs)
-    print(f"config 5, {Ff} frames: {100 * (n == P).mean():.2f}% frames with {P} tracks; {100 * full_len:.2f}% of tracklets span their "
+    print(f"config 5 ({walk}), {Ff} frames: {100 * (n == P).mean():.2f}% frames with {P} tracks; {100 * full_len:.2f}% of tracklets span their "
           f"whole chain; mean joint error vs ground truth: median {np.median(errs) * 100:.2f} cm, p95 {np.quantile(errs, 0.95) * 100:.2f} cm")
     assert (n == P).mean() > 0.95 and full_len > 0.9 and np.median(errs) < 0.05

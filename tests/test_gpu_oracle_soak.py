@@ -14,7 +14,18 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 
 def test_three_seeds_of_configs_4_and_5_against_the_oracle_tracker():
     import oracle_soak as soak
-    res = soak.run([soak.WORKLOADS[0], soak.WORKLOADS[2], soak.WORKLOADS[3]], [21, 22, 23], workers=min(14, os.cpu_count() or 4))
+    check(soak.run([soak.WORKLOADS[0], soak.WORKLOADS[2], soak.WORKLOADS[3]], [21, 22, 23], workers=min(14, os.cpu_count() or 4)))
+
+
+def test_three_scenes_of_config_4_against_the_oracle_tracker():
+    """Consecutive chains of the benchmark's kind of data (one bounded scene per seed, tools/oracle_soak.py's scene workload)."""
+    import oracle_soak as soak
+    wl = soak.WORKLOADS[5]
+    assert wl[0] == "scene" and wl[4:] == (0.0, 0.0)
+    check(soak.run([wl], [21, 22, 23], workers=min(14, os.cpu_count() or 4)))
+
+
+def check(res):
     for r in res:
         C, P, n_chains, occ, spur = r["workload"]
         assert r["frames"] == 3 * n_chains * 16

@@ -2,6 +2,7 @@
 import hashlib
 
 import numpy as np
+import pytest
 
 from multiview_motion_capture_amd import synth
 
@@ -36,3 +37,36 @@ def test_the_default_generator_is_unchanged():
     """Fixtures recorded from the reference on synthetic inputs (tests/golden) depend on generate()'s default stream."""
     d = synth.generate(64, 5, 4, 20260103, chain_len=16)
     assert hashlib.sha256(d["kps25"].tobytes()).hexdigest()[:16] == "c1cd9cbcd422420c"
+
+
+# the steps bench.py times (tests/helpers.bench_step_data): config 4 (rank 0 of the default run) and config 5 (rank 0, and rank 7 of
+# --frames-total 200064), with the reference fixtures recorded on chains of them (oracle/gen_golden_scene.py)
+BENCH_STEPS = [((10000, 5, 4, 20260103, 0), 4327783271.264681, "synth_c4_scene_tracker.npz"),
+               ((25008, 8, 8, 20260104, 0), 35714945175.748474, "synth_c5_scene_tracker.npz"),
+               ((25008, 8, 8, 20260104, 7), 35787608856.01163, "synth_c5_scene_tracker.npz")]
+
+
+@pytest.mark.parametrize("step,checksum,fixture", BENCH_STEPS, ids=["c4_seg0", "c5_seg0", "c5_seg7"])
+def test_the_benchmark_steps_and_their_reference_fixtures_are_pinned(step, checksum, fixture):
+    from conftest import load_golden
+    from helpers import bench_step_data, closest_pair_root
+    F, C, P, seed, seg = step
+    data = bench_step_data(F, C, P, seed, seg)
+    assert data["kps25"].shape == (F, C, P, 25, 3) and (data["counts"] == P).all()
+    assert float(np.abs(data["kps25"].astype(np.float64)).sum()) == checksum
+    # the fixture was recorded on chains of exactly this step, and its chains are the ones its rule selects
+    g = load_golden(fixture)
+    L = int(g["chain_len"])
+    assert (int(g["n_frames"]), int(g["n_views"]), int(g["n_people"]), int(g["seed"])) == (F, C, P, seed)
+    segs = [int(s) for s in np.unique(g["segments"])]
+    assert float(g["step_checksum"][segs.index(seg)]) == checksum
+    mine = np.nonzero(g["segments"] == seg)[0]
+    chains = [int(b) for b in g["chains"][mine]]
+    for i, b in zip(mine, chains):
+        assert float(np.abs(data["kps25"][b * L:(b + 1) * L].astype(np.float64)).sum()) == float(g["chain_checksum"][i])
+    head = closest_pair_root(data["gt_joints"][0::L])
+    n_close = len(chains) - 1 - int(F // L - 1 in chains[1:2])
+    assert chains[0] == 0
+    assert sorted(chains[-n_close:]) == sorted(int(b) for b in np.argsort(head, kind="stable")[:n_close])
+    assert np.allclose(head[chains], g["head_closest_pair"][mine], rtol=0, atol=1e-12)
+    assert head[chains].min() < 0.2          # the close-pair regime the fixture is for

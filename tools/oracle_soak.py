@@ -2,7 +2,8 @@
 
     python tools/oracle_soak.py > gpurun_out/oracle_soak.txt
 
-For several seeds, clean and with occlusion + false detections (births, deaths, ninth tracklets), every chain of a small batch goes through
+For several seeds, clean and with occlusion + false detections (births, deaths, ninth tracklets), on the random walk restarted per chain
+and on consecutive chains of the benchmark's bounded scene (some pairs of people stay close there), every chain of a small batch goes through
 mvmc_chain_run on the device and through tracker_np.OracleTracker driving trf_np.pose_solver_solve_clean on the host (a process per
 chain).  Reported per workload: frames whose tracker table equals the oracle's, and the joint differences on those frames.  The tests hold
 the same comparison on two fixed seeds (tests/test_gpu_synth_tracker.py); this is the wider net."""
@@ -52,21 +53,26 @@ def oracle_chain(job):
     return rows, orc.next_id, orc.n_dead
 
 
-WORKLOADS = [(5, 4, 4, 0.0, 0.0), (5, 4, 4, 0.05, 0.2), (5, 4, 4, 0.15, 0.5), (8, 8, 1, 0.0, 0.0), (8, 8, 1, 0.05, 0.2)]
+WORKLOADS = [(5, 4, 4, 0.0, 0.0), (5, 4, 4, 0.05, 0.2), (5, 4, 4, 0.15, 0.5), (8, 8, 1, 0.0, 0.0), (8, 8, 1, 0.05, 0.2),
+             # the benchmark's kind of data (bench.py --walk continuous): consecutive chains of one bounded scene, segment = the seed's
+             # index in the seed list, so that different seeds give different scenes
+             ("scene", 5, 4, 16, 0.0, 0.0), ("scene", 5, 4, 16, 0.05, 0.2)]
 
 
 def main():
     workloads = WORKLOADS
     if os.environ.get("SOAK_WORKLOADS"):      # e.g. "3 4": indices into the list above
         workloads = [workloads[int(i)] for i in os.environ["SOAK_WORKLOADS"].split()]
-    if os.environ.get("SOAK_CUSTOM"):         # e.g. "3,2,4,0.1,0.3,0.2,6.0;6,6,2,0,0": views, people, chains, occlusion, spurious[, drop, pixel sigma]
-        workloads = [tuple(float(v) if "." in v else int(v) for v in w.split(",")) for w in os.environ["SOAK_CUSTOM"].split(";")]
+    if os.environ.get("SOAK_CUSTOM"):         # e.g. "3,2,4,0.1,0.3,0.2,6.0;6,6,2,0,0;scene,5,4,8,0,0": [scene,] views, people, chains, occlusion, spurious[, drop, pixel sigma]
+        num = lambda v: v if v == "scene" else float(v) if "." in v else int(v)
+        workloads = [tuple(num(v) for v in w.split(",")) for w in os.environ["SOAK_CUSTOM"].split(";")]
     seeds = [int(s) for s in os.environ.get("SOAK_SEEDS", "1 2 3 4 5 6").split()]
     run(workloads, seeds, int(os.environ.get("SOAK_WORKERS", "14")))
 
 
 def run(workloads, seeds, workers=14):
-    """-> one dict per workload: frames, tables_equal, als_equal, als_capped, tracklet_frames, above_1e6 [(dj, hits)], worst"""
+    """-> one dict per workload: frames, tables_equal, als_equal, als_capped, tracklet_frames, above_1e6 [(dj, hits)], worst, walk.
+    A workload whose first element is "scene" takes its frames from one scene (synth.generate(walk="scene")), segment i for seeds[i]."""
     import torch
     from multiview_motion_capture_amd import synth
     from multiview_motion_capture_amd.pipeline import HotPath
@@ -75,13 +81,18 @@ def run(workloads, seeds, workers=14):
     results = []
     with ProcessPoolExecutor(max_workers=workers, mp_context=SPAWN) as pool:
         for wl in workloads:
+            walk = "scene" if wl[0] == "scene" else "chains"
+            wl = wl[1:] if walk == "scene" else wl
             C, P, n_chains, occ, spur = wl[:5]
             extra = dict(zip(("drop", "pix_sigma"), wl[5:]))
             offenders = []
             frames = same = void = als_frames = als_same = als_cap = als_unexplained = repaired = 0
             dd, first_bad = [], None
-            for seed in seeds:
-                data = synth.generate(n_chains * L, C, P, seed, chain_len=L, occlusion=occ, spurious=spur, **extra)
+            for i_seed, seed in enumerate(seeds):
+                if walk == "scene":
+                    data = synth.generate(n_chains * L, C, P, seed, occlusion=occ, spurious=spur, walk="scene", segment=i_seed, **extra)
+                else:
+                    data = synth.generate(n_chains * L, C, P, seed, chain_len=L, occlusion=occ, spurious=spur, **extra)
                 hp = HotPath(data["K"], data["Rt"], device=d)
                 out = run_chains_fused(hp, torch.from_numpy(data["kps25"]).to(d), torch.from_numpy(data["counts"]).to(d), L, want_info=True)
                 torch.cuda.synchronize()
@@ -127,7 +138,7 @@ def run(workloads, seeds, workers=14):
                                 dd.append(dj)
                                 if dj > 1e-6:
                                     offenders.append((dj, int(exp[s][2])))
-                                    tag = f"C{C}P{P}_occ{occ}_sp{spur}_seed{seed}_chain{b}"
+                                    tag = f"{walk}_C{C}P{P}_occ{occ}_sp{spur}_seed{seed}_chain{b}"
                                     print(f"    above 1e-6: {tag} frame {tt} slot {s} (id, state, hits, length) {exp[s].tolist()}: {dj:.2e} m; the frame's ALS "
                                           f"iterations: oracle {it_o}, device {als_dev[f]}" + (" (AT THE CAP: the result of an unconverged iteration)" if it_o >= 1000 else ""),
                                           flush=True)
@@ -141,12 +152,12 @@ def run(workloads, seeds, workers=14):
                                 first_bad = (seed, b, tt)
                             ok_chain = False      # (a chain's later frames follow from the first different table)
             dd = np.array(dd) if dd else np.array([np.nan])
-            print(f"C{C} P{P} occlusion {occ} spurious {spur}{' ' + str(extra) if extra else ''}: {len(seeds)} seeds x {n_chains} chain(s) of {L}: tables equal on {same} / {frames} "
+            print(f"{walk}: C{C} P{P} occlusion {occ} spurious {spur}{' ' + str(extra) if extra else ''}: {len(seeds)} seeds x {n_chains} chain(s) of {L}: tables equal on {same} / {frames} "
                   f"frames (first difference: {first_bad}; chains with a void word, not compared: {void}; chains that went through the repair tier: {repaired}); {len(dd)} tracklet-frames, joint "
                   f"difference median {np.nanmedian(dd):.1e} p90 {np.nanpercentile(dd, 90):.1e} p99 {np.nanpercentile(dd, 99):.1e} max {np.nanmax(dd):.1e} m; "
                   f"above 1e-6: {int((dd > 1e-6).sum())}; ALS iteration counts equal on {als_same} / {als_frames} frames ({als_cap} at the cap of 1000; different counts in a chain that has not met the cap: {als_unexplained})", flush=True)
             results.append(dict(workload=(C, P, n_chains, occ, spur), frames=frames, tables_equal=same, als_equal=als_same, als_capped=als_cap,
-                                tracklet_frames=len(dd), above_1e6=offenders, worst=float(np.nanmax(dd))))
+                                tracklet_frames=len(dd), above_1e6=offenders, worst=float(np.nanmax(dd)), walk=walk))
     return results
 
 
