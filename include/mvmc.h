@@ -455,6 +455,55 @@ int mvmc_chain_run_rigs(const mvmcSkeleton* skel_host, const mvmcChainBuffers* b
 int mvmc_chain_run_sessions(const mvmcSkeleton* skel_host, const mvmcChainBuffers* buffers, const int32_t* rig_of_chain, int n_rigs,
                             const uint8_t* active, mvmcStream_t stream);
 
+/* ---- body fit of finished tracklets (multiview_motion_capture_amd/body_fit.py).  No counterpart in the reference: its IK fits the
+ * side lengths again on every frame (inverse_kinematics.py:380-433).  One side-length vector per identity, every frame's pose re-solved
+ * against it.  A "problem" is one (identity, frame) pair of a tracklet record; problems of one launch may come from several sequences
+ * (frames laid end to end in kps17, one rig of n_views cameras per sequence). ---- */
+
+/* Observation selection.  Per (problem b, camera c): among the poses of frame frame_of[b] in camera c, the one with the smallest
+ * reprojection_error (motion_capture.py:403-414; the 2D-3D distance of mvmc_st_affinity) to the problem's joints, if that distance is
+ * finite and below max_dist (the affinity floor 15 + 30 ln(999) / 5 of the tracker's graph; ties between poses: the lower slot).
+ * Then two problems of one frame that chose the same pose: the smaller distance keeps it (equal: the lower rank), the other takes
+ * nothing in that camera.
+ *   kps17 (F,C,P,17,3), counts (F,C) as mvmc_ingest writes them; Pmats (R,C,3,4), R = n_rigs
+ *   frame_of, rig_of (B) i32; joints (B,18,3) f64: the record's FK joints
+ *   order (B) i32: the problems sorted so that each frame's are contiguous; grp_lo, grp_hi (B) i32: the range of order[] that holds
+ *   the problems of b's frame; rank (B) i32: the position of b's record in the caller's list (the tie-break)
+ *   choice (B,C) i32 out: nearest pose index q = (f C + c) P + p before the conflicts, or -1; dist (B,C) f64 out (+inf: none)
+ *   members (B,C) i32 out: the selected pose index or -1 (the members format of mvmc_ik_solve); n_views_out (B) i32 out */
+int mvmc_body_observe(const double* kps17, const int32_t* counts, int n_frames, int n_views, int p_max, const double* Pmats,
+                      int n_rigs, const int32_t* frame_of, const int32_t* rig_of, const double* joints, const int32_t* order,
+                      const int32_t* grp_lo, const int32_t* grp_hi, const int32_t* rank, int n_problems, double min_score,
+                      double max_dist, int32_t* choice, double* dist, int32_t* members, int32_t* n_views_out, mvmcStream_t stream);
+
+/* Length step: Levenberg-Marquardt on the side lengths of every identity, all roots and angles fixed; ONE launch, one 64-lane
+ * workgroup per identity.  Identity i owns problems [id_lo[i], id_lo[i+1]) (every one with >= 2 members).  The residual is the IK's
+ * (16 observation rows per member, score-weighted, 1e-5 in the denominator), E = 1/2 sum r^2; H = J^T J, g = J^T r over the
+ * identity's problems, summed per lane in problem order and across lanes in a fixed butterfly (no atomics: bit-identical from run to
+ * run and whatever else the launch holds).  Each trial solves (H + mu diag(H)) d = -g on the free slots, mu starts at mu0, / 10 after
+ * an accepted trial (E(l + d) < E(l)), x 10 after a rejected one; stop after max_iter trials, when |d|_inf < xtol, when the model's
+ * predicted reduction is below ftol E, or when an accepted trial reduced E by less than ftol E.
+ *   params (B,68) f64: root and angles of each problem (its lengths are not read); members (B,C) as from mvmc_body_observe
+ *   lens (n_ids,11) f64 in/out; free_mask (n_ids) i32: bit s = slot s is free; fix_free 0: set from diag(H) > 0 at the start and
+ *   written, 1: read
+ *   info (n_ids, MVMC_BODY_INFO_DOUBLES) f64 out: {E at the start, E at the end, trials made, trials accepted, per trial 1 accepted /
+ *   0 rejected, -1 after the last}; max_iter <= MVMC_BODY_INFO_DOUBLES - 4
+ *   work (B, MVMC_BODY_WORK_DOUBLES) f64 device workspace */
+#define MVMC_BODY_INFO_DOUBLES 16
+#define MVMC_BODY_WORK_DOUBLES 270
+int mvmc_body_lengths(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                      const int32_t* rig_of, const int32_t* members, const double* params, const int32_t* id_lo, int n_ids,
+                      double* lens, int32_t* free_mask, int fix_free, int max_iter, double mu0, double ftol, double xtol,
+                      double* info, double* work, mvmcStream_t stream);
+
+/* mvmc_ik_solve_stages (reprojection mode) with a calibration per problem: Pmats (R,C,3,4), R = n_rigs, and problem b uses rig
+ * rig_of_problem[b] ((B) i32 device).  The same device code as mvmc_ik_solve_stages; a problem whose rig lies outside [0, n_rigs)
+ * gets NaN outputs, as one with fewer than two views. */
+int mvmc_ik_solve_stages_rigs(const mvmcSkeleton* skel_host, const double* kps17, const double* Pmats, int n_rigs,
+                              const int32_t* rig_of_problem, const int32_t* members, int n_problems, int v_max, int n_views,
+                              int p_max, const double* init_params, int stage_mask, int max_nfev, double* params_out,
+                              double* joints_out, double* info_out, double* scratch, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@ IK_SCRATCH_DOUBLES = 7680
 IK_FD_WORK_DOUBLES = 40960
 IK_STEP_OUT_DOUBLES = 240
 BOUND_WORDS, ROW_WORDS = 56, 128
+BODY_INFO_DOUBLES, BODY_WORK_DOUBLES = 16, 270
 
 # every symbol declared in include/mvmc.h
 SYMBOLS = (
@@ -29,7 +30,7 @@ SYMBOLS = (
     "mvmc_affinity", "mvmc_als_associate", "mvmc_closure_labels", "mvmc_cluster_members", "mvmc_dlt", "mvmc_triangulate_postopt", "mvmc_fk", "mvmc_ik_solve",
     "mvmc_fmats_from_projections", "mvmc_st_affinity", "mvmc_track_assign", "mvmc_track_commit", "mvmc_debug_eigh",
     "mvmc_debug_trstep", "mvmc_ik_solve_stages", "mvmc_chain_run", "mvmc_svt_associate", "mvmc_debug_ik_solve_fd", "mvmc_debug_ik_model_step", "mvmc_ingest_dlt", "mvmc_ingest_dlt_f32", "mvmc_pack_message_words", "mvmc_pack_work_words", "mvmc_stitch_work_words", "mvmc_pack_tracks", "mvmc_stitch_chains",
-    "mvmc_chain_run_rigs", "mvmc_chain_run_sessions",
+    "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
 )
 
 
@@ -131,6 +132,9 @@ def load():
         "mvmc_stitch_work_words": [i32, i32, i32],
         "mvmc_pack_tracks": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, f64, vp, i32, vp, vp, vp],
         "mvmc_stitch_chains": [vp, C.c_longlong, i32, i32, i32, i32, i32, f64, i32, vp, vp, vp, vp, vp],
+        "mvmc_body_observe": [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, f64, vp, vp, vp, vp, vp],
+        "mvmc_body_lengths": [SK, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f64, f64, f64, vp, vp, vp],
+        "mvmc_ik_solve_stages_rigs": [SK, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
                 "mvmc_stitch_work_words": C.c_longlong}

@@ -339,6 +339,79 @@ def ik_solve_stages(init_params: torch.Tensor, stage_mask: int, max_nfev: int, k
     return params, joints, info
 
 
+
+def ik_solve_stages_rigs(init_params: torch.Tensor, stage_mask: int, max_nfev: int, kps17: torch.Tensor, Pmats: torch.Tensor,
+                         rig_of_problem: torch.Tensor, members: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None):
+    """ik_solve_stages in reprojection mode with a calibration per problem: Pmats (R,C,3,4), rig_of_problem (B,) i32
+    (include/mvmc.h: mvmc_ik_solve_stages_rigs)."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    B = init_params.shape[0]
+    _req(init_params, torch.float64, "init_params", (B, 68))
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    _req(rig_of_problem, torch.int32, "rig_of_problem", (B,))
+    _req(members, torch.int32, "members", (B, None))
+    dev = init_params.device
+    params = torch.empty((B, 68), dtype=torch.float64, device=dev)
+    joints = torch.empty((B, 18, 3), dtype=torch.float64, device=dev)
+    info = torch.empty((B, 8), dtype=torch.float64, device=dev)
+    check(_cabi.load().mvmc_ik_solve_stages_rigs(C.byref(sk), _p(kps17), _p(Pmats), int(Pmats.shape[0]), _p(rig_of_problem), _p(members),
+                                                 B, members.shape[1], Cn, P, _p(init_params), int(stage_mask), int(max_nfev), _p(params),
+                                                 _p(joints), _p(info), _p(_ik_scratch(B, dev)), _stream()), "mvmc_ik_solve_stages_rigs")
+    return params, joints, info
+
+
+def body_observe(kps17: torch.Tensor, counts: torch.Tensor, Pmats: torch.Tensor, frame_of: torch.Tensor, rig_of: torch.Tensor,
+                 joints: torch.Tensor, order: torch.Tensor, grp_lo: torch.Tensor, grp_hi: torch.Tensor, rank: torch.Tensor,
+                 max_dist: float, min_score=0.1):
+    """Observation selection of the body fit (include/mvmc.h: mvmc_body_observe).  kps17 (F,C,P,17,3) and counts (F,C) from ingest();
+    Pmats (R,C,3,4); per problem (B,): frame_of, rig_of, order, grp_lo, grp_hi, rank i32 and joints (B,18,3) f64
+    -> members (B,C) i32 (pose index into kps17 or -1), n_views (B,) i32, choice (B,C) i32, dist (B,C) f64."""
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(counts, torch.int32, "counts", (F, Cn))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    B = joints.shape[0]
+    _req(joints, torch.float64, "joints", (B, 18, 3))
+    for name, t in (("frame_of", frame_of), ("rig_of", rig_of), ("order", order), ("grp_lo", grp_lo), ("grp_hi", grp_hi),
+                    ("rank", rank)):
+        _req(t, torch.int32, name, (B,))
+    d = joints.device
+    choice = torch.empty((B, Cn), dtype=torch.int32, device=d)
+    dist = torch.empty((B, Cn), dtype=torch.float64, device=d)
+    members = torch.empty((B, Cn), dtype=torch.int32, device=d)
+    n_views = torch.empty((B,), dtype=torch.int32, device=d)
+    check(_cabi.load().mvmc_body_observe(_p(kps17), _p(counts), F, Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(frame_of), _p(rig_of),
+                                         _p(joints), _p(order), _p(grp_lo), _p(grp_hi), _p(rank), B, float(min_score), float(max_dist),
+                                         _p(choice), _p(dist), _p(members), _p(n_views), _stream()), "mvmc_body_observe")
+    return members, n_views, choice, dist
+
+
+def body_lengths(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, params: torch.Tensor,
+                 id_lo: torch.Tensor, lens: torch.Tensor, free_mask: torch.Tensor, fix_free: bool, max_iter: int, mu0: float,
+                 ftol: float, xtol: float, skeleton: Optional[MvmcSkeleton] = None):
+    """Length step of the body fit (include/mvmc.h: mvmc_body_lengths), one workgroup per identity.  lens (n_ids,11) f64 and free_mask
+    (n_ids,) i32 are updated in place; -> info (n_ids, 16) f64."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    B = params.shape[0]
+    _req(params, torch.float64, "params", (B, 68))
+    _req(rig_of, torch.int32, "rig_of", (B,))
+    _req(members, torch.int32, "members", (B, Cn))
+    n_ids = id_lo.shape[0] - 1
+    _req(id_lo, torch.int32, "id_lo", (n_ids + 1,))
+    _req(lens, torch.float64, "lens", (n_ids, 11))
+    _req(free_mask, torch.int32, "free_mask", (n_ids,))
+    info = torch.empty((n_ids, _cabi.BODY_INFO_DOUBLES), dtype=torch.float64, device=params.device)
+    work = torch.empty((max(B, 1), _cabi.BODY_WORK_DOUBLES), dtype=torch.float64, device=params.device)
+    check(_cabi.load().mvmc_body_lengths(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(params), _p(id_lo),
+                                         n_ids, _p(lens), _p(free_mask), int(bool(fix_free)), int(max_iter), float(mu0), float(ftol),
+                                         float(xtol), _p(info), _p(work), _stream()), "mvmc_body_lengths")
+    return info
+
 def ik_solve_fd(kps17: torch.Tensor, Pmats: torch.Tensor, members: torch.Tensor, init_params: Optional[torch.Tensor] = None,
                 cold: Optional[torch.Tensor] = None, max_nfev_cold=50, max_nfev_warm=5, stage_mask=3,
                 skeleton: Optional[MvmcSkeleton] = None):
