@@ -1,8 +1,11 @@
 """Benchmark of the hot path (BASELINE.json metric): frames/s for association + triangulation + IK
 on synthetic (F frames x C views x P people x 25 joints) keypoints, one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W] [--frames F --views C --people P --workload full] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--frames F --views C --people P --workload full] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times its steps and prints the line; --full adds the records that take runs of their own (sustained,
+host buffers, one step alone, CPU baselines, the other BASELINE configurations) and the accuracy checks.
 
 A step = one pass of the whole hot path over this rank's F frames (inputs resident in HBM before
 the timed region).  Frames shard across ranks as contiguous chain ranges (weak scaling: F per GPU is fixed) with no data-path
@@ -401,7 +404,8 @@ def other_config_lines():
     import subprocess
     lines = []
     for name, argv in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--sustain", "0", "--host-io", "0", "--cpu-frames", "0", "--no-other-configs"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--full", "--sustain", "0", "--host-io", "0", "--cpu-frames", "0",
+                                                                    "--no-other-configs"]
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -417,8 +421,14 @@ def other_config_lines():
     return lines
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, measure and check everything else: the sustained (--sustain 300) and host-buffer "
+                         "(--host-io 20) records, one step alone, accuracy against the generator's ground truth, the CPU baselines "
+                         "(--cpu-frames 1) and, for the default headline command, the other BASELINE configurations (--other-configs); "
+                         "without it a run sets up, warms up, times its steps, writes --dump-outputs and prints its line.  An option given "
+                         "explicitly holds either way")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
@@ -446,7 +456,7 @@ def main():
                     help="steps in flight: consecutive steps (independent batches) are issued on N alternating HIP streams, so the "
                          "tail of one launch (its slowest chains, a fifth of the workgroup slots idle) is filled by the head of the "
                          "next; 1 = strictly one step after the other")
-    ap.add_argument("--cpu-frames", type=int, default=1, help="frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-frames", type=int, default=None, help="frames of the CPU baseline sample (0 = skip; default 1 with --full, else 0)")
     ap.add_argument("--cpu-workers", type=int, default=0,
                     help="worker processes of the CPU baseline on the chain protocol (0 = min(16, host cores))")
     ap.add_argument("--seed", type=int, default=20260103)
@@ -472,12 +482,13 @@ def main():
                     help="fused path: how a chain's workgroups follow one another: ticket = (part, chain) from a ticket drawn at start "
                          "(no assumption about dispatch order; the default at every N), static = the same mapping by block index "
                          "(relies on in-order dispatch), queue = ready queue (no assumption, ~3 %% slower); auto = ticket")
-    ap.add_argument("--host-io", type=int, default=20,
+    ap.add_argument("--host-io", type=int, default=None,
                     help="after the timed region: this many further steps with the host buffers of the boundary inside the bracket (inputs "
-                         "from pinned host memory, results back to it), reported as 'host_io' beside 'value'; 0 = skip")
-    ap.add_argument("--sustain", type=int, default=300,
+                         "from pinned host memory, results back to it), reported as 'host_io' beside 'value'; 0 = skip (default 20 with "
+                         "--full, else 0)")
+    ap.add_argument("--sustain", type=int, default=None,
                     help="after the timed region: this many further consecutive steps of the same command (capped at ~15 s of work), "
-                         "reported as 'sustained' beside 'value'; 0 = skip")
+                         "reported as 'sustained' beside 'value'; 0 = skip (default 300 with --full, else 0)")
     ap.add_argument("--tile-from", type=int, default=0,
                     help="generate this many frames on the host and tile them on the device up to --frames (config 2 at 2 M frames: the "
                          "generator would take minutes; the kernel reads every frame from HBM either way); 0 = generate all frames")
@@ -491,12 +502,12 @@ def main():
     ap.add_argument("--other-configs", dest="other_configs", action="store_true", default=None,
                     help="after the headline region also time BASELINE config 5 (C8 P8, 25,008 frames, 3 steps), config 3 (C5 P4, association "
                          "+ triangulation, 10 steps) and config 2 (C5 P1, triangulation only, 2 M frames, 20 launches) as child runs of this script and report them under "
-                         "'other_configs' (default: on for the default headline command at N = 1)")
+                         "'other_configs' (default: on with --full for the default headline command)")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps: write what the last timed step computed (rank 0's shard) as DIR/<name>.npy, float32 or "
                          "float64, at most 64 MB in all (a fixed sample of frames, frame_index.npy, when the step's outputs are larger)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     args.scaling = "weak"
@@ -504,8 +515,12 @@ def main():
         if args.frames_total % (args.gpus * args.chain_len):
             raise SystemExit("--frames-total must be a multiple of --gpus x --chain-len (whole chains per rank)")
         args.frames, args.scaling = args.frames_total // args.gpus, "strong"
+    # a plain run measures the headline figure only: every further record is off unless --full or its own option asks for it
+    for name, full_default in (("cpu_frames", 1), ("host_io", 20), ("sustain", 300)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
     if args.other_configs is None:
-        args.other_configs = (args.workload == "full" and (args.frames, args.views, args.people) == (10000, 5, 4)
+        args.other_configs = (args.full and args.workload == "full" and (args.frames, args.views, args.people) == (10000, 5, 4)
                               and args.occlusion == 0.0 and args.path == "fused")
     if args.overlap is None:
         # steps in flight fill the tail of the chain kernel's launches; the memory-bound triangulation-only pass (config 2) has no
@@ -515,7 +530,11 @@ def main():
         # 557 k (profiles/r06_ik_experiments.txt; round 5 had 2 and 4 at 530 - 534 k against 547 - 550 k at 3).  Six since round 6.
         # Config 5 (one workgroup per CU) does not care (109.9 k / 109.7 k) and keeps two.
         args.overlap = 1 if args.workload == "dlt" else (6 if args.views * args.people <= 40 and args.workload == "full" else 2)
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks as fresh child processes.  Nothing in this process has touched the GPU
         # (no HIP call, no torch.cuda call), and it never does: it only waits and passes rank 0's line through.
@@ -855,7 +874,7 @@ def run_workload(args, rank, world, d):
 
     # for the record: one step on its own, nothing else in flight (untimed region)
     serial_ms = None
-    if args.overlap > 1:
+    if args.full and args.overlap > 1:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         step(False)
@@ -1073,7 +1092,7 @@ def run_workload(args, rank, world, d):
                                  (f" ({args.overlap} launches share the GPU, so a launch lasts longer than ms_per_step)" if args.overlap > 1 else "") +
                                  "; see DESIGN.md"},
         }
-        if chain and "gt_joints" in data:
+        if args.full and chain and "gt_joints" in data:
             # accuracy of the last step's output against the generator's ground truth (the parity gates against the
             # reference are the tests'; this is the size-independent check at the benchmark's full size)
             n_t = out["n_tracks"][:F].cpu().numpy()

@@ -49,6 +49,21 @@ def test_als_histogram_and_the_defaults_of_the_command_line():
     assert bench.DEFAULT_NCCL_MAX_NCHANNELS == "4" and bench.OTHER_CONFIGS[1][1][:6] == ["--views", "8", "--people", "8", "--frames", "25008"]
 
 
+def test_a_plain_run_times_the_headline_only_and_full_adds_the_records():
+    """A plain command measures its headline figure and nothing else; --full restores every further record, and an option given
+    explicitly holds either way."""
+    sys.path.insert(0, ROOT)
+    import bench
+    records = lambda a: (a.full, a.sustain, a.host_io, a.cpu_frames, a.other_configs)
+    assert records(bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])) == (False, 0, 0, 0, False)
+    assert records(bench.parse_args(["--full"])) == (True, 300, 20, 1, True)
+    assert records(bench.parse_args(["--full", "--views", "8", "--people", "8", "--frames", "25008"])) == (True, 300, 20, 1, False)
+    assert records(bench.parse_args(["--full", "--sustain", "0", "--no-other-configs"])) == (True, 0, 20, 1, False)
+    assert records(bench.parse_args(["--host-io", "5", "--other-configs"])) == (False, 0, 5, 0, True)
+    r =subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
 def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
     """--dump-outputs: every file float32 / float64, integer tables exact, and a step larger than the budget written as a fixed, seeded
     sample of frames (the same frames on every run) that keeps the files under DUMP_BYTES_MAX."""

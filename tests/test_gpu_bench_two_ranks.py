@@ -1,5 +1,5 @@
 """GPU: the line the first `--gpus N` run of bench.py prints.  Two ranks share the one GPU of the test box (host-staged gloo
-collective: the rehearsal of the N > 1 call path); the headline command at N > 1 must also time BASELINE config 5 -- the configuration
+collective: the rehearsal of the N > 1 call path); the headline command at N > 1 with --full must also time BASELINE config 5 -- the configuration
 BASELINE defines by its scaling curve (200 k frames, C8 P8 over 8 GPUs = 25,008 frames per GPU; the sequential pass it shards:
 motion_capture.py:1062-1116) -- and every line must say what its collective was."""
 import json
@@ -23,7 +23,7 @@ def _check_collective(c, world):
 def test_two_ranks_print_config_4_and_config_5_with_their_collectives():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo", "--steps", "2",
-                        "--warmup", "1", "--sustain", "0", "--cpu-frames", "0"], capture_output=True, text=True, timeout=900, env=env)
+                        "--warmup", "1", "--sustain", "0", "--cpu-frames", "0", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["views"] == 5 and line["config"]["people"] == 4 and line["config"]["frames_per_gpu"] == 10000
