@@ -504,6 +504,41 @@ int mvmc_ik_solve_stages_rigs(const mvmcSkeleton* skel_host, const double* kps17
                               int p_max, const double* init_params, int stage_mask, int max_nfev, double* params_out,
                               double* joints_out, double* info_out, double* scratch, mvmcStream_t stream);
 
+/* ---- trajectory smoothing of finished tracklets (multiview_motion_capture_amd/smoothing.py).  No counterpart in the reference, whose
+ * only temporal element is the IK's warm start.  One Levenberg-Marquardt solve per identity over every frame from its first to its last:
+ * E = 1/2 sum_t sum_v |r_tv(x_t)|^2 (the IK's stage-1 residual at frame t's lengths, the views members[t] selects)
+ *   + 1/2 sum_t |Wv^1/2 (x_t - x_{t-1})|^2 + 1/2 sum_t |Wa^1/2 (x_{t+1} - 2 x_t + x_{t-1})|^2,
+ * x_t = the MVMC_SMOOTH_K stage-1 parameters of frame t (root translation, then the Euler angles of the joints whose rotation moves an
+ * observed joint); W diagonal: root_* on the translation, ang_* on the angles.  Every other column of a frame's 68 is held.  A frame
+ * (row) of the launch belongs to identity id_of[f]; identity i owns the rows [id_lo[i], id_lo[i+1]), consecutive frames, >= 2 of them.
+ * The host issues, with phase = 0, 1, ..., max_iter: mvmc_smooth_blocks (at x for phase 0, at x_trial after) then mvmc_smooth_step.
+ * Every decision is taken on the device; a stopped identity is skipped by both.  Nothing is allocated or synchronised inside. ---- */
+#define MVMC_SMOOTH_K 39
+#define MVMC_SMOOTH_BLOCK_DOUBLES 820    /* per row and buffer: J^T J upper triangle (780), J^T r (39), E */
+#define MVMC_SMOOTH_WORK_DOUBLES 3940    /* per row: the factor (780 + 2 x 1521), y / d, g, diag A (39 each) */
+#define MVMC_SMOOTH_INFO_DOUBLES 32      /* per identity: E_data, E_prior at the start; E_data, E_prior now; trials, accepted, mu, stop
+                                          * reason (0 running, 1 max_iter, 2 xtol, 3 predicted reduction below ftol E, 4 achieved
+                                          * reduction below ftol E, 5 factorisation failed); per trial 1 accepted / 0 rejected, -1 after
+                                          * the last.  max_iter <= MVMC_SMOOTH_INFO_DOUBLES - 8 */
+#define MVMC_SMOOTH_MAX_VIEWS 64
+
+/* The data blocks of one evaluation: one wave per row.  kps17 (F,C,P,17,3) as mvmc_ingest writes it; Pmats (R,C,3,4); rig_of (N) i32;
+ * members (N,C) i32 pose indices or -1 (a row without any: zero blocks); x (N,68) f64 the point; id_of (N) i32; ctl (n_ids,4) i32 the
+ * identities' control words ({stopped, buffer of the accepted point, 0, 0}; {0, 1, 0, 0} before phase 0).  blk (2,N,
+ * MVMC_SMOOTH_BLOCK_DOUBLES) f64 out: the row's blocks go to buffer 1 - ctl[id][1]. */
+int mvmc_smooth_blocks(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                       const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of, const int32_t* ctl,
+                       int n_frames, double* blk, mvmcStream_t stream);
+
+/* One LM step per identity, one 256-lane workgroup each.  phase 0: E at x from the blocks, mu = mu0; phase > 0: the trial x_trial is
+ * accepted when E(x_trial) < E(x) (x = x_trial, mu / 10; stop when the reduction is below ftol E), else mu x 10.  Then, unless
+ * max_iter trials are made: (A + mu diag A) d = -grad E by a block-banded Cholesky (the factor in work (N, MVMC_SMOOTH_WORK_DOUBLES)),
+ * stop when |d|_inf < xtol or the predicted reduction is below ftol E, else x_trial = x + d.  x, x_trial (N,68) f64 in/out; blk as
+ * written by mvmc_smooth_blocks; id_lo (n_ids + 1) i32; ctl (n_ids,4) i32 in/out; info (n_ids, MVMC_SMOOTH_INFO_DOUBLES) f64 out. */
+int mvmc_smooth_step(const mvmcSkeleton* skel_host, double* x, double* x_trial, const double* blk, const int32_t* id_lo, int n_ids,
+                     int n_frames, double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol,
+                     double xtol, int max_iter, int phase, int32_t* ctl, double* info, double* work, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

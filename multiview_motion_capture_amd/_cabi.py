@@ -23,6 +23,7 @@ IK_FD_WORK_DOUBLES = 40960
 IK_STEP_OUT_DOUBLES = 240
 BOUND_WORDS, ROW_WORDS = 56, 128
 BODY_INFO_DOUBLES, BODY_WORK_DOUBLES = 16, 270
+SMOOTH_K, SMOOTH_BLOCK_DOUBLES, SMOOTH_WORK_DOUBLES, SMOOTH_INFO_DOUBLES, SMOOTH_MAX_VIEWS = 39, 820, 3940, 32, 64
 
 # every symbol declared in include/mvmc.h
 SYMBOLS = (
@@ -31,6 +32,7 @@ SYMBOLS = (
     "mvmc_fmats_from_projections", "mvmc_st_affinity", "mvmc_track_assign", "mvmc_track_commit", "mvmc_debug_eigh",
     "mvmc_debug_trstep", "mvmc_ik_solve_stages", "mvmc_chain_run", "mvmc_svt_associate", "mvmc_debug_ik_solve_fd", "mvmc_debug_ik_model_step", "mvmc_ingest_dlt", "mvmc_ingest_dlt_f32", "mvmc_pack_message_words", "mvmc_pack_work_words", "mvmc_stitch_work_words", "mvmc_pack_tracks", "mvmc_stitch_chains",
     "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
+    "mvmc_smooth_blocks", "mvmc_smooth_step",
 )
 
 
@@ -135,6 +137,8 @@ def load():
         "mvmc_body_observe": [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, f64, vp, vp, vp, vp, vp],
         "mvmc_body_lengths": [SK, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, i32, f64, f64, f64, vp, vp, vp],
         "mvmc_ik_solve_stages_rigs": [SK, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
+        "mvmc_smooth_blocks": [SK, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp],
+        "mvmc_smooth_step": [SK, vp, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, f64, f64, i32, i32, vp, vp, vp, vp],
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
                 "mvmc_stitch_work_words": C.c_longlong}

@@ -412,6 +412,45 @@ def body_lengths(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor,
                                          float(xtol), _p(info), _p(work), _stream()), "mvmc_body_lengths")
     return info
 
+def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,
+                  id_of: torch.Tensor, ctl: torch.Tensor, blk: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None) -> None:
+    """The data blocks of the trajectory smoother at x (include/mvmc.h: mvmc_smooth_blocks), one wave per row, into blk (2,N,820)."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    N = x.shape[0]
+    _req(x, torch.float64, "x", (N, 68))
+    _req(rig_of, torch.int32, "rig_of", (N,))
+    _req(id_of, torch.int32, "id_of", (N,))
+    _req(members, torch.int32, "members", (N, Cn))
+    _req(ctl, torch.int32, "ctl", (None, 4))
+    _req(blk, torch.float64, "blk", (2, N, _cabi.SMOOTH_BLOCK_DOUBLES))
+    check(_cabi.load().mvmc_smooth_blocks(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of), _p(ctl),
+                                          N, _p(blk), _stream()), "mvmc_smooth_blocks")
+
+
+def smooth_step(x: torch.Tensor, x_trial: torch.Tensor, blk: torch.Tensor, id_lo: torch.Tensor, weights, mu0: float, ftol: float,
+                xtol: float, max_iter: int, phase: int, ctl: torch.Tensor, info: torch.Tensor, work: torch.Tensor,
+                skeleton: Optional[MvmcSkeleton] = None) -> None:
+    """One Levenberg-Marquardt step of every identity (include/mvmc.h: mvmc_smooth_step); weights = (root_vel, root_acc, ang_vel,
+    ang_acc).  x, x_trial (N,68), ctl (n_ids,4) i32, info (n_ids,32) and work (N,3940) are updated in place."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    N = x.shape[0]
+    n_ids = id_lo.shape[0] - 1
+    _req(x, torch.float64, "x", (N, 68))
+    _req(x_trial, torch.float64, "x_trial", (N, 68))
+    _req(blk, torch.float64, "blk", (2, N, _cabi.SMOOTH_BLOCK_DOUBLES))
+    _req(id_lo, torch.int32, "id_lo", (n_ids + 1,))
+    _req(ctl, torch.int32, "ctl", (n_ids, 4))
+    _req(info, torch.float64, "info", (n_ids, _cabi.SMOOTH_INFO_DOUBLES))
+    _req(work, torch.float64, "work", (N, _cabi.SMOOTH_WORK_DOUBLES))
+    rv, ra, av, aa = (float(w) for w in weights)
+    check(_cabi.load().mvmc_smooth_step(C.byref(sk), _p(x), _p(x_trial), _p(blk), _p(id_lo), n_ids, N, rv, ra, av, aa, float(mu0),
+                                        float(ftol), float(xtol), int(max_iter), int(phase), _p(ctl), _p(info), _p(work), _stream()),
+          "mvmc_smooth_step")
+
+
 def ik_solve_fd(kps17: torch.Tensor, Pmats: torch.Tensor, members: torch.Tensor, init_params: Optional[torch.Tensor] = None,
                 cold: Optional[torch.Tensor] = None, max_nfev_cold=50, max_nfev_warm=5, stage_mask=3,
                 skeleton: Optional[MvmcSkeleton] = None):

@@ -1,0 +1,345 @@
+"""Trajectory smoothing of finished tracklet records: one solve per identity over every frame from its first to its last.
+
+The IK solves each frame on its own (the body fit's pose step too: stage 1, 5 evaluations, warm from the frame's own pose), so nothing
+ties frame t to t +- 1, and a frame the tracker missed is a hole.  smooth_sequences() minimises, per identity (one record, frames f0..f1,
+the missing ones included),
+
+  E(X) = 1/2 sum_t sum_{v in V_t} |r_tv(x_t)|^2                                         (data: the IK's stage-1 residual)
+       + 1/2 sum_t |Wv^1/2 (x_t - x_{t-1})|^2 + 1/2 sum_t |Wa^1/2 (x_{t+1} - 2 x_t + x_{t-1})|^2      (prior)
+
+over x_t = the 39 stage-1 parameters of frame t (root translation, the Euler angles of the 12 joints whose rotation moves an observed
+joint: the columns of the IK's stage 1).  The other 6 joints' angles and the bone lengths are held per frame.  r_tv is
+solve_pose_reproj's residual (inverse_kinematics.py:219-234) at frame t's lengths; V_t is the body fit's selection (body_fit.py: the
+pose nearest to the record's joints per camera, MAX_DIST, MIN_SCORE) on the input record; a frame that is missing or has no selected
+view has no data term.  Wv, Wa are diagonal: root_* on the translation (px^2 / m^2), ang_* on the angles (px^2 / rad^2).
+
+Before the solve, every record frame's Euler triples are unwrapped towards the previous record frame's (the nearest of the 2 pi shifts
+of both branches (a, b, c) and (a + pi, pi - b, c + pi) of R = Rx Ry Rz: tracker records restart the IK cold at chain heads and births),
+and the missing frames start from the linear interpolation of the unwrapped record; their 6 held joints keep it, their lengths are the
+nearest earlier record frame's.  The solve is Levenberg-Marquardt, (A + mu diag A) d = -grad E with A = the Gauss-Newton data blocks +
+the exact prior Hessian, factored exactly by a block-banded Cholesky; mu starts at LM_MU0, / 10 after an accepted trial, x 10 after a
+rejected one; stop on max_iter, LM_XTOL or LM_FTOL, as the body fit's length step.
+
+Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; selection: mvmc_body_observe); NumPy
+restatement: tests/smooth_np.py.  Sequences with the same number of cameras share every launch, each with its own rig.
+"""
+from __future__ import annotations
+
+import math
+import time
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from .body_fit import MAX_DIST, MIN_SCORE, _record_arrays
+from .sequences import SequenceInput, check_sequences
+
+# Default prior weights: tools/smooth_weight_sweep.py on synthetic scene walks with ground truth (profiles/smooth_weight_sweep.json)
+ROOT_VEL, ROOT_ACC = 1e4, 1e4    # px^2 / m^2
+ANG_VEL, ANG_ACC = 1e4, 1e4      # px^2 / rad^2
+LM_MU0 = 1e-3       # Marquardt's damping: (A + mu diag(A)) d = -g, mu dimensionless
+LM_FTOL = 1e-12     # stop: predicted or achieved reduction below LM_FTOL E
+LM_XTOL = 1e-10     # stop: |d|_inf below LM_XTOL (m / rad)
+MAX_ITER_CAP = 24   # include/mvmc.h: MVMC_SMOOTH_INFO_DOUBLES - 8
+MAX_VIEWS = 64      # include/mvmc.h: MVMC_SMOOTH_MAX_VIEWS
+MAX_WORK_BYTES = 1 << 30
+_BLOCK, _WORK = 820, 3940   # include/mvmc.h: doubles per row
+
+
+def stage1_columns() -> np.ndarray:
+    """The 39 stage-1 columns of a 68-parameter row: translation, then the 3 angles of every joint that is a strict ancestor of an
+    observed joint (Ik1Tables::act[0])."""
+    from .device import SKEL_PARENTS
+    obs = [1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 14, 15, 16, 17]
+    moved = set()
+    for k in obs:
+        j = int(SKEL_PARENTS[k])
+        while j >= 0:
+            moved.add(j)
+            j = int(SKEL_PARENTS[j])
+    return np.array([0, 1, 2] + [3 + 3 * a + c for a in sorted(moved) for c in range(3)], dtype=np.int64)
+
+
+def unwrap_euler(ang: np.ndarray) -> np.ndarray:
+    """(n,18,3) Euler triples of consecutive record frames -> the same rotations, each triple the equivalent one nearest (Euclidean) to
+    the previous frame's: per branch ((a,b,c) and (a+pi, pi-b, c+pi)) the 2 pi shift of every component nearest to it, then the nearer
+    branch (a tie keeps the first).  Sequential from the first frame, which is kept."""
+    return unwrap_euler_many([ang])[0]
+
+
+def unwrap_euler_many(angs: Sequence[np.ndarray]) -> List[np.ndarray]:
+    """unwrap_euler of several records at once: one pass over the frame index for all of them (the same operations per element)."""
+    outs = [np.array(a, dtype=np.float64, copy=True).reshape(-1, 18, 3) for a in angs]
+    if not outs:
+        return []
+    n = np.array([o.shape[0] for o in outs])
+    pad = np.zeros((len(outs), int(n.max()), 18, 3))
+    for r, o in enumerate(outs):
+        pad[r, :o.shape[0]] = o
+    tp = 2.0 * math.pi
+    for k in range(1, pad.shape[1]):
+        live = np.flatnonzero(n > k)
+        prev, a = pad[live, k - 1], pad[live, k]
+        b = np.stack([a[..., 0] + math.pi, math.pi - a[..., 1], a[..., 2] + math.pi], axis=-1)
+        ca = a + tp * np.round((prev - a) / tp)
+        cb = b + tp * np.round((prev - b) / tp)
+        da = ((ca - prev) ** 2).sum(-1)
+        db = ((cb - prev) ** 2).sum(-1)
+        pad[live, k] = np.where((db < da)[..., None], cb, ca)
+    return [pad[r, :n[r]].copy() for r in range(len(outs))]
+
+
+def initial_trajectory(frames: np.ndarray, params: np.ndarray):
+    """One record's frames (n,) (increasing) and params (n,68) -> (x (m,68) over frames[0]..frames[-1], filled (m,) bool): unwrapped
+    record rows; the missing rows linearly interpolated in root and angles, lengths of the nearest earlier record frame."""
+    return initial_trajectories([frames], [params])[0]
+
+
+def initial_trajectories(frames_list: Sequence[np.ndarray], params_list: Sequence[np.ndarray]) -> list:
+    """initial_trajectory of several records (their Euler angles unwrapped in one pass)."""
+    ps = [np.array(p, np.float64, copy=True) for p in params_list]
+    un = unwrap_euler_many([p[:, 3:57].reshape(-1, 18, 3) for p in ps])
+    out = []
+    for frames, p, u in zip(frames_list, ps, un):
+        frames = np.asarray(frames, np.int64)
+        p[:, 3:57] = u.reshape(-1, 54)
+        full = np.arange(frames[0], frames[-1] + 1)
+        m = full.size
+        x = np.empty((m, 68))
+        for c in range(57):
+            x[:, c] = np.interp(full, frames, p[:, c])
+        src = np.searchsorted(frames, full, side="right") - 1
+        x[:, 57:] = p[src, 57:]
+        filled = np.ones(m, dtype=bool)
+        filled[frames - frames[0]] = False
+        x[frames - frames[0]] = p      # the record's own rows exactly
+        out.append((x, filled))
+    return out
+
+
+def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes):
+    w = np.array([root_vel, root_acc, ang_vel, ang_acc], dtype=np.float64)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("smooth_sequences: the prior weights must be finite and >= 0")
+    if not (w[0] + w[1] > 0 and w[2] + w[3] > 0):
+        raise ValueError("smooth_sequences: root_vel + root_acc > 0 and ang_vel + ang_acc > 0 required")
+    if int(max_iter) != max_iter or not 0 <= int(max_iter) <= MAX_ITER_CAP:
+        raise ValueError(f"smooth_sequences: 0 <= max_iter <= {MAX_ITER_CAP} required")
+    if not int(max_work_bytes) > 0:
+        raise ValueError("smooth_sequences: max_work_bytes must be positive")
+    return w
+
+
+def _check(sequences, tracklets_per_sequence):
+    if len(tracklets_per_sequence) != len(sequences):
+        raise ValueError(f"smooth_sequences: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
+    shapes = check_sequences(sequences)
+    recs = []
+    for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
+        if C > MAX_VIEWS:
+            raise ValueError(f"sequence {s}: {C} cameras, at most {MAX_VIEWS}")
+        rr = []
+        for j, t in enumerate(tl):
+            where = f"sequence {s}, record {j}"
+            fr, par, jn = _record_arrays(t, F, where)
+            if np.any(np.diff(fr) <= 0):
+                raise ValueError(f"{where}: frame indices must increase")
+            if not np.all(np.isfinite(par)):
+                raise ValueError(f"{where}: parameters must be finite")
+            rr.append((fr, par, jn))
+        recs.append(rr)
+    return shapes, recs
+
+
+def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], root_vel: float = ROOT_VEL,
+                     root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
+                     fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0",
+                     timings: Optional[dict] = None) -> List[list]:
+    """Smooth every identity of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows
+    track_sequences and fit_sequences take -- from its MvTracklet records (fit_sequences, track_sequences, run_main_batched,
+    MvTracker.update_4d, LivePool).  Returns, per sequence, NEW records in the input order (the inputs are not touched): the same
+    track_id, state, hits, time_since_update (and bone_lens where the input has one); frame_idxs f0..f1 without holes (fill_gaps=False:
+    the input's frames, the others solved but left out); poses[k] = (frame, PoseShapeParam, FK joints); ``smooth_filled`` (n,) bool:
+    the frame was missing from the input; ``smooth_views`` (n,) the views of the data term; ``smooth_select`` (n, C) the pose slot
+    (ingest order) used per camera or -1; ``smooth_cost`` [E_data, E_prior] at the start and at the end; ``smooth_trials`` per trial 1
+    accepted / 0 rejected.  A one-frame record is returned as a copy of the input's (cost 0).
+    Sequences with the same camera count share every launch; max_work_bytes caps the device workspace (~45 KB per frame): a group
+    larger than the cap runs as several launch sequences one after another (an identity larger than the cap gets one of its own).
+    timings: a dict that receives the seconds spent in {"prepare" (input checks, unwrapping and interpolation, packing and uploads),
+    "select", "blocks", "solve", "records"} (synchronising between the parts)."""
+    t_start = time.perf_counter()
+    w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
+    if len(sequences) == 0:
+        if len(tracklets_per_sequence):
+            raise ValueError("smooth_sequences: records without sequences")
+        return []
+    shapes, recs = _check(sequences, tracklets_per_sequence)
+    import torch
+
+    from . import device as dev
+    d = torch.device(device)
+    tm = {"prepare": time.perf_counter() - t_start, "select": 0.0, "blocks": 0.0, "solve": 0.0, "records": 0.0}
+
+    def lap(k, t0):
+        if timings is not None:
+            torch.cuda.synchronize(d)
+        t1 = time.perf_counter()
+        tm[k] += t1 - t0
+        return t1
+
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+    out: List[list] = [[None] * len(r) for r in recs]
+    by_c = {}
+    for i, (_, C, _) in enumerate(shapes):
+        by_c.setdefault(C, []).append(i)
+    per_row = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
+    for C, ids in by_c.items():
+        items = [(i, j) for i in ids for j in range(len(recs[i]))]
+        if not items:
+            continue
+        t0 = time.perf_counter()
+        Pg = max(shapes[i][2] for i in ids)
+        f_off = np.concatenate([[0], np.cumsum([shapes[i][0] for i in ids])]).astype(np.int64)
+        ks = [np.asarray(sequences[i][0]) for i in ids]
+        dt = np.float32 if all(k.dtype == np.float32 for k in ks) else np.float64
+        kps = np.zeros((int(f_off[-1]), C, Pg, ks[0].shape[3], 3), dtype=dt)
+        cnt = np.zeros((int(f_off[-1]), C), dtype=np.int32)
+        for r, i in enumerate(ids):
+            kps[f_off[r]:f_off[r + 1], :, :ks[r].shape[2]] = ks[r]
+            cnt[f_off[r]:f_off[r + 1]] = np.asarray(sequences[i][1])
+        Pm = np.array([[np.asarray(c.P, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
+        rig_of_seq = {i: r for r, i in enumerate(ids)}
+        t0 = lap("prepare", t0)
+        # selection on the record frames, in (sequence, record, frame) order (body_fit.fit_sequences' problems)
+        fr = [recs[i][j][0] for i, j in items]
+        n_of = np.array([f.shape[0] for f in fr], dtype=np.int64)
+        rec_lo = np.concatenate([[0], np.cumsum(n_of)]).astype(np.int64)
+        frame_of = np.concatenate([f + f_off[rig_of_seq[i]] for f, (i, _) in zip(fr, items)]).astype(np.int32)
+        rig_of = np.repeat(np.array([rig_of_seq[i] for i, _ in items], dtype=np.int32), n_of)
+        rank = np.repeat(np.array([j for _, j in items], dtype=np.int32), n_of)
+        joints = np.concatenate([recs[i][j][2] for i, j in items])
+        order = np.argsort(frame_of, kind="stable").astype(np.int32)
+        fs = frame_of[order]
+        lo = np.searchsorted(fs, frame_of, side="left").astype(np.int32)
+        hi = np.searchsorted(fs, frame_of, side="right").astype(np.int32)
+        k17, c17 = dev.ingest(T(kps), T(cnt))
+        Pm_d = T(Pm)
+        members, n_views, _, _ = dev.body_observe(k17, c17, Pm_d, T(frame_of), T(rig_of), T(joints), T(order), T(lo), T(hi), T(rank),
+                                                  MAX_DIST, MIN_SCORE)
+        mem_h = members.cpu().numpy()
+        nv_h = n_views.cpu().numpy()
+        t0 = lap("select", t0)
+        # full trajectories of the identities with two frames or more
+        traj = []
+        multi = [a for a in range(len(items)) if fr[a].shape[0] >= 2]
+        inits = initial_trajectories([fr[a] for a in multi], [recs[items[a][0]][items[a][1]][1] for a in multi])
+        for a, (x0, filled) in zip(multi, inits):
+            i, j = items[a]
+            f = fr[a]
+            m = x0.shape[0]
+            mem = -np.ones((m, C), np.int32)
+            nvf = np.zeros(m, np.int32)
+            rows = f - f[0]
+            mem[rows] = mem_h[rec_lo[a]:rec_lo[a + 1]]
+            nvf[rows] = nv_h[rec_lo[a]:rec_lo[a + 1]]
+            traj.append((a, x0, filled, mem, nvf, rig_of_seq[i]))
+        t0 = lap("prepare", t0)
+        res = {}
+        cap = max(1, int(max_work_bytes) // per_row)
+        at = 0
+        while at < len(traj):
+            b = at + 1
+            rows = traj[at][1].shape[0]
+            while b < len(traj) and rows + traj[b][1].shape[0] <= cap:
+                rows += traj[b][1].shape[0]
+                b += 1
+            part = traj[at:b]
+            at = b
+            t0 = time.perf_counter()
+            x_h = np.concatenate([p[1] for p in part])
+            N = x_h.shape[0]
+            m_of = np.array([p[1].shape[0] for p in part])
+            id_lo = np.concatenate([[0], np.cumsum(m_of)]).astype(np.int32)
+            id_of = np.repeat(np.arange(len(part), dtype=np.int32), m_of)
+            x = T(x_h)
+            xt = x.clone()
+            mem_d = T(np.concatenate([p[3] for p in part]))
+            rig_d = T(np.repeat(np.array([p[5] for p in part], np.int32), m_of))
+            ctl = torch.zeros((len(part), 4), dtype=torch.int32, device=d)
+            ctl[:, 1] = 1
+            info = torch.empty((len(part), 32), dtype=torch.float64, device=d)
+            blk = torch.empty((2, N, _BLOCK), dtype=torch.float64, device=d)
+            work = torch.empty((N, _WORK), dtype=torch.float64, device=d)
+            id_of_d, id_lo_d = T(id_of), T(id_lo)
+            t0 = lap("prepare", t0)
+            for phase in range(int(max_iter) + 1):
+                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x if phase == 0 else xt, id_of_d, ctl, blk)
+                t0 = lap("blocks", t0)
+                dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info, work)
+                t0 = lap("solve", t0)
+            jn = dev.fk(x).cpu().numpy()
+            xs, inf = x.cpu().numpy(), info.cpu().numpy()
+            for s, p in enumerate(part):
+                sl = slice(id_lo[s], id_lo[s + 1])
+                res[p[0]] = (xs[sl], jn[sl], inf[s])
+            lap("records", t0)
+        t0 = time.perf_counter()
+        _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, Pg)
+        lap("records", t0)
+    if timings is not None:
+        timings.update(tm)
+    return out
+
+
+def _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, Pg):
+    from .inverse_kinematics import PoseShapeParam
+    from .motion_capture import MvTracklet
+    from .pose_def import KpsFormat, Pose
+    tr = {p[0]: p for p in traj}
+    ones = np.ones((18, 1))
+    for a, (i, j) in enumerate(items):
+        src = tracklets_per_sequence[i][j]
+        f = recs[i][j][0]
+        if a in tr:
+            _, _, filled, mem, nvf, _ = tr[a]
+            xs, jn, inf = res[a]
+            frm = np.arange(f[0], f[-1] + 1)
+            keep = np.ones(frm.size, bool) if fill_gaps else ~filled
+            idx = np.flatnonzero(keep)
+            poses = [(int(frm[k]), PoseShapeParam(xs[k, :3].copy(), xs[k, 3:57].reshape(18, 3).copy(), xs[k, 57:].copy()),
+                      Pose(KpsFormat.BASIC_18, jn[k].copy(), ones.copy(), None)) for k in idx]
+            cost = np.array([inf[0], inf[1], inf[2], inf[3]])
+            n_t = int(inf[4])
+            trials = [int(v) for v in inf[8:8 + n_t]]
+            filled_k, views_k, mem_k = filled[idx], nvf[idx], mem[idx]
+        else:   # one frame: nothing to smooth (a copy of the input's pose)
+            _, par, jnt = recs[i][j]
+            poses = [(int(f[0]), PoseShapeParam(par[0, :3].copy(), par[0, 3:57].reshape(18, 3).copy(), par[0, 57:].copy()),
+                      Pose(KpsFormat.BASIC_18, jnt[0].copy(), ones.copy(), None))]
+            cost = np.zeros(4)
+            trials = []
+            filled_k = np.zeros(1, bool)
+            views_k = nv_h[rec_lo[a]:rec_lo[a + 1]].astype(np.int32)
+            mem_k = mem_h[rec_lo[a]:rec_lo[a + 1]]
+        t = MvTracklet(src.track_id, poses[0][0], poses[0][1], poses[0][2])
+        t.frame_idxs = [p[0] for p in poses]
+        t.poses = poses
+        t.state = src.state
+        t.hits = src.hits
+        t.time_since_update = getattr(src, "time_since_update", 0)
+        if getattr(src, "bone_lens", None) is not None:
+            t.bone_lens = np.array(src.bone_lens, np.float64).copy()
+        t.smooth_filled = np.asarray(filled_k, bool)
+        t.smooth_views = np.asarray(views_k, np.int32)
+        t.smooth_select = np.where(mem_k >= 0, mem_k % Pg, -1).astype(np.int32)
+        t.smooth_cost = cost
+        t.smooth_trials = trials
+        out[i][j] = t
+
+
+def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, root_vel: float = ROOT_VEL,
+                     root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
+                     fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0", timings: Optional[dict] = None) -> list:
+    """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records."""
+    return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel, ang_acc=ang_acc,
+                            max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings)[0]
