@@ -539,6 +539,35 @@ int mvmc_smooth_step(const mvmcSkeleton* skel_host, double* x, double* x_trial, 
                      int n_frames, double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol,
                      double xtol, int max_iter, int phase, int32_t* ctl, double* info, double* work, mvmcStream_t stream);
 
+/* ---- fixed-lag smoothing of live sessions (multiview_motion_capture_amd/live_smoothing.py).  The objective is the trajectory
+ * smoother's above; the problem is a short sliding window per live identity (one tracklet of one session), and ONE launch does a whole
+ * tick of every identity of every session: one 256-lane workgroup per item.  State that stays on the device between ticks, per
+ * identity slot: rows (MVMC_SMOOTH_WIN_RING, 68) f64 and members (MVMC_SMOOTH_WIN_RING, C) i32, row r of the identity (r = frame -
+ * first frame) at ring position r mod MVMC_SMOOTH_WIN_RING, and count (2) i32 = {rows, first frame}.  kps17 is the sessions' ring of
+ * ingested keypoints, (F,C,P,17,3) as mvmc_ingest writes them, which the members index.
+ * An item (MVMC_SMOOTH_WIN_ITEM_INTS i32): {slot, rig, d, is_data, reset, src, first_frame, work_row}.  The identity gets d new rows
+ * (reset: it is new and gets exactly one): d - 1 missing rows, then row src of new_params (n_new,68) / new_members (n_new,C) when
+ * is_data, else one more missing row; a missing row is a copy of the identity's last row and has no members.  Then, with n rows: the
+ * last m = min(window, n) rows are free, the h = min(2, n - m) rows before them frozen history, and n_iter Levenberg-Marquardt trials
+ * (mvmc_smooth_step's rules, mu from mu0) minimise the free rows' data terms + every velocity / acceleration term that touches a free
+ * row over the free rows' MVMC_SMOOTH_K columns, warm from the rows' values; the free rows go back into the ring.  n < 2: no solve.
+ *   info (n_items, MVMC_SMOOTH_WIN_INFO_DOUBLES) f64 out: E_data, E_prior at the start; E_data, E_prior at the end; trials, accepted,
+ *   mu, stop reason (mvmc_smooth_step's; 6: the item was malformed and skipped; 0 with trials 0: nothing to solve); per trial 1 / 0,
+ *   -1 after the last.  n_iter <= MVMC_SMOOTH_WIN_INFO_DOUBLES - 8.
+ *   work: device workspace of at least mvmc_smooth_window_work_doubles(n_items, window) doubles; item i uses rows work_row ..
+ *   work_row + window of its row part (work_row + window <= n_items * window).
+ * Argument errors return before any HIP call; nothing is allocated or synchronised inside. ---- */
+#define MVMC_SMOOTH_WIN_MAX 32
+#define MVMC_SMOOTH_WIN_RING 66
+#define MVMC_SMOOTH_WIN_ITEM_INTS 8
+#define MVMC_SMOOTH_WIN_INFO_DOUBLES 16
+long long mvmc_smooth_window_work_doubles(int n_items, int window);   /* -1: bad arguments */
+int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats, int n_rigs,
+                       const int32_t* items, int n_items, const double* new_params, const int32_t* new_members, int n_new,
+                       double* rows, int32_t* members, int32_t* count, int n_slots, int window, int n_iter, double root_vel,
+                       double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
+                       double* work, long long work_doubles, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

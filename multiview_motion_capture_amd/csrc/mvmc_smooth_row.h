@@ -1,0 +1,229 @@
+// The row block of the trajectory smoothers (csrc/mvmc_smooth.hip: finished tracklets; csrc/mvmc_smooth_window.hip: live sessions):
+// FK, the stage-1 residual and its analytic Jacobian of ONE row on ONE wave, and the prior's coefficients.  Included inside the
+// including file's anonymous namespace, after mvmc_common.h, mvmc_track.hip and mvmc_ik1.hip (MVMC_DEVICE_ONLY).
+#pragma once
+constexpr int SK = MVMC_SMOOTH_K;                 // 39 stage-1 parameters (Ik1Tables::act[0])
+constexpr int SK2 = SK * SK;
+constexpr int SKH = SK * (SK + 1) / 2;            // packed triangle
+constexpr int SM_BLK = MVMC_SMOOTH_BLOCK_DOUBLES;  // per frame: J^T J upper (SKH), J^T r (SK), E
+constexpr int SM_WORK = MVMC_SMOOTH_WORK_DOUBLES;  // per frame: L_tt lower (SKH), L_{t+1,t}, L_{t+2,t} (SK2 each), y / d, g, diag A (SK each)
+constexpr int W_L1 = SKH, W_L2 = SKH + SK2, W_Y = SKH + 2 * SK2, W_G = W_Y + SK, W_D = W_G + SK;
+static_assert(W_D + SK <= SM_WORK, "smoothing workspace layout");
+static_assert(SKH + SK + 1 <= SM_BLK, "smoothing block layout");
+
+// upper-triangle index (s <= t) of the packed J^T J, and the packed lower triangle (r >= c) of the factor
+__device__ __forceinline__ int sm_up(int s, int t) { return s * SK - s * (s - 1) / 2 + (t - s); }
+__device__ __forceinline__ int sm_lo(int r, int c) { return r * (r + 1) / 2 + c; }
+
+// ---- blocks ----
+struct SmBlkLds {
+    double Rl[18 * 9], Rg[18 * 9], pos[18 * 3], ax[18 * 9];   // local and global rotations, joints, rotation axes (global frame)
+    double W[NOBS * 6], t[NOBS * 3];
+    double D[NOBS * 3 * SK], WD[NOBS * 3 * SK];
+    int mq[MVMC_SMOOTH_MAX_VIEWS], mc[MVMC_SMOOTH_MAX_VIEWS];
+    int nv;
+};
+
+// One row on the calling wave: members (C) pose indices or -1, Prig the row's rig (C,3,4), x the row's 68 parameters -> out (SM_BLK)
+__device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, const double* __restrict__ kps17,
+                                             const double* __restrict__ Prig, int C, int Pmax, const int32_t* __restrict__ members,
+                                             const double* __restrict__ x, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) {
+        int n = 0;
+        for (int c = 0; c < C; ++c) {
+            const int m = members[c];
+            if (m >= 0 && n < MVMC_SMOOTH_MAX_VIEWS) { L.mq[n] = m; L.mc[n] = (m / Pmax) % C; ++n; }
+        }
+        L.nv = n;
+    }
+    MVMC_WAVE_SYNC();
+    const int nv = uni(L.nv);
+    if (nv == 0) {   // no data: the prior alone places the frame
+        for (int i = lane; i < SM_BLK; i += 64) out[i] = 0.0;
+        return;
+    }
+    if (lane < 18) {
+        euler_to_rot(x + 3 + 3 * lane, &L.Rl[9 * lane]);
+        // the Euler axes in the parent's frame (oracle/trf_np.py: ik_jacobian): x, Rx y, Rx Ry z
+        const double a0 = x[3 + 3 * lane], a1 = x[4 + 3 * lane];
+        const double ca = cos(a0), sa = sin(a0), cb = cos(a1), sb = sin(a1);
+        double* A = &L.ax[9 * lane];
+        A[0] = 1.0; A[1] = 0.0; A[2] = 0.0;
+        A[3] = 0.0; A[4] = ca; A[5] = sa;
+        A[6] = sb; A[7] = -sa * cb; A[8] = ca * cb;
+    }
+    if (lane < 3) L.pos[lane] = x[lane];
+    MVMC_WAVE_SYNC();
+    if (lane < 9) L.Rg[lane] = L.Rl[lane];
+    MVMC_WAVE_SYNC();
+    for (int j = 1; j < 18; ++j) {
+        const int p = T.parents[j];
+        const double* Gp = &L.Rg[9 * p];
+        if (lane < 9) {
+            const int r = lane / 3, c = lane - 3 * r;
+            const double* Rj = &L.Rl[9 * j];
+            L.Rg[9 * j + lane] = Gp[3 * r] * Rj[c] + Gp[3 * r + 1] * Rj[3 + c] + Gp[3 * r + 2] * Rj[6 + c];
+        } else if (lane < 12) {
+            const int e = lane - 9;
+            const double len = x[57 + T.side_map[j]];
+            const double o0 = T.dirs[3 * j] * len, o1 = T.dirs[3 * j + 1] * len, o2 = T.dirs[3 * j + 2] * len;
+            L.pos[3 * j + e] = Gp[3 * e] * o0 + Gp[3 * e + 1] * o1 + Gp[3 * e + 2] * o2 + L.pos[3 * p + e];
+        }
+        MVMC_WAVE_SYNC();
+    }
+    double axl[9];
+    if (lane < 18) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) axl[e] = L.ax[9 * lane + e];
+    }
+    MVMC_WAVE_SYNC();
+    if (lane < 18) {   // axes into the global frame: R_parent a (the root's parent frame is the world)
+        const int p = T.parents[lane];
+        for (int c = 0; c < 3; ++c)
+            for (int e = 0; e < 3; ++e)
+                L.ax[9 * lane + 3 * c + e] = p < 0 ? axl[3 * c + e]
+                                                   : L.Rg[9 * p + 3 * e] * axl[3 * c] + L.Rg[9 * p + 3 * e + 1] * axl[3 * c + 1] +
+                                                         L.Rg[9 * p + 3 * e + 2] * axl[3 * c + 2];
+    }
+    // residual and the per-joint blocks: lane (k, r) = observed joint k in the views r, r + 4, ... (as ik1_eval)
+    const int k = lane & 15, r = lane >> 4;
+    const double X0 = L.pos[3 * kIkSkel[k]], X1 = L.pos[3 * kIkSkel[k] + 1], X2 = L.pos[3 * kIkSkel[k] + 2];
+    const int obs = kIkObs[k];
+    double f2 = 0.0, o[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int v = r; v < nv; v += 4) {
+        const double* kp = kps17 + (size_t)L.mq[v] * 51;
+        const double* P = Prig + (size_t)L.mc[v] * 12;
+        double ob0, ob1, s;
+        if (obs < 17) { ob0 = kp[obs * 3]; ob1 = kp[obs * 3 + 1]; s = kp[obs * 3 + 2]; }
+        else {
+            const double sh0 = 0.5 * (kp[5 * 3] + kp[6 * 3]), hp0 = 0.5 * (kp[11 * 3] + kp[12 * 3]);
+            const double sh1 = 0.5 * (kp[5 * 3 + 1] + kp[6 * 3 + 1]), hp1 = 0.5 * (kp[11 * 3 + 1] + kp[12 * 3 + 1]);
+            ob0 = 0.5 * (sh0 + hp0); ob1 = 0.5 * (sh1 + hp1);
+            s = kp[5 * 3 + 2] * kp[6 * 3 + 2];
+            s *= kp[11 * 3 + 2] * kp[12 * 3 + 2];
+        }
+        const double h0 = P[0] * X0 + P[1] * X1 + P[2] * X2 + P[3];
+        const double h1 = P[4] * X0 + P[5] * X1 + P[6] * X2 + P[7];
+        const double h2 = P[8] * X0 + P[9] * X1 + P[10] * X2 + P[11];
+        const double w = 1e-5 + h2;
+        const double u = h0 / w, vv = h1 / w;
+        const double fu = (u - ob0) * s, fv = (vv - ob1) * s;
+        f2 += fu * fu + fv * fv;
+        double du[3], dv[3];
+        for (int c = 0; c < 3; ++c) {
+            du[c] = (P[c] - u * P[8 + c]) / w;
+            dv[c] = (P[4 + c] - vv * P[8 + c]) / w;
+        }
+        const double s2 = s * s;
+        o[0] += s2 * (du[0] * du[0] + dv[0] * dv[0]);
+        o[1] += s2 * (du[0] * du[1] + dv[0] * dv[1]);
+        o[2] += s2 * (du[0] * du[2] + dv[0] * dv[2]);
+        o[3] += s2 * (du[1] * du[1] + dv[1] * dv[1]);
+        o[4] += s2 * (du[1] * du[2] + dv[1] * dv[2]);
+        o[5] += s2 * (du[2] * du[2] + dv[2] * dv[2]);
+        o[6] += s * (du[0] * fu + dv[0] * fv);
+        o[7] += s * (du[1] * fu + dv[1] * fv);
+        o[8] += s * (du[2] * fu + dv[2] * fv);
+    }
+    const double E = 0.5 * wave_sum(f2);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+        o[e] += xor_lane<16>(o[e]);
+        o[e] += xor_lane<32>(o[e]);
+    }
+    if (lane < NOBS) {
+#pragma unroll
+        for (int e = 0; e < 6; ++e) L.W[lane * 6 + e] = o[e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) L.t[lane * 3 + e] = o[6 + e];
+    }
+    MVMC_WAVE_SYNC();
+    // D_k (3 x 39) = d X_k / d x: translation, then per active Euler column cross(axis, X_k - X_a) when joint a is a strict ancestor
+    for (int i = lane; i < NOBS * SK; i += 64) {
+        const int kk = i / SK, col = i - kk * SK, K = kIkSkel[kk];
+        double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+        const int act = T.act[0][col];
+        if (act < 3) { d0 = act == 0; d1 = act == 1; d2 = act == 2; }
+        else {
+            const int a = (act - 3) / 3, c = (act - 3) - 3 * ((act - 3) / 3);
+            if ((T.anc[K] >> a) & 1) {
+                const double* A = &L.ax[9 * a + 3 * c];
+                const double l0 = L.pos[3 * K] - L.pos[3 * a], l1 = L.pos[3 * K + 1] - L.pos[3 * a + 1], l2 = L.pos[3 * K + 2] - L.pos[3 * a + 2];
+                d0 = A[1] * l2 - A[2] * l1;
+                d1 = A[2] * l0 - A[0] * l2;
+                d2 = A[0] * l1 - A[1] * l0;
+            }
+        }
+        L.D[(kk * 3) * SK + col] = d0;
+        L.D[(kk * 3 + 1) * SK + col] = d1;
+        L.D[(kk * 3 + 2) * SK + col] = d2;
+    }
+    MVMC_WAVE_SYNC();
+    for (int i = lane; i < NOBS * SK; i += 64) {
+        const int kk = i / SK, col = i - kk * SK;
+        const double* Wk = &L.W[kk * 6];
+        const double a0 = L.D[(kk * 3) * SK + col], a1 = L.D[(kk * 3 + 1) * SK + col], a2 = L.D[(kk * 3 + 2) * SK + col];
+        L.WD[(kk * 3) * SK + col] = Wk[0] * a0 + Wk[1] * a1 + Wk[2] * a2;
+        L.WD[(kk * 3 + 1) * SK + col] = Wk[1] * a0 + Wk[3] * a1 + Wk[4] * a2;
+        L.WD[(kk * 3 + 2) * SK + col] = Wk[2] * a0 + Wk[4] * a1 + Wk[5] * a2;
+    }
+    MVMC_WAVE_SYNC();
+    for (int i = lane; i < SKH; i += 64) {
+        int s = 0, rem = i;
+        while (rem >= SK - s) { rem -= SK - s; ++s; }
+        const int t = s + rem;
+        double h = 0.0;
+        for (int q = 0; q < NOBS * 3; ++q) h += L.D[q * SK + s] * L.WD[q * SK + t];
+        out[i] = h;
+    }
+    if (lane < SK) {
+        double g = 0.0;
+        for (int q = 0; q < NOBS * 3; ++q) g += L.D[q * SK + lane] * L.t[q];
+        out[SKH + lane] = g;
+    }
+    if (lane == 0) {
+        out[SKH + SK] = E;
+        for (int i = SKH + SK + 1; i < SM_BLK; ++i) out[i] = 0.0;
+    }
+}
+
+// prior Hessian coefficient between local frames i and j of n (|i - j| <= 2): velocity (Dv^T Dv) and acceleration (Da^T Da) terms
+__device__ __forceinline__ double sm_cv(int i, int j, int n) {
+    const int hi = i > j ? i : j, lo = i < j ? i : j;
+    double s = 0.0;
+    for (int k = hi < 1 ? 1 : hi; k <= lo + 1 && k < n; ++k) {   // term k: x_k - x_{k-1}
+        const double a = (i == k) ? 1.0 : -1.0, b = (j == k) ? 1.0 : -1.0;
+        s += a * b;
+    }
+    return s;
+}
+__device__ __forceinline__ double sm_ca(int i, int j, int n) {
+    const int hi = i > j ? i : j, lo = i < j ? i : j;
+    double s = 0.0;
+    for (int c = hi - 1 < 1 ? 1 : hi - 1; c <= lo + 1 && c + 1 < n; ++c) {   // term c: x_{c+1} - 2 x_c + x_{c-1}
+        const double a = (i == c) ? -2.0 : 1.0, b = (j == c) ? -2.0 : 1.0;
+        s += a * b;
+    }
+    return s;
+}
+
+// the prior's gradient at local frame i, parameter q (column cx of x): Dv^T Dv x and Da^T Da x through the differences
+__device__ __forceinline__ double sm_prior_grad(const double* __restrict__ x, int i, int n, int cx, double wv, double wa) {
+    double gv = 0.0, ga = 0.0;
+    if (i >= 1) gv += x[(size_t)i * 68 + cx] - x[(size_t)(i - 1) * 68 + cx];
+    if (i + 1 < n) gv -= x[(size_t)(i + 1) * 68 + cx] - x[(size_t)i * 68 + cx];
+    for (int c = i - 1; c <= i + 1; ++c) {
+        if (c < 1 || c + 1 >= n) continue;
+        const double acc = (x[(size_t)(c + 1) * 68 + cx] - 2.0 * x[(size_t)c * 68 + cx]) + x[(size_t)(c - 1) * 68 + cx];
+        ga += (c == i ? -2.0 : 1.0) * acc;
+    }
+    return wv * gv + wa * ga;
+}
+
+inline bool sm_tables(const mvmcSkeleton* skel_host, Ik1Tables* T) {
+    SkelDev sk;
+    if (!skel_to_dev(skel_host, &sk) || sk.n_side != MVMC_N_SIDE) return false;
+    ik1_build_tables_host(*T, sk);
+    return T->na[0] == SK;
+}

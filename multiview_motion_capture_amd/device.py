@@ -451,6 +451,52 @@ def smooth_step(x: torch.Tensor, x_trial: torch.Tensor, blk: torch.Tensor, id_lo
           "mvmc_smooth_step")
 
 
+_SW_WORK = {}
+
+
+def smooth_window_work(n_items: int, window: int, dev) -> torch.Tensor:
+    """Workspace of mvmc_smooth_window for ``n_items`` identities of one tick: one buffer per (device, stream), sized by the identities
+    active in the tick and grown on demand (include/mvmc.h: mvmc_smooth_window_work_doubles)."""
+    need = int(_cabi.load().mvmc_smooth_window_work_doubles(int(n_items), int(window)))
+    if need < 0:
+        raise ValueError(f"smooth_window: no workspace for {n_items} items of window {window}")
+    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    buf = _SW_WORK.get(key)
+    if buf is None or buf.numel() < need:
+        buf = torch.empty((max(need, 1),), dtype=torch.float64, device=dev)
+        _SW_WORK[key] = buf
+    return buf
+
+
+def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, new_params: torch.Tensor, new_members: torch.Tensor,
+                  rows: torch.Tensor, members: torch.Tensor, count: torch.Tensor, window: int, n_iter: int, weights, mu0: float,
+                  ftol: float, xtol: float, skeleton: Optional[MvmcSkeleton] = None) -> torch.Tensor:
+    """One tick of the live smoother for every item (include/mvmc.h: mvmc_smooth_window), one launch.  kps17 (F,C,P,17,3) the
+    sessions' keypoint ring; Pmats (R,C,3,4); items (n,8) i32; new_params (B,68), new_members (B,C) the tick's data rows; rows
+    (n_slots,66,68), members (n_slots,66,C), count (n_slots,2) the identities' device state, updated in place.  -> info (n,16)."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    n = items.shape[0]
+    _req(items, torch.int32, "items", (n, _cabi.SMOOTH_WIN_ITEM_INTS))
+    B = new_params.shape[0]
+    _req(new_params, torch.float64, "new_params", (B, 68))
+    _req(new_members, torch.int32, "new_members", (B, Cn))
+    n_slots = rows.shape[0]
+    _req(rows, torch.float64, "rows", (n_slots, _cabi.SMOOTH_WIN_RING, 68))
+    _req(members, torch.int32, "members", (n_slots, _cabi.SMOOTH_WIN_RING, Cn))
+    _req(count, torch.int32, "count", (n_slots, 2))
+    rv, ra, av, aa = (float(w) for w in weights)
+    info = torch.empty((n, _cabi.SMOOTH_WIN_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
+    work = smooth_window_work(n, window, rows.device)
+    check(_cabi.load().mvmc_smooth_window(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(new_params),
+                                          _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window), int(n_iter), rv, ra,
+                                          av, aa, float(mu0), float(ftol), float(xtol), _p(info), _p(work), int(work.numel()), _stream()),
+          "mvmc_smooth_window")
+    return info
+
+
 def ik_solve_fd(kps17: torch.Tensor, Pmats: torch.Tensor, members: torch.Tensor, init_params: Optional[torch.Tensor] = None,
                 cold: Optional[torch.Tensor] = None, max_nfev_cold=50, max_nfev_warm=5, stage_mask=3,
                 skeleton: Optional[MvmcSkeleton] = None):

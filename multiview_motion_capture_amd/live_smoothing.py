@@ -1,0 +1,491 @@
+"""Fixed-lag smoothing of live sessions: the trajectory smoother's objective (smoothing.py) on a short sliding window per live identity,
+one kernel launch per tick for every identity of every session (include/mvmc.h: mvmc_smooth_window; csrc/mvmc_smooth_window.hip).
+
+Per identity (one tracklet of one session) the rows are the consecutive frames from its first frame f0 to the session's newest.  A row
+is a DATA row when the tracker appended a pose for that frame (commit_tables' rule: the tracklet is new or its hits grew), else a
+MISSING row.  A data row starts from the tracker's 68 parameters, its Euler triples unwrapped (smoothing.unwrap_euler's rule) towards
+the unwrapped INPUT angles of the identity's previous data row, so that the stream of unwrapped inputs equals unwrap_euler of the
+complete record; its views are the body fit's selection (mvmc_body_observe on the tracker's joints, MAX_DIST, MIN_SCORE).  A missing row
+starts as a copy of the previous row's current values and has no data term.  A session whose frame index jumps by d gets d - 1 missing
+rows in every live identity.
+
+Per tick, for every live identity with two rows or more whose session delivered a frame: the last m = min(window, rows) rows are free,
+the up to two rows before them are frozen history, and ``n_iter`` Levenberg-Marquardt trials (smoothing.py's rules, mu from LM_MU0,
+warm from the rows' current values) minimise the free rows' data terms + every velocity / acceleration term whose stencil touches a
+free row.  A row that leaves the window keeps its value for good (final).  The row of frame f_new - lag is emitted.  A tracklet that
+leaves the session's table is finished: rows after its last data row are dropped and its record is handed over.
+
+The rows, their members, the row counts and the sessions' rings of the last ``window`` frames' ingested keypoints stay on the device
+between ticks.  A tick costs a number of launches that does not depend on sessions or identities (ingest, selection, exactly one
+mvmc_smooth_window, FK of the rows read back) and one synchronisation, the read-back.  NumPy restatement: tests/live_smooth_np.py.
+INTEGRATION.md section C.5.
+"""
+from __future__ import annotations
+
+import time
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from .body_fit import MAX_DIST, MIN_SCORE
+from .smoothing import ANG_ACC, ANG_VEL, LM_FTOL, LM_MU0, LM_XTOL, ROOT_ACC, ROOT_VEL, unwrap_euler_many
+from .tracker import T_WIDE
+
+WINDOW_MAX = 32     # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
+N_ITER_MAX = 8      # include/mvmc.h: MVMC_SMOOTH_WIN_INFO_DOUBLES - 8
+RING = 66           # include/mvmc.h: MVMC_SMOOTH_WIN_RING
+MAX_VIEWS = 64      # include/mvmc.h: MVMC_SMOOTH_MAX_VIEWS
+
+
+def check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc) -> np.ndarray:
+    """LiveSmoother's parameter checks (host only) -> the four prior weights."""
+    if int(window) != window or not 2 <= int(window) <= WINDOW_MAX:
+        raise ValueError(f"LiveSmoother: 2 <= window <= {WINDOW_MAX} required")
+    if int(lag) != lag or not 0 <= int(lag) < int(window):
+        raise ValueError("LiveSmoother: 0 <= lag < window required")
+    if int(n_iter) != n_iter or not 1 <= int(n_iter) <= N_ITER_MAX:
+        raise ValueError(f"LiveSmoother: 1 <= n_iter <= {N_ITER_MAX} required")
+    w = np.array([root_vel, root_acc, ang_vel, ang_acc], dtype=np.float64)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        raise ValueError("LiveSmoother: the prior weights must be finite and >= 0")
+    if not (w[0] + w[1] > 0 and w[2] + w[3] > 0):
+        raise ValueError("LiveSmoother: root_vel + root_acc > 0 and ang_vel + ang_acc > 0 required")
+    return w
+
+
+class TickOutput:
+    """One session's results of one tick.  ``emitted``: [(track_id, frame_idx, PoseShapeParam, Pose (FK joints), filled, views)] for
+    frame idx - lag, in the table's order; ``finished``: the records of the tracklets that died this tick; ``solved``: track_id ->
+    dict(cost [E_data, E_prior at the start, E_data, E_prior at the end], trials [1 accepted / 0 rejected], stop)."""
+
+    def __init__(self):
+        self.emitted: list = []
+        self.finished: list = []
+        self.solved: Dict[int, dict] = {}
+
+
+class _Ident:
+    def __init__(self, tid: int, slot: int, f0: int):
+        self.tid, self.slot, self.f0 = tid, slot, f0
+        self.hits, self.state = -1, 1
+        self.prev_in: Optional[np.ndarray] = None      # the unwrapped INPUT angles of the last data row (18,3)
+        self.filled: List[bool] = []
+        self.views: List[int] = []
+        self.sel: List[Optional[np.ndarray]] = []
+        self.params: List[Optional[np.ndarray]] = []   # a row's values once it is final (None before)
+        self.joints: List[Optional[np.ndarray]] = []
+        self.n_final = 0
+
+    @property
+    def n(self) -> int:
+        return len(self.filled)
+
+    def append(self, data: bool, C: int) -> None:
+        self.filled.append(not data)
+        self.views.append(0)
+        self.sel.append(-np.ones(C, np.int32))
+        self.params.append(None)
+        self.joints.append(None)
+
+    def last_data(self) -> int:
+        return max(i for i, f in enumerate(self.filled) if not f) + 1
+
+
+class _Session:
+    def __init__(self, key, s: int, calibs):
+        self.key, self.s, self.calibs = key, s, list(calibs)
+        self.f_last: Optional[int] = None
+        self.ids: Dict[int, _Ident] = {}
+
+
+class LiveSmoother:
+    """``capacity`` sessions of ``n_views`` cameras, up to tracker.T_WIDE live identities each."""
+
+    def __init__(self, n_views: int, capacity: int, p_max: int = 8, window: int = 24, lag: int = 8, n_iter: int = 2,
+                 root_vel: float = ROOT_VEL, root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC,
+                 device=None, skeleton=None):
+        self.w = check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc)
+        if int(capacity) < 1 or not 1 <= int(n_views) <= MAX_VIEWS or int(p_max) < 1:
+            raise ValueError(f"LiveSmoother: capacity >= 1, 1 <= n_views <= {MAX_VIEWS} and p_max >= 1 required")
+        self.C, self.P, self.capacity = int(n_views), int(p_max), int(capacity)
+        self.W, self.lag, self.n_iter = int(window), int(lag), int(n_iter)
+        self.device, self.skeleton = device, skeleton
+        self._sessions: Dict[object, _Session] = {}
+        self._free_s = list(range(self.capacity))
+        self._free_id = list(range(self.capacity * T_WIDE))
+        self._next_key = 0
+        self._Pm_h = np.zeros((self.capacity, self.C, 3, 4))
+        self._Pm_dirty = True
+        self._st = None        # the device state, allocated by the first tick
+        self._pool = None
+        self._stage = None
+        self.timings = dict(pack=0.0, launch=0.0, records=0.0)   # seconds by part of a tick, accumulated (the probe's split)
+
+    @classmethod
+    def for_pool(cls, pool, **kw) -> "LiveSmoother":
+        """A smoother that follows ``pool``'s sessions (their sids are its keys; a session is opened here on its first tick).  The
+        pool itself is not changed: call update_4d / update_4d_arrays after the pool's, with the same arguments."""
+        sm = cls(pool.C, pool.capacity, p_max=pool.P, device=pool.device, **kw)
+        sm._pool = pool
+        return sm
+
+    # -- sessions ----------------------------------------------------------------------------------------------------------------------
+    def open_session(self, calibs, key=None):
+        """A new session on the rig ``calibs`` (one Calib per camera); returns its key (host only: the rig is uploaded by the next tick)."""
+        if len(calibs) != self.C:
+            raise ValueError(f"open_session: {len(calibs)} cameras, the smoother's sessions have {self.C}")
+        if not self._free_s:
+            raise ValueError(f"open_session: all {self.capacity} session slots are taken")
+        if key is None:
+            while self._next_key in self._sessions:
+                self._next_key += 1
+            key = self._next_key
+        if key in self._sessions:
+            raise ValueError(f"open_session: session {key} is open")
+        P = np.array([np.asarray(c.P, np.float64).reshape(3, 4) for c in calibs])
+        s = self._free_s.pop(0)
+        self._Pm_h[s] = P
+        self._Pm_dirty = True
+        self._sessions[key] = _Session(key, s, calibs)
+        return key
+
+    def _session(self, key, what: str) -> _Session:
+        if key not in self._sessions:
+            raise ValueError(f"{what}: no open session {key}")
+        return self._sessions[key]
+
+    @property
+    def keys(self) -> list:
+        return list(self._sessions)
+
+    # -- device state ------------------------------------------------------------------------------------------------------------------
+    def _state(self):
+        import torch
+        if self._st is None:
+            if self.device is None:
+                from .motion_capture import _d
+                self.device = _d()
+            d = torch.device(self.device)
+            n_slots = self.capacity * T_WIDE
+            self._st = dict(
+                d=d, kps=torch.zeros((self.capacity * self.W, self.C, self.P, 17, 3), dtype=torch.float64, device=d),
+                cnt=torch.zeros((self.capacity * self.W, self.C), dtype=torch.int32, device=d),
+                rows=torch.zeros((n_slots, RING, 68), dtype=torch.float64, device=d),
+                members=torch.full((n_slots, RING, self.C), -1, dtype=torch.int32, device=d),
+                count=torch.zeros((n_slots, 2), dtype=torch.int32, device=d), Pm=None)
+        if self._Pm_dirty:
+            self._st["Pm"] = torch.from_numpy(self._Pm_h.copy()).to(self._st["d"])
+            self._Pm_dirty = False
+        return self._st
+
+    def _fetch(self, wanted):
+        """[(ident, row)] -> params (n,68), joints (n,18,3) of those rows as they stand on the device (one read-back)."""
+        import torch
+
+        from . import device as dev
+        if not wanted:
+            return np.zeros((0, 68)), np.zeros((0, 18, 3))
+        st = self._state()
+        idx = torch.as_tensor([i.slot * RING + r % RING for i, r in wanted], dtype=torch.int64).to(st["d"])
+        P = st["rows"].view(-1, 68).index_select(0, idx)
+        J = dev.fk(P, self.skeleton)
+        return P.cpu().numpy(), J.cpu().numpy()
+
+    # -- ticks -------------------------------------------------------------------------------------------------------------------------
+    def _check_table(self, key, f, inputs, meta, params, joints):
+        sess = self._sessions[key]
+        if int(f) != f:
+            raise ValueError(f"session {key}: the frame index must be an integer")
+        if sess.f_last is not None:
+            if f <= sess.f_last:
+                raise ValueError(f"session {key}: frame index {f} does not increase (the last was {sess.f_last})")
+            if f - sess.f_last - 1 >= self.W:
+                raise ValueError(f"session {key}: frame index jumps from {sess.f_last} to {f}, a window ({self.W}) or more")
+        try:
+            kps, cnt = inputs
+        except (TypeError, ValueError):
+            raise ValueError(f"session {key}: frame_inputs must be (kps (C,P,25|17,3), counts (C,))") from None
+        kps, cnt = np.asarray(kps), np.asarray(cnt)
+        if kps.ndim != 4 or kps.shape[0] != self.C or kps.shape[2] not in (17, 25) or kps.shape[3] != 3 or kps.shape[1] > self.P:
+            raise ValueError(f"session {key}: kps {kps.shape}, expected ({self.C}, P <= {self.P}, 25|17, 3)")
+        if cnt.shape != (self.C,) or np.any(cnt < 0) or np.any(cnt > kps.shape[1]):
+            raise ValueError(f"session {key}: counts must be ({self.C},) with 0 <= counts <= {kps.shape[1]}")
+        meta, params, joints = np.asarray(meta), np.asarray(params, np.float64), np.asarray(joints, np.float64)
+        n = meta.shape[0] if meta.ndim == 2 else -1
+        if meta.ndim != 2 or meta.shape[1] != 4 or params.shape != (n, 68) or joints.shape != (n, 18, 3):
+            raise ValueError(f"session {key}: the table must be meta (n,4), params (n,68), joints (n,18,3)")
+        if n > T_WIDE:
+            raise ValueError(f"session {key}: {n} live identities, at most {T_WIDE}")
+        if len(set(int(t) for t in meta[:, 0])) != n:
+            raise ValueError(f"session {key}: a track_id appears twice in the table")
+        if not (np.all(np.isfinite(params)) and np.all(np.isfinite(joints))):
+            raise ValueError(f"session {key}: parameters and joints must be finite")
+        return kps, cnt.astype(np.int32), meta.astype(np.int64), params, joints
+
+    def update_tables(self, tables: Dict[object, tuple], failed=()) -> Dict[object, TickOutput]:
+        """One tick: tables[key] = (frm_idx, (kps (C,P,25|17,3), counts (C,)), meta (n,4), params (n,68), joints (n,18,3)) -- the frame's
+        2-D poses and the rows commit_tables takes -- for every session that delivered a frame.  A key in ``failed`` is not stepped."""
+        t_start = time.perf_counter()
+        for key in tables:
+            self._session(key, "update_tables")
+        work = []
+        for key, row in tables.items():
+            if key in failed:
+                continue
+            try:
+                f, inputs, meta, params, joints = row
+            except (TypeError, ValueError):
+                raise ValueError(f"session {key}: expected (frm_idx, frame_inputs, meta, params, joints)") from None
+            work.append((key, int(f)) + self._check_table(key, f, inputs, meta, params, joints))
+        out = {key: TickOutput() for key, *_ in work}
+        if not work:
+            return out
+        if len({w[2].shape[2] for w in work}) != 1:
+            raise ValueError("update_tables: the sessions of one tick must all deliver 25-row or all 17-row poses")
+        import torch
+
+        from . import device as dev
+        st = self._state()
+        d, C, W = st["d"], self.C, self.W
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+        # ---- host: the tick's rows, items and selection problems ----
+        J = work[0][2].shape[2]
+        kst = np.zeros((len(work), C, self.P, J, 3))
+        cst = np.zeros((len(work), C), np.int32)
+        ring_at = np.zeros(len(work), np.int64)
+        items, newp, prob, fin, solved_of = [], [], [], [], []
+        for i, (key, f, kps, cnt, meta, params, joints) in enumerate(work):
+            sess = self._sessions[key]
+            dd = 1 if sess.f_last is None else f - sess.f_last
+            kst[i, :, :kps.shape[1]] = kps
+            cst[i] = cnt
+            ring_at[i] = sess.s * W + f % W
+            tids = [int(t) for t in meta[:, 0]]
+            for tid in [t for t in sess.ids if t not in tids]:
+                fin.append((key, sess.ids.pop(tid)))
+            for k, tid in enumerate(tids):
+                idn = sess.ids.get(tid)
+                new = idn is None
+                if new:
+                    idn = sess.ids[tid] = _Ident(tid, self._free_id.pop(0), f)
+                data = new or int(meta[k, 2]) > idn.hits
+                for _ in range(0 if new else dd - 1):
+                    idn.append(False, C)
+                idn.append(data, C)
+                idn.hits, idn.state = int(meta[k, 2]), int(meta[k, 1])
+                if data:
+                    newp.append((idn, params[k].copy()))
+                    prob.append((int(ring_at[i]), sess.s, joints[k], k))
+                items.append([idn.slot, sess.s, dd, int(data), int(new), len(newp) - 1 if data else -1, f, len(items) * W])
+                solved_of.append((key, idn, f))
+            sess.f_last = f
+        pairs = [(idn, p) for idn, p in newp if idn.prev_in is not None]
+        un = unwrap_euler_many([np.stack([idn.prev_in, p[3:57].reshape(18, 3)]) for idn, p in pairs])
+        for (idn, p), u in zip(pairs, un):
+            p[3:57] = u[1].ravel()
+        for idn, p in newp:
+            idn.prev_in = p[3:57].reshape(18, 3).copy()
+        # rows wanted back: the finished identities' rows that are not final yet (gathered before the launch, their slots are free
+        # for the tick's new identities), then per item the rows that leave the window and the emitted row
+        want_fin = []
+        for key, idn in fin:
+            keep = idn.last_data()
+            want_fin += [(idn, r) for r in range(idn.n_final, keep)]
+            self._free_id.append(idn.slot)
+        self._free_id.sort()
+        want = []
+        was_final = [idn.n_final for _, idn, _ in solved_of]
+        for key, idn, f in solved_of:
+            nf = idn.n - min(W, idn.n)
+            want += [(idn, r) for r in range(idn.n_final, nf)]
+            idn.n_final = nf
+            if f - self.lag - idn.f0 >= 0:
+                want.append((idn, f - self.lag - idn.f0))
+        t_pack = time.perf_counter()
+        # ---- device: ingest into the sessions' rings, selection, ONE window launch, the rows wanted back ----
+        k17, c17 = dev.ingest(T(kst), T(cst))
+        at_d = T(ring_at)
+        st["kps"].index_copy_(0, at_d, k17)
+        st["cnt"].index_copy_(0, at_d, c17)
+        slot_idx = lambda wl: T(np.array([i.slot * RING + r % RING for i, r in wl], np.int64))
+        P_fin = st["rows"].view(-1, 68).index_select(0, slot_idx(want_fin)) if want_fin else None
+        B = len(newp)
+        if B:
+            frame_of = np.array([p[0] for p in prob], np.int32)
+            order = np.argsort(frame_of, kind="stable").astype(np.int32)
+            fs = frame_of[order]
+            mem_d, nv_d, _, _ = dev.body_observe(st["kps"], st["cnt"], st["Pm"], T(frame_of), T(np.array([p[1] for p in prob], np.int32)),
+                                                 T(np.array([p[2] for p in prob])), T(order),
+                                                 T(np.searchsorted(fs, frame_of, side="left").astype(np.int32)),
+                                                 T(np.searchsorted(fs, frame_of, side="right").astype(np.int32)),
+                                                 T(np.array([p[3] for p in prob], np.int32)), MAX_DIST, MIN_SCORE)
+            newp_d = T(np.array([p for _, p in newp]))
+        else:
+            mem_d = torch.zeros((0, C), dtype=torch.int32, device=d)
+            nv_d = torch.zeros((0,), dtype=torch.int32, device=d)
+            newp_d = torch.zeros((0, 68), dtype=torch.float64, device=d)
+        parts = []
+        if items:
+            info = dev.smooth_window(st["kps"], st["Pm"], T(np.array(items, np.int32)), newp_d, mem_d, st["rows"], st["members"],
+                                     st["count"], W, self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton)
+            parts.append(info.reshape(-1))
+        Pg = [p for p in (P_fin, st["rows"].view(-1, 68).index_select(0, slot_idx(want)) if want else None) if p is not None]
+        n_rows = len(want_fin) + len(want)
+        if n_rows:
+            Pall = torch.cat(Pg) if len(Pg) > 1 else Pg[0]
+            parts += [Pall.reshape(-1), dev.fk(Pall, self.skeleton).reshape(-1)]
+        parts += [mem_d.to(torch.float64).reshape(-1), nv_d.to(torch.float64).reshape(-1)]
+        host = torch.cat(parts).cpu().numpy()      # the tick's one synchronisation
+        t_launch = time.perf_counter()
+        # ---- host: the records ----
+        at = 0
+
+        def take(n, shape):
+            nonlocal at
+            a = host[at:at + n].reshape(shape)
+            at += n
+            return a
+        inf_h = take(len(items) * 16, (len(items), 16))
+        P_h = take(n_rows * 68, (n_rows, 68))
+        J_h = take(n_rows * 54, (n_rows, 18, 3))
+        mem_h = take(B * C, (B, C)).astype(np.int64)
+        nv_h = take(B, (B,)).astype(np.int64)
+        for b, (idn, _) in enumerate(newp):
+            idn.views[-1] = int(nv_h[b])
+            idn.sel[-1] = np.where(mem_h[b] >= 0, mem_h[b] % self.P, -1).astype(np.int32)
+        got = {}
+        for k, (idn, r) in enumerate(want_fin + want):
+            got[(id(idn), r)] = k
+        for key, idn in fin:
+            keep = idn.last_data()
+            for r in range(idn.n_final, keep):
+                k = got[(id(idn), r)]
+                idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
+            idn.n_final = keep
+            out[key].finished.append(self._record(idn, keep, 3))
+        for a, (key, idn, f) in enumerate(solved_of):
+            for r in range(was_final[a], idn.n_final):
+                k = got[(id(idn), r)]
+                idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
+            if idn.n >= 2:
+                n_t = int(inf_h[a, 4])
+                if int(inf_h[a, 7]) == 6:
+                    raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed item")
+                out[key].solved[idn.tid] = dict(cost=inf_h[a, :4].copy(), trials=[int(v) for v in inf_h[a, 8:8 + n_t]], stop=int(inf_h[a, 7]))
+            r = f - self.lag - idn.f0
+            if r >= 0:
+                k = got[(id(idn), r)]
+                out[key].emitted.append((idn.tid, f - self.lag) + self._pose(P_h[k], J_h[k]) + (bool(idn.filled[r]), int(idn.views[r])))
+        t_end = time.perf_counter()
+        self.timings["pack"] += t_pack - t_start
+        self.timings["launch"] += t_launch - t_pack
+        self.timings["records"] += t_end - t_launch
+        return out
+
+    # -- the pool route ----------------------------------------------------------------------------------------------------------------
+    def _pool_table(self, sid, fi):
+        """A session's table of frame fi from the pool's public records after its tick."""
+        s = self._pool.session(sid)
+        if sid not in self._sessions:
+            self.open_session(s.calibs, key=sid)
+        trs = list(s.tracklets)
+        meta = np.zeros((len(trs), 4), np.int64)
+        params = np.zeros((len(trs), 68))
+        joints = np.zeros((len(trs), 18, 3))
+        for k, t in enumerate(trs):
+            meta[k] = (t.track_id, int(getattr(t.state, "value", t.state)), t.hits, len(t))
+            q = t.poses[-1]
+            params[k] = np.concatenate([np.ravel(q[1].root), np.ravel(q[1].euler_angles), np.ravel(q[1].bone_lens)])
+            joints[k] = q[2].keypoints
+            if t.frame_idxs[-1] != fi and sid in self._sessions and t.track_id not in self._sessions[sid].ids:
+                raise ValueError(f"session {sid}: tracklet {t.track_id} is unknown and has no pose at frame {fi}: call update_4d after "
+                                 "every tick of the pool")
+        return meta, params, joints
+
+    def update_4d(self, frames: Dict[int, tuple], failed=()) -> Dict[int, TickOutput]:
+        """After pool.update_4d(frames), the same argument (failed = LiveSessionError.errors when the pool raised one)."""
+        from .motion_capture import pack_frame
+        if self._pool is None:
+            raise ValueError("update_4d: this smoother follows no pool (LiveSmoother.for_pool)")
+        tables = {}
+        for sid, (fi, fr) in frames.items():
+            if sid in failed:
+                continue
+            if len(fr) != self.C:
+                raise ValueError(f"update_4d: session {sid}'s frame has {len(fr)} views, the smoother's sessions have {self.C}")
+            kps = np.zeros((1, self.C, self.P, 17, 3))
+            cnt = np.zeros((1, self.C), np.int32)
+            pack_frame(kps, cnt, 0, fr, self.P)
+            tables[sid] = (fi, (kps[0], cnt[0])) + self._pool_table(sid, fi)
+        return self.update_tables(tables)
+
+    def update_4d_arrays(self, sids: Sequence[int], frm_idxs: Sequence[int], kps25, counts, failed=()) -> Dict[int, TickOutput]:
+        """After pool.update_4d_arrays(sids, frm_idxs, kps25, counts), the same arguments."""
+        if self._pool is None:
+            raise ValueError("update_4d_arrays: this smoother follows no pool (LiveSmoother.for_pool)")
+        k = kps25.cpu().numpy() if hasattr(kps25, "cpu") else np.asarray(kps25)
+        c = counts.cpu().numpy() if hasattr(counts, "cpu") else np.asarray(counts)
+        if len(frm_idxs) != len(sids) or k.shape[0] != len(sids) or c.shape[0] != len(sids):
+            raise ValueError(f"update_4d_arrays: {len(sids)} sessions, {len(frm_idxs)} frame indices, kps25 {k.shape}, counts {c.shape}")
+        tables = {}
+        for i, sid in enumerate(sids):
+            if sid in failed:
+                continue
+            tables[int(sid)] = (int(frm_idxs[i]), (k[i], c[i])) + self._pool_table(int(sid), int(frm_idxs[i]))
+        return self.update_tables(tables)
+
+    # -- records -----------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _pose(p, j):
+        from .inverse_kinematics import PoseShapeParam
+        from .pose_def import KpsFormat, Pose
+        return (PoseShapeParam(p[:3].copy(), p[3:57].reshape(18, 3).copy(), p[57:].copy()),
+                Pose(KpsFormat.BASIC_18, np.array(j, np.float64).reshape(18, 3).copy(), np.ones((18, 1)), None))
+
+    def _record(self, idn: _Ident, n: int, state: Optional[int] = None, live=None):
+        """The identity's rows 0..n-1 as an MvTracklet-like record (save_bvh takes it); ``live``: values of the rows not final yet."""
+        from .motion_capture import MvTracklet, TrackState
+        poses = []
+        for r in range(n):
+            p, j = (idn.params[r], idn.joints[r]) if idn.params[r] is not None else live[r]
+            poses.append((idn.f0 + r,) + self._pose(p, j))
+        t = MvTracklet(idn.tid, poses[0][0], poses[0][1], poses[0][2])
+        t.frame_idxs = [q[0] for q in poses]
+        t.poses = poses
+        t.state = TrackState(idn.state if state is None else state)
+        t.hits = idn.hits
+        t.time_since_update = idn.n - idn.last_data()
+        t.smooth_filled = np.array(idn.filled[:n], bool)
+        t.smooth_views = np.array(idn.views[:n], np.int32)
+        t.smooth_select = np.array(idn.sel[:n], np.int32).reshape(n, self.C)
+        t.smooth_final = np.arange(n) < idn.n_final
+        return t
+
+    def tracklets(self, key) -> list:
+        """The session's live identities as records f0..newest without holes: poses, smooth_filled, smooth_views, smooth_select,
+        smooth_final (the row has left the window).  Reads the rows that are not final back from the device."""
+        sess = self._session(key, "tracklets")
+        want = [(idn, r) for idn in sess.ids.values() for r in range(idn.n_final, idn.n)]
+        P, J = self._fetch(want)
+        live = {}
+        for k, (idn, r) in enumerate(want):
+            live.setdefault(id(idn), {})[r] = (P[k], J[k])
+        return [self._record(idn, idn.n, live=live.get(id(idn))) for idn in sess.ids.values()]
+
+    def close_session(self, key) -> list:
+        """Ends a session: every live identity is finished (rows after its last data row dropped) and its record returned."""
+        sess = self._session(key, "close_session")
+        want = [(idn, r) for idn in sess.ids.values() for r in range(idn.n_final, idn.last_data())]
+        P, J = self._fetch(want)
+        for k, (idn, r) in enumerate(want):
+            idn.params[r], idn.joints[r] = P[k].copy(), J[k].copy()
+        done = []
+        for idn in sess.ids.values():
+            idn.n_final = idn.last_data()
+            done.append(self._record(idn, idn.n_final, 3))
+            self._free_id.append(idn.slot)
+        self._free_id.sort()
+        del self._sessions[key]
+        self._free_s.append(sess.s)
+        self._free_s.sort()
+        return done
