@@ -568,6 +568,32 @@ int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* kps17, int n
                        double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
                        double* work, long long work_doubles, mvmcStream_t stream);
 
+/* ---- re-linking of the records of one person (multiview_motion_capture_amd/relinking.py).  No counterpart in the reference.  Per
+ * sequence, its records in (first frame, track id) order are the nodes; record a may be followed by record b when 1 <= gap =
+ * first(b) - last(a) <= max_gap, at the cost mean_k |last_joints(a)[k] + v gap - first_joints(b)[k]| (metres; v = the mean of a's end
+ * velocity and b's start velocity, of the one that is defined, or zero), allowed when cost <= min(max_dist, near_dist + speed gap).
+ * The links taken minimise sum cost + max_dist x (records without a successor): an optimal assignment (Kuhn-Munkres with potentials,
+ * rows in record order, the first minimum wins) on the n x 2n matrix of the allowed costs and one dummy column per row.  ONE launch,
+ * one 256-lane workgroup per sequence; at most MVMC_RELINK_MAX_RECORDS records per sequence.
+ *   rec (N, MVMC_RELINK_REC_DOUBLES) f64 per record: the joints (18,3) of its last pose, of its first pose, then four joint centroids:
+ *     of the last pose, of the pose k = min(4, poses - 1) before it, of the first pose, of the pose k after it
+ *   frames (N,4) i32 per record: first frame, last frame, the frames between the two end centroids, between the two start centroids
+ *     (0: the record has one pose and no velocity)
+ *   seq (S,4) i32 per sequence: its first record, its records, the offset of its part of work (in 8-byte words), 0
+ *   succ (N) i32 out: the record that follows (position within the sequence) or -1; head (N) i32 out: the first record of its chain;
+ *   pos (N) i32 out: its position in the chain; link_cost (N) f64 out: the cost of the link to succ (0 without one)
+ *   status (S) i32 out: 0 ok, 1 the assignment hit its loop bound (the sequence's outputs are not written), 2 the sequence's row of seq
+ *     does not fit n_records / the capacity / work (nothing is read or written for it)
+ *   work: a sequence of more than 64 records keeps its n x n costs there: mvmc_relink_work_words(n) 8-byte words each (-1: n outside
+ *     the capacity), work_words in all; may be NULL when no sequence needs any.
+ * Argument errors return before any HIP call; nothing is allocated, freed or synchronised inside. ---- */
+#define MVMC_RELINK_MAX_RECORDS 512
+#define MVMC_RELINK_REC_DOUBLES 120
+long long mvmc_relink_work_words(int n_records);
+int mvmc_relink(const double* rec, const int32_t* frames, const int32_t* seq, int n_records, int n_seqs, int max_gap, double max_dist,
+                double near_dist, double speed, int32_t* succ, int32_t* head, int32_t* pos, double* link_cost, int32_t* status,
+                double* work, long long work_words, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ BOUND_WORDS, ROW_WORDS = 56, 128
 BODY_INFO_DOUBLES, BODY_WORK_DOUBLES = 16, 270
 SMOOTH_K, SMOOTH_BLOCK_DOUBLES, SMOOTH_WORK_DOUBLES, SMOOTH_INFO_DOUBLES, SMOOTH_MAX_VIEWS = 39, 820, 3940, 32, 64
 SMOOTH_WIN_MAX, SMOOTH_WIN_RING, SMOOTH_WIN_ITEM_INTS, SMOOTH_WIN_INFO_DOUBLES = 32, 66, 8, 16
+RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
 
 # every symbol declared in include/mvmc.h
 SYMBOLS = (
@@ -33,7 +34,7 @@ SYMBOLS = (
     "mvmc_fmats_from_projections", "mvmc_st_affinity", "mvmc_track_assign", "mvmc_track_commit", "mvmc_debug_eigh",
     "mvmc_debug_trstep", "mvmc_ik_solve_stages", "mvmc_chain_run", "mvmc_svt_associate", "mvmc_debug_ik_solve_fd", "mvmc_debug_ik_model_step", "mvmc_ingest_dlt", "mvmc_ingest_dlt_f32", "mvmc_pack_message_words", "mvmc_pack_work_words", "mvmc_stitch_work_words", "mvmc_pack_tracks", "mvmc_stitch_chains",
     "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
-    "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window",
+    "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
 )
 
 
@@ -143,9 +144,11 @@ def load():
         "mvmc_smooth_window_work_doubles": [i32, i32],
         "mvmc_smooth_window": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, f64, f64, f64, f64, f64, f64,
                                f64, vp, vp, C.c_longlong, vp],
+        "mvmc_relink_work_words": [i32],
+        "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
-                "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong}
+                "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong}
     # A build of another revision loaded through MVMC_LIB_PATH for a same-box A/B comparison (tools/lib_diff.py, tools/*_ab.sh) may
     # lack entry points that were added since WITHIN the same ABI version (checked above); only then is a missing symbol skipped -- the
     # shipped library must export every one.

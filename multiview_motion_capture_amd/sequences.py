@@ -179,7 +179,7 @@ def tables_to_tracklets(meta: np.ndarray, n_tracks: np.ndarray, params: np.ndarr
 
 def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_max: Optional[int] = None,
                     max_dist: float = parallel.MAX_DIST, frame_idx0: int = 0, device="cuda:0", timings: Optional[dict] = None,
-                    tables: Optional[list] = None):
+                    tables: Optional[list] = None, relink: bool = False):
     """Track every sequence -- (kps25 (F_s,C,P_s,25,3), counts (F_s,C), calibs: one Calib per camera), what
     motion_capture.load_openpose_sequence returns -- and return, per sequence, its MvTracklet records (longest first).
 
@@ -189,7 +189,9 @@ def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_m
     frame_idx0: the frm_idx of every sequence's first frame in the records.
     timings: a dict that receives the seconds spent in {"kernel", "repair_stitch", "convert"} (synchronising between the parts).
     tables: a list that receives, per sequence, its stitched tables as host arrays (padded frames included): dict(params, joints,
-    meta, n_tracks, gid (its chains, parallel.ID_CAP), match, n_frames)."""
+    meta, n_tracks, gid (its chains, parallel.ID_CAP), match, n_frames).
+    relink: join the records of one person per sequence afterwards (relinking.relink_sequences with its defaults, max_dist as here;
+    the tables stay the tracker's own).  Off by default: the records are then the stitch's, as before."""
     import time
 
     import torch
@@ -248,6 +250,11 @@ def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_m
             if tables is not None:
                 per_seq[i] = dict({k: v[f0:f1] for k, v in host.items()}, gid=gid, match=st["match"].cpu().numpy(), n_frames=lay.n_frames[r])
         lap("convert", t0)
+    if relink:
+        from .relinking import relink_sequences
+        t0 = time.perf_counter()
+        result = relink_sequences(result, max_dist=max_dist, device=device)
+        tm["relink"] = time.perf_counter() - t0
     if timings is not None:
         timings.update(tm)
     if tables is not None:
