@@ -594,6 +594,51 @@ int mvmc_relink(const double* rec, const int32_t* frames, const int32_t* seq, in
                 double near_dist, double speed, int32_t* succ, int32_t* head, int32_t* pos, double* link_cost, int32_t* status,
                 double* work, long long work_words, mvmcStream_t stream);
 
+/* ---- refinement of every sequence's camera rig from its tracked people (multiview_motion_capture_amd/rig_refine.py; restated in
+ * tests/rig_refine_np.py).  No counterpart in the reference.  A bundle adjustment: the unknowns are the points (one per record frame
+ * and keypoint) and, per free camera, a rotation increment (R <- exp([w]x) R) and a translation increment; the residual is the plain
+ * pixel reprojection K (R X + t), E = 1/2 sum r^2; Levenberg-Marquardt ((A + mu diag A) d = -g, mu / 10 accepted, x 10 rejected) with
+ * the points eliminated by a Schur complement.  Sequences of one camera count share every launch; every sum has a fixed order (tiles
+ * of MVMC_RIG_TILE points cut from the sequence's own points, tile parts added in tile order), no atomics.
+ *   X, X_trial (N,3) f64; uv (N,C,2) f64, NaN = the camera does not observe the point
+ *   tile (T,4) i32: sequence, first point, points (<= MVMC_RIG_TILE), 0;  seq (S,4) i32: first tile, tiles, first point, points
+ *   slot (S,C) i32: the camera's position in the reduced system (0 .. n_free - 1, ascending with the camera) or -1 = held
+ *   cams, cams_trial (S,C,MVMC_RIG_CAM_DOUBLES) f64: K (9), R (9), t (3), row-major
+ *   ctl (S,4) i32 in/out: stop (0 = running, MVMC_RIG_STOP_*), trials made, trials accepted, 1 = the current reduced matrix is not
+ *     positive definite.  A sequence whose stop is not 0 idles
+ *   info (S,MVMC_RIG_INFO_DOUBLES) f64: E at the start, E now, mu, |c_ref - c_0| of the input, the camera part of d.g, of d^T diag(A) d,
+ *     of |d|_inf, the last predicted reduction; [8, 8 + MAX_ITER) per trial 1 accepted / 0 rejected; [8 + MAX_ITER, ..) E at the start
+ *     and after every trial
+ *   part (T, mvmc_rig_part_doubles(C)) and part2 (T,4) f64 workspaces; red (S, mvmc_rig_red_doubles(C)) f64 out: the reduced matrix
+ *     (M x M, M = 6 (C - 1), identity on unused slots), the reduced gradient (M), the camera step (M)
+ * One trial = mvmc_rig_accumulate (tile parts at the current state and mu, on the matrix cores with variant = 1 or as FMAs with
+ * variant = 0; then per sequence the sum, the Cholesky solve and the trial cameras) followed by mvmc_rig_step (the points' steps and
+ * the trial cost per tile; then per sequence accept / reject, the gauge rescale about camera 0's centre that keeps |c_ref - c_0|, and
+ * the stop rules).  Nothing is read back, allocated or synchronised inside.
+ * mvmc_rig_start: per candidate point the DLT of mvmc_dlt over the views with score > min_score, with the point's own rig:
+ *   obs (N,C,3) f64 u, v, score; rig_of (N) i32; Pmats (R,C,3,4) -> X0 (N,4) x, y, z, mean score; dist (N,C) reprojection distance
+ *   (px) in the views used, NaN elsewhere. ---- */
+#define MVMC_RIG_TILE 64
+#define MVMC_RIG_MAX_CAMS 8
+#define MVMC_RIG_MAX_ITER 24
+#define MVMC_RIG_CAM_DOUBLES 21
+#define MVMC_RIG_INFO_DOUBLES 64
+#define MVMC_RIG_STOP_XTOL 1
+#define MVMC_RIG_STOP_FTOL 2
+#define MVMC_RIG_STOP_FEW_CAMERAS 3
+#define MVMC_RIG_STOP_FEW_POINTS 4
+#define MVMC_RIG_STOP_MAX_ITER 5
+long long mvmc_rig_part_doubles(int n_views);   /* -1: n_views outside 2 .. MVMC_RIG_MAX_CAMS */
+long long mvmc_rig_red_doubles(int n_views);
+int mvmc_rig_start(const double* obs, const int32_t* rig_of, const double* Pmats, int n_points, int n_views, int n_rigs,
+                   double min_score, double* X0, double* dist, mvmcStream_t stream);
+int mvmc_rig_accumulate(const double* X, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                        const double* cams, double* cams_trial, int32_t* ctl, double* info, int n_points, int n_tiles, int n_seqs,
+                        int n_views, int max_iter, double mu0, int variant, double* part, double* red, mvmcStream_t stream);
+int mvmc_rig_step(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                  double* cams, const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points, int n_tiles,
+                  int n_seqs, int n_views, int max_iter, double ftol, double xtol, double* part2, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

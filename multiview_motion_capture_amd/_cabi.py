@@ -26,6 +26,8 @@ BODY_INFO_DOUBLES, BODY_WORK_DOUBLES = 16, 270
 SMOOTH_K, SMOOTH_BLOCK_DOUBLES, SMOOTH_WORK_DOUBLES, SMOOTH_INFO_DOUBLES, SMOOTH_MAX_VIEWS = 39, 820, 3940, 32, 64
 SMOOTH_WIN_MAX, SMOOTH_WIN_RING, SMOOTH_WIN_ITEM_INTS, SMOOTH_WIN_INFO_DOUBLES = 32, 66, 8, 16
 RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
+RIG_TILE, RIG_MAX_CAMS, RIG_MAX_ITER, RIG_CAM_DOUBLES, RIG_INFO_DOUBLES = 64, 8, 24, 21, 64
+RIG_STOP = {0: "running", 1: "xtol", 2: "ftol", 3: "few_cameras", 4: "few_points", 5: "max_iter"}    # MVMC_RIG_STOP_*
 
 # every symbol declared in include/mvmc.h
 SYMBOLS = (
@@ -35,6 +37,7 @@ SYMBOLS = (
     "mvmc_debug_trstep", "mvmc_ik_solve_stages", "mvmc_chain_run", "mvmc_svt_associate", "mvmc_debug_ik_solve_fd", "mvmc_debug_ik_model_step", "mvmc_ingest_dlt", "mvmc_ingest_dlt_f32", "mvmc_pack_message_words", "mvmc_pack_work_words", "mvmc_stitch_work_words", "mvmc_pack_tracks", "mvmc_stitch_chains",
     "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
+    "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
 )
 
 
@@ -146,9 +149,15 @@ def load():
                                f64, vp, vp, C.c_longlong, vp],
         "mvmc_relink_work_words": [i32],
         "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
+        "mvmc_rig_part_doubles": [i32],
+        "mvmc_rig_red_doubles": [i32],
+        "mvmc_rig_start": [vp, vp, vp, i32, i32, i32, f64, vp, vp, vp],
+        "mvmc_rig_accumulate": [vp] * 9 + [i32] * 5 + [f64, i32, vp, vp, vp],
+        "mvmc_rig_step": [vp] * 11 + [i32] * 5 + [f64, f64, vp, vp],
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
-                "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong}
+                "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong,
+                "mvmc_rig_part_doubles": C.c_longlong, "mvmc_rig_red_doubles": C.c_longlong}
     # A build of another revision loaded through MVMC_LIB_PATH for a same-box A/B comparison (tools/lib_diff.py, tools/*_ab.sh) may
     # lack entry points that were added since WITHIN the same ABI version (checked above); only then is a missing symbol skipped -- the
     # shipped library must export every one.

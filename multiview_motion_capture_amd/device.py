@@ -611,3 +611,71 @@ def track_commit(status, n_new, ik_params, ik_joints, track_params, track_joints
     check(_cabi.load().mvmc_track_commit(_p(status), _p(n_new), _p(ik_params), _p(ik_joints), B, T, k_max, n_inits,
                                          _p(track_params), _p(track_joints), _p(meta), _p(n_tracks), _p(next_id),
                                          _p(n_dead), _p(slot_src), _p(overflow), _stream()), "mvmc_track_commit")
+
+
+def rig_start(obs: torch.Tensor, rig_of: torch.Tensor, Pmats: torch.Tensor, min_score=0.1):
+    """Start values of the rig refinement (include/mvmc.h: mvmc_rig_start).  obs (N,C,3) f64 u, v, score per candidate point and
+    camera; rig_of (N,) i32; Pmats (R,C,3,4) -> X0 (N,4) the DLT of the views with score > min_score, dist (N,C) px (NaN: not used)."""
+    N, Cn = obs.shape[:2]
+    _req(obs, torch.float64, "obs", (N, Cn, 3))
+    _req(rig_of, torch.int32, "rig_of", (N,))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    X0 = torch.empty((N, 4), dtype=torch.float64, device=obs.device)
+    dist = torch.empty((N, Cn), dtype=torch.float64, device=obs.device)
+    check(_cabi.load().mvmc_rig_start(_p(obs), _p(rig_of), _p(Pmats), N, Cn, int(Pmats.shape[0]), float(min_score), _p(X0), _p(dist),
+                                      _stream()), "mvmc_rig_start")
+    return X0, dist
+
+
+def rig_work(n_tiles: int, n_seqs: int, n_views: int, dev):
+    """(part (T, mvmc_rig_part_doubles), part2 (T,4), red (S, mvmc_rig_red_doubles)) of mvmc_rig_accumulate / mvmc_rig_step."""
+    lib = _cabi.load()
+    pd, rd = int(lib.mvmc_rig_part_doubles(int(n_views))), int(lib.mvmc_rig_red_doubles(int(n_views)))
+    if pd < 0 or rd < 0:
+        raise ValueError(f"rig_work: {n_views} cameras outside 2 .. {_cabi.RIG_MAX_CAMS}")
+    return (torch.empty((max(n_tiles, 1), pd), dtype=torch.float64, device=dev),
+            torch.empty((max(n_tiles, 1), 4), dtype=torch.float64, device=dev), torch.zeros((n_seqs, rd), dtype=torch.float64, device=dev))
+
+
+def _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red):
+    N, S, Cn = X.shape[0], seq.shape[0], slot.shape[1]
+    _req(X, torch.float64, "X", (N, 3))
+    _req(uv, torch.float64, "uv", (N, Cn, 2))
+    _req(tile, torch.int32, "tile", (None, 4))
+    _req(seq, torch.int32, "seq", (S, 4))
+    _req(slot, torch.int32, "slot", (S, Cn))
+    _req(cams, torch.float64, "cams", (S, Cn, _cabi.RIG_CAM_DOUBLES))
+    _req(cams_trial, torch.float64, "cams_trial", (S, Cn, _cabi.RIG_CAM_DOUBLES))
+    _req(ctl, torch.int32, "ctl", (S, 4))
+    _req(info, torch.float64, "info", (S, _cabi.RIG_INFO_DOUBLES))
+    _req(red, torch.float64, "red", (S, int(_cabi.load().mvmc_rig_red_doubles(Cn))))
+    return N, int(tile.shape[0]), S, Cn
+
+
+def rig_accumulate(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor, cams: torch.Tensor,
+                   cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, max_iter: int, mu0: float, part: torch.Tensor,
+                   red: torch.Tensor, variant: int = 1) -> None:
+    """First half of a trial of the rig refinement (include/mvmc.h: mvmc_rig_accumulate): the reduced camera system of every running
+    sequence at (X, cams) and its mu into red, its solution and the trial cameras.  variant 1: matrix cores, 0: FMAs."""
+    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
+    _req(part, torch.float64, "part", (None, int(_cabi.load().mvmc_rig_part_doubles(Cn))))
+    if part.shape[0] < T:
+        raise ValueError(f"part: {part.shape[0]} rows for {T} tiles")
+    check(_cabi.load().mvmc_rig_accumulate(_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info), N, T,
+                                           S, Cn, int(max_iter), float(mu0), int(variant), _p(part), _p(red), _stream()),
+          "mvmc_rig_accumulate")
+
+
+def rig_step(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
+             cams: torch.Tensor, cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, red: torch.Tensor, max_iter: int,
+             ftol: float, xtol: float, part2: torch.Tensor) -> None:
+    """Second half of a trial (include/mvmc.h: mvmc_rig_step): the points' steps, the trial cost, accept / reject with the gauge
+    rescale, the stop rules.  X, cams, ctl and info are updated in place."""
+    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
+    _req(X_trial, torch.float64, "X_trial", (N, 3))
+    _req(part2, torch.float64, "part2", (None, 4))
+    if part2.shape[0] < T:
+        raise ValueError(f"part2: {part2.shape[0]} rows for {T} tiles")
+    check(_cabi.load().mvmc_rig_step(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
+                                     _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), _stream()),
+          "mvmc_rig_step")

@@ -1,0 +1,293 @@
+"""Refine each sequence's camera rig from its own tracked people: an offline step between a first track and a re-track.
+
+Every stage of the offline pipeline takes the rig as given.  refine_rigs() repairs a rig that is a little stale (a bumped tripod, a
+calibration a day old) by a bundle adjustment over the keypoints of the people the tracker already follows:
+
+  a. selection: the body fit's (mvmc_body_observe on the records' joints: per record frame and camera a pose slot or -1), every
+     ``frame_step``-th frame of each record;
+  b. points: one per (record, frame, keypoint of the 17 ingested) that at least ``min_views`` selected views see with score >
+     ``min_score``; start = mvmc_dlt's arithmetic on the input rig (a NaN point is dropped); an observation farther than ``max_px``
+     from its point's reprojection is dropped, once; a point left with fewer than ``min_views`` observations is dropped.  The set is
+     then fixed;
+  c. cameras: camera 0 is held; a camera with fewer than ``min_cam_obs`` observations is held too -- it is not moved at all, not even
+     by the gauge rescale, so its observations leave the problem (points are checked against ``min_views`` once more; one pass).
+     Fewer than two free cameras or fewer than 3 points: the input rig comes back with ``stop`` saying so;
+  d. Levenberg-Marquardt with the body fit's rules on E = 1/2 sum r^2 (plain pixel reprojection, unweighted, NO robust loss: the two
+     gates are the only outlier handling); unknowns: every point, and per free camera a rotation increment (R <- exp([w]x) R) and a
+     translation increment.  The points are eliminated by a Schur complement; the reduced camera system is solved by Cholesky;
+  e. after every accepted trial the camera centres and points are scaled about camera 0's centre so that the distance from camera 0
+     to the first free camera keeps its input length (an exact gauge move).
+
+It does not touch intrinsics or distortion, does no time synchronisation and is no calibration from scratch: the input rig must be
+good enough for the tracker to produce records.
+
+Device code: csrc/mvmc_rigfit.hip (include/mvmc.h: mvmc_rig_start, mvmc_rig_accumulate, mvmc_rig_step); NumPy restatement:
+tests/rig_refine_np.py.  Sequences with the same number of cameras share every launch, each with its own rig; there is no host
+synchronisation between the trials and one read-back per group.
+"""
+from __future__ import annotations
+
+import time
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import body_fit
+from .body_fit import LM_FTOL, LM_MU0, LM_XTOL, _record_arrays
+from .common import Calib
+from .sequences import SequenceInput, check_sequences
+
+TILE = 64            # include/mvmc.h: MVMC_RIG_TILE
+MAX_CAMS = 8         # MVMC_RIG_MAX_CAMS
+MAX_ITER_CAP = 24    # MVMC_RIG_MAX_ITER
+STOP = {0: "running", 1: "xtol", 2: "ftol", 3: "few_cameras", 4: "few_points", 5: "max_iter"}   # MVMC_RIG_STOP_*
+
+
+@dataclass
+class RigRefinement:
+    calibs: list                 # NEW [Calib] * C: K and img_wh_size kept, Rt / P / Kr_inv new
+    rms_before: float            # px, over the observations of the problem (NaN without any)
+    rms_after: float
+    n_points: int
+    n_obs: int
+    obs_per_camera: np.ndarray   # (C,)
+    held: np.ndarray             # (C,) bool: cameras not moved
+    cost: np.ndarray             # E at the start and after every trial
+    trials: list                 # 1 accepted / 0 rejected
+    stop: str                    # "ftol", "xtol", "max_iter", "few_cameras", "few_points"
+    moved: np.ndarray            # (C, 2): rotation angle (rad) and centre displacement (m)
+
+
+def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step):
+    """The input checks of refine_rigs, before any device work: ValueError, or (shapes, per sequence the records' (frames, params,
+    joints) arrays)."""
+    if len(tracklets_per_sequence) != len(sequences):
+        raise ValueError(f"refine_rigs: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
+    if int(min_views) < 2:
+        raise ValueError("refine_rigs: min_views >= 2 required (a point needs two views)")
+    if int(frame_step) < 1:
+        raise ValueError("refine_rigs: frame_step >= 1 required")
+    if not 0 <= int(max_iter) <= MAX_ITER_CAP:
+        raise ValueError(f"refine_rigs: 0 <= max_iter <= {MAX_ITER_CAP} required")
+    if not (float(max_px) > 0.0 and float(min_score) >= 0.0 and int(min_cam_obs) >= 0):
+        raise ValueError("refine_rigs: max_px > 0, min_score >= 0 and min_cam_obs >= 0 required")
+    shapes = check_sequences(sequences)
+    recs = []
+    for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
+        if not 2 <= C <= MAX_CAMS:
+            raise ValueError(f"refine_rigs: sequence {s} has {C} cameras, 2 .. {MAX_CAMS} required")
+        recs.append([_record_arrays(t, F, f"sequence {s}, record {j}") for j, t in enumerate(tl)])
+    return shapes, recs
+
+
+def _per_camera(seq_of, obs, n_seqs):
+    """(S, C) observations per sequence and camera."""
+    return np.stack([np.bincount(seq_of[obs[:, c]], minlength=n_seqs) for c in range(obs.shape[1])], axis=1)
+
+
+def pack_problems(valid, dist, x_ok, seq_of, n_seqs, max_px, min_views, min_cam_obs):
+    """Steps b - c on the candidates of a group.  valid (n,C) bool: the camera sees the candidate; dist (n,C) px at the start values;
+    x_ok (n,) bool: the start value is finite; seq_of (n,) the candidate's sequence (position in the group).
+    -> (obs (n,C) bool: the observations of the problem, held (S,C) bool, stop (S,) int: 0 or MVMC_RIG_STOP_FEW_*)."""
+    valid = np.asarray(valid, bool)
+    n, C = valid.shape
+    with np.errstate(invalid="ignore"):
+        obs = valid & (np.asarray(dist) <= max_px) & np.asarray(x_ok, bool)[:, None]
+    obs &= (obs.sum(axis=1) >= min_views)[:, None]
+    seq_of = np.asarray(seq_of, np.int64)
+    held = _per_camera(seq_of, obs, n_seqs) < min_cam_obs
+    held[:, 0] = True
+    drop = held.copy()
+    drop[:, 0] = False                       # camera 0 stays in the problem: it is the anchor
+    obs &= ~drop[seq_of]
+    obs &= (obs.sum(axis=1) >= min_views)[:, None]
+    n_pts = np.bincount(seq_of[obs.any(axis=1)], minlength=n_seqs)
+    stop = np.where((~held).sum(axis=1) < 2, 3, np.where(n_pts < 3, 4, 0)).astype(np.int32)
+    return obs, held, stop
+
+
+def tile_tables(n_points):
+    """n_points (S,) points per sequence, stored sequence by sequence -> tile (T,4) i32 (sequence, first point, points, 0) and seq (S,4)
+    i32 (first tile, tiles, first point, points): tiles of TILE points cut from each sequence's own points."""
+    n_points = np.asarray(n_points, np.int64)
+    p_lo = np.concatenate([[0], np.cumsum(n_points)])
+    n_t = (n_points + TILE - 1) // TILE
+    t_lo = np.concatenate([[0], np.cumsum(n_t)])
+    tile = np.zeros((int(t_lo[-1]), 4), np.int32)
+    for s in range(n_points.shape[0]):
+        k = np.arange(n_t[s])
+        tile[t_lo[s]:t_lo[s + 1], 0] = s
+        tile[t_lo[s]:t_lo[s + 1], 1] = p_lo[s] + k * TILE
+        tile[t_lo[s]:t_lo[s + 1], 2] = np.minimum(TILE, n_points[s] - k * TILE)
+    seq = np.stack([t_lo[:-1], n_t, p_lo[:-1], n_points], axis=1).astype(np.int32)
+    return tile, seq
+
+
+def _moved(Rt_in, Rt_out):
+    out = np.zeros((Rt_in.shape[0], 2))
+    for c in range(Rt_in.shape[0]):
+        D = Rt_out[c, :, :3] @ Rt_in[c, :, :3].T
+        w = 0.5 * np.array([D[2, 1] - D[1, 2], D[0, 2] - D[2, 0], D[1, 0] - D[0, 1]])
+        out[c, 0] = np.arctan2(np.linalg.norm(w), (np.trace(D) - 1.0) / 2.0)     # (arccos of the trace alone loses half the digits near 0)
+        out[c, 1] = np.linalg.norm(Rt_out[c, :, :3].T @ Rt_out[c, :, 3] - Rt_in[c, :, :3].T @ Rt_in[c, :, 3])
+    return out
+
+
+def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], max_iter: int = 10,
+                max_px: float = body_fit.MAX_DIST, min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100,
+                frame_step: int = 1, device="cuda:0", timings: Optional[dict] = None, variant: int = 1,
+                problems: Optional[list] = None) -> List[RigRefinement]:
+    """Refine the rig of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows track_sequences
+    takes -- from its MvTracklet records.  -> one RigRefinement per sequence; the inputs are not touched.
+    timings: a dict that receives the seconds spent in {"select", "start", "trials", "records"} (synchronising between the parts).
+    variant: 1 the tile products on the matrix cores, 0 as FMAs.  problems: a list that receives, per sequence, the packed problem
+    (dict X0 (N,3), uv (N,C,2), cand (n,C,3), rows (N,): the candidates that became points) -- what the tests compare."""
+    if len(sequences) == 0:
+        if len(tracklets_per_sequence):
+            raise ValueError("refine_rigs: records without sequences")
+        return []
+    shapes, recs = check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step)
+    import torch
+
+    from . import _cabi
+    from . import device as dev
+    d = torch.device(device)
+    tm = {"select": 0.0, "start": 0.0, "trials": 0.0, "records": 0.0}
+
+    def lap(k, t0):
+        if timings is not None:
+            torch.cuda.synchronize(d)
+        t1 = time.perf_counter()
+        tm[k] += t1 - t0
+        return t1
+
+    out: List[Optional[RigRefinement]] = [None] * len(sequences)
+    if problems is not None:
+        problems[:] = [None] * len(sequences)
+    by_c = {}
+    for i, (_, C, _) in enumerate(shapes):
+        by_c.setdefault(C, []).append(i)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+    for C, ids in by_c.items():
+        t0 = time.perf_counter()
+        S = len(ids)
+        Pg = max(shapes[i][2] for i in ids)
+        f_off = np.concatenate([[0], np.cumsum([shapes[i][0] for i in ids])]).astype(np.int64)
+        ks = [np.asarray(sequences[i][0]) for i in ids]
+        dt = np.float32 if all(k.dtype == np.float32 for k in ks) else np.float64
+        kps = np.zeros((int(f_off[-1]), C, Pg, ks[0].shape[3], 3), dtype=dt)
+        cnt = np.zeros((int(f_off[-1]), C), dtype=np.int32)
+        for r, i in enumerate(ids):
+            kps[f_off[r]:f_off[r + 1], :, :ks[r].shape[2]] = ks[r]
+            cnt[f_off[r]:f_off[r + 1]] = np.asarray(sequences[i][1])
+        Kin = np.array([[np.asarray(c.K, np.float64).reshape(3, 3) for c in sequences[i][2]] for i in ids])
+        Rtin = np.array([[np.asarray(c.Rt, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
+        Pm = np.array([[np.asarray(c.P, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
+        items = [(r, j) for r, i in enumerate(ids) for j in range(len(recs[i]))]
+        n_cand = 0
+        if items:
+            # the body fit's selection, problems in (sequence, record, frame) order
+            fr = [recs[ids[r]][j][0] for r, j in items]
+            n_of = np.array([f.shape[0] for f in fr], dtype=np.int64)
+            frame_of = np.concatenate([f + f_off[r] for f, (r, _) in zip(fr, items)]).astype(np.int32)
+            rig_of = np.repeat(np.array([r for r, _ in items], dtype=np.int32), n_of)
+            rank = np.repeat(np.array([j for _, j in items], dtype=np.int32), n_of)
+            joints = np.concatenate([recs[ids[r]][j][2] for r, j in items])
+            order = np.argsort(frame_of, kind="stable").astype(np.int32)
+            fs = frame_of[order]
+            lo = np.searchsorted(fs, frame_of, side="left").astype(np.int32)
+            hi = np.searchsorted(fs, frame_of, side="right").astype(np.int32)
+            k17, c17 = dev.ingest(T(kps), T(cnt))
+            Pm_d = T(Pm)
+            members, _, _, _ = dev.body_observe(k17, c17, Pm_d, T(frame_of), T(rig_of), T(joints), T(order), T(lo), T(hi), T(rank),
+                                                float(max_px), float(min_score))
+            take = np.concatenate([np.arange(0, n, int(frame_step)) + o for n, o in zip(n_of, np.cumsum(n_of) - n_of)])
+            mem = members[T(take)].long()                                    # (B, C)
+            o17 = k17.reshape(-1, 17, 3)[mem.clamp(min=0)]                     # (B, C, 17, 3)
+            o17[..., 2] = torch.where((mem >= 0)[:, :, None], o17[..., 2], torch.zeros((), dtype=o17.dtype, device=d))
+            obs_all = o17.permute(0, 2, 1, 3).reshape(-1, C, 3)
+            is_cand = ((obs_all[:, :, 2] > float(min_score)).sum(dim=1) >= int(min_views))
+            obs_d = obs_all[is_cand].contiguous()
+            rig_c = T(np.repeat(rig_of[take], 17))[is_cand].contiguous()
+            n_cand = int(obs_d.shape[0])
+        t0 = lap("select", t0)
+        if n_cand:
+            # the points and distances stay on the device; the host gates on the distances alone
+            X0_d, dist_d = dev.rig_start(obs_d, rig_c, Pm_d, float(min_score))
+            dist, seq_of = dist_d.cpu().numpy(), rig_c.cpu().numpy().astype(np.int64)
+            x_ok = torch.isfinite(X0_d[:, :3]).all(dim=1).cpu().numpy()
+        else:
+            dist, seq_of, x_ok = np.zeros((0, C)), np.zeros((0,), np.int64), np.zeros((0,), bool)
+        obs, held, stop0 = pack_problems(~np.isnan(dist), dist, x_ok, seq_of, S, float(max_px), int(min_views), int(min_cam_obs))
+        is_pt = obs.any(axis=1)
+        n_pts = np.bincount(seq_of[is_pt], minlength=S)
+        n_obs = _per_camera(seq_of, obs, S)
+        run = stop0 == 0
+        dev_pt = is_pt & run[seq_of]                                            # points of the sequences that are solved
+        tile, seq = tile_tables(np.where(run, n_pts, 0))
+        slot = np.where(held, -1, np.cumsum(~held, axis=1) - 1).astype(np.int32)
+        cams = np.concatenate([Kin.reshape(S, C, 9), Rtin[:, :, :, :3].reshape(S, C, 9), Rtin[:, :, :, 3]], axis=2)
+        info = np.zeros((S, _cabi.RIG_INFO_DOUBLES))
+        info[:, 8:8 + MAX_ITER_CAP] = -1.0
+        ctl = np.zeros((S, 4), np.int32)
+        ctl[:, 0] = stop0
+        if n_cand:
+            pt_d = T(dev_pt)
+            X_d = X0_d[pt_d][:, :3].contiguous()
+            uv_d = torch.where(T(obs[dev_pt])[:, :, None], obs_d[pt_d][:, :, :2], torch.full((), float("nan"), dtype=torch.float64, device=d))
+            uv_d = uv_d.contiguous()
+        else:
+            X_d, uv_d = torch.zeros((0, 3), dtype=torch.float64, device=d), torch.zeros((0, C, 2), dtype=torch.float64, device=d)
+        t0 = lap("start", t0)
+        Xt_d = X_d.clone()
+        tile_d, seq_d, slot_d, cams_d, info_d, ctl_d = T(tile), T(seq), T(slot), T(cams), T(info), T(ctl)
+        camt_d = cams_d.clone()
+        part, part2, red = dev.rig_work(tile.shape[0], S, C, d)
+        if run.any():
+            for _ in range(max(int(max_iter), 1)):
+                dev.rig_accumulate(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant)
+                if int(max_iter):
+                    dev.rig_step(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, LM_FTOL, LM_XTOL,
+                                 part2)
+        t0 = lap("trials", t0)
+        back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()]).cpu().numpy()   # the one read-back
+        cams_h = back[:S * C * 21].reshape(S, C, 21)
+        info_h = back[S * C * 21:S * C * 21 + info.size].reshape(S, -1)
+        ctl_h = back[S * C * 21 + info.size:].reshape(S, 4).astype(np.int64)
+        if problems is not None and n_cand:
+            cand, X0 = obs_d.cpu().numpy(), X0_d.cpu().numpy()
+        for r, i in enumerate(ids):
+            Rt_new = np.concatenate([cams_h[r, :, 9:18].reshape(C, 3, 3), cams_h[r, :, 18:21, None]], axis=2)
+            n_o = int(n_obs[r].sum())
+            if run[r]:
+                n_t = int(ctl_h[r, 1])
+                cost = info_h[r, 8 + MAX_ITER_CAP:8 + MAX_ITER_CAP + n_t + 1].copy()
+                trials = [int(v) for v in info_h[r, 8:8 + n_t]]
+                rb, ra = float(np.sqrt(2.0 * info_h[r, 0] / n_o)), float(np.sqrt(2.0 * info_h[r, 1] / n_o))
+            else:
+                dd = dist[(seq_of == r)[:, None] & obs]
+                e0 = 0.5 * float(np.sum(dd * dd))
+                cost, trials = (np.array([e0]) if n_o else np.zeros(0)), []
+                rb = ra = float(np.sqrt(2.0 * e0 / n_o)) if n_o else float("nan")
+            calibs = [Calib.from_k_rt(np.array(c.K, np.float64), Rt_new[k].copy(), c.img_wh_size) for k, c in enumerate(sequences[i][2])]
+            out[i] = RigRefinement(calibs=calibs, rms_before=rb, rms_after=ra, n_points=int(n_pts[r]), n_obs=n_o,
+                                   obs_per_camera=n_obs[r].copy(), held=held[r].copy(), cost=cost, trials=trials,
+                                   stop=STOP[int(ctl_h[r, 0])], moved=_moved(Rtin[r], Rt_new))
+            if problems is not None and n_cand:
+                m = seq_of == r
+                pr = is_pt[m]
+                problems[i] = dict(cand=cand[m], rows=np.flatnonzero(pr), X0=X0[m][pr][:, :3],
+                                   uv=np.where(obs[m][pr][:, :, None], cand[m][pr][:, :, :2], np.nan))
+        lap("records", t0)
+    if timings is not None:
+        timings.update(tm)
+    return out
+
+
+def refine_rig(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, max_iter: int = 10, max_px: float = body_fit.MAX_DIST,
+               min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100, frame_step: int = 1, device="cuda:0",
+               timings: Optional[dict] = None) -> RigRefinement:
+    """refine_rigs for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> RigRefinement."""
+    return refine_rigs([(kps, counts, calibs)], [tracklets], max_iter=max_iter, max_px=max_px, min_score=min_score, min_views=min_views,
+                       min_cam_obs=min_cam_obs, frame_step=frame_step, device=device, timings=timings)[0]
