@@ -600,7 +600,9 @@ int mvmc_relink(const double* rec, const int32_t* frames, const int32_t* seq, in
  * pixel reprojection K (R X + t), E = 1/2 sum r^2; Levenberg-Marquardt ((A + mu diag A) d = -g, mu / 10 accepted, x 10 rejected) with
  * the points eliminated by a Schur complement.  Sequences of one camera count share every launch; every sum has a fixed order (tiles
  * of MVMC_RIG_TILE points cut from the sequence's own points, tile parts added in tile order), no atomics.
- *   X, X_trial (N,3) f64; uv (N,C,2) f64, NaN = the camera does not observe the point
+ *   X, X_trial (N,3) f64; uv (N,C,2) f64, NaN = the camera does not observe the point.  PRECONDITION: every point of a running
+ *     sequence has at least two observations among the cameras of the problem (a point without any has V = 0: its V* has no Cholesky
+ *     factor and NaN goes into every sum of its tile); the caller's packing sees to that (rig_refine.py: pack_problems, min_views >= 2)
  *   tile (T,4) i32: sequence, first point, points (<= MVMC_RIG_TILE), 0;  seq (S,4) i32: first tile, tiles, first point, points
  *   slot (S,C) i32: the camera's position in the reduced system (0 .. n_free - 1, ascending with the camera) or -1 = held
  *   cams, cams_trial (S,C,MVMC_RIG_CAM_DOUBLES) f64: K (9), R (9), t (3), row-major

@@ -101,7 +101,8 @@ def cost(X, uv, K, R, t):
 
 def terms(X, uv, K, R, t, held, mu):
     """The damped normal equations at (X, cameras) and their Schur reduction onto the free cameras (slot order = camera order):
-    -> dict(E, S (6n,6n), g (6n,), and what the back-substitution needs)."""
+    -> dict(E, S (6n,6n), g (6n,), and what the back-substitution needs: Wf (N,6n,3), the damped point blocks Vd = V* and their inverses
+    Vi, the gradients gp (N,3) and gc (6n,), the diagonals dU (6n,) and dV (N,3))."""
     N, C = uv.shape[:2]
     free = np.flatnonzero(~held)
     slot = -np.ones(C, np.int64)
@@ -137,7 +138,7 @@ def terms(X, uv, K, R, t, held, mu):
     for s, c in enumerate(free):
         S[6 * s:6 * s + 6, 6 * s:6 * s + 6] += U[c] + mu * np.diag(np.diag(U[c]))
         dU[6 * s:6 * s + 6] = np.diag(U[c])
-    return dict(E=E, S=S, g=g, free=free, Wf=Wf, Vi=Vi, gp=gp, gc=gc[free].reshape(M), dU=dU, dV=dV)
+    return dict(E=E, S=S, g=g, free=free, Wf=Wf, Vd=Vd, Vi=Vi, gp=gp, gc=gc[free].reshape(M), dU=dU, dV=dV)
 
 
 def rescale(X, R, t, held, L0):
@@ -152,9 +153,37 @@ def rescale(X, R, t, held, L0):
     return c[0] + s * (X - c[0]), t2
 
 
-def solve(prob, K, Rt, max_iter=10, mu0=LM_MU0, ftol=LM_FTOL, xtol=LM_XTOL):
+def trial(X, uv, K, R, t, held, mu):
+    """Everything one Levenberg-Marquardt trial at (X, cameras) and mu computes -> dict(terms, mu, bad); and where the reduced matrix is
+    positive definite (bad False): dc (6 n_free,) the camera step, dp (N,3) the point steps, dg = d.g, dDd = d^T diag(A) d,
+    pred = 1/2 (mu dDd - dg), dmax = |d|_inf, the trial cameras R, t and points X, and their cost Et."""
+    T = terms(X, uv, K, R, t, held, mu)
+    out = dict(terms=T, mu=mu, bad=False)
+    try:
+        Lc = np.linalg.cholesky(T["S"])
+    except np.linalg.LinAlgError:
+        out["bad"] = True
+        return out
+    dc = -np.linalg.solve(Lc.T, np.linalg.solve(Lc, T["g"]))
+    dp = np.einsum("nkl,nl->nk", T["Vi"], -T["gp"] - np.einsum("nik,i->nk", T["Wf"], dc))
+    dg = dc @ T["gc"] + np.sum(dp * T["gp"])
+    dDd = np.sum(dc * dc * T["dU"]) + np.sum(dp * dp * T["dV"])
+    pred = 0.5 * (mu * dDd - dg)
+    dmax = max(np.abs(dc).max(), np.abs(dp).max())
+    Rn, tn = R.copy(), t.copy()
+    for s, c in enumerate(T["free"]):
+        Rn[c] = rodrigues(dc[6 * s:6 * s + 3]) @ R[c]
+        tn[c] = t[c] + dc[6 * s + 3:6 * s + 6]
+    Xn = X + dp
+    out.update(dc=dc, dp=dp, dg=dg, dDd=dDd, pred=pred, dmax=dmax, R=Rn, t=tn, X=Xn, Et=cost(Xn, uv, K, Rn, tn))
+    return out
+
+
+def solve(prob, K, Rt, max_iter=10, mu0=LM_MU0, ftol=LM_FTOL, xtol=LM_XTOL, trace=None):
     """Steps d - e on build_problem's output -> dict(Rt (C,3,4), X, cost [E0, E after every trial], trials [1 / 0], stop, n_points,
-    n_obs, rms_before, rms_after, gauge: per accepted trial the relative change of E by the rescale)."""
+    n_obs, rms_before, rms_after, gauge: per accepted trial the relative change of E by the rescale).  trace: a list that receives
+    trial()'s dict of every look at the system -- the last one made no trial when the stop is xtol or ftol before a trial -- with E,
+    the cost it started from."""
     K, Rt = np.asarray(K, np.float64), np.asarray(Rt, np.float64)
     X, uv, held = prob["X"].copy(), prob["uv"], prob["held"]
     R, t = Rt[:, :, :3].copy(), Rt[:, :, 3].copy()
@@ -172,32 +201,22 @@ def solve(prob, K, Rt, max_iter=10, mu0=LM_MU0, ftol=LM_FTOL, xtol=LM_XTOL):
     L0 = np.linalg.norm(c_in[free[0]] - c_in[0])
     mu, stop = mu0, "max_iter"
     for _ in range(int(max_iter)):
-        T = terms(X, uv, K, R, t, held, mu)
-        try:
-            Lc = np.linalg.cholesky(T["S"])
-        except np.linalg.LinAlgError:
+        tr = trial(X, uv, K, R, t, held, mu)
+        tr["E"] = E
+        if trace is not None:
+            trace.append(tr)
+        if tr["bad"]:
             out["trials"].append(0)
             out["cost"].append(E)
             mu *= 10.0
             continue
-        dc = -np.linalg.solve(Lc.T, np.linalg.solve(Lc, T["g"]))
-        dp = np.einsum("nkl,nl->nk", T["Vi"], -T["gp"] - np.einsum("nik,i->nk", T["Wf"], dc))
-        dg = dc @ T["gc"] + np.sum(dp * T["gp"])
-        dDd = np.sum(dc * dc * T["dU"]) + np.sum(dp * dp * T["dV"])
-        pred = 0.5 * (mu * dDd - dg)
-        dmax = max(np.abs(dc).max(), np.abs(dp).max())
-        if dmax < xtol:
+        if tr["dmax"] < xtol:
             stop = "xtol"
             break
-        if pred < ftol * E:
+        if tr["pred"] < ftol * E:
             stop = "ftol"
             break
-        Rn, tn = R.copy(), t.copy()
-        for s, c in enumerate(free):
-            Rn[c] = rodrigues(dc[6 * s:6 * s + 3]) @ R[c]
-            tn[c] = t[c] + dc[6 * s + 3:6 * s + 6]
-        Xn = X + dp
-        Et = cost(Xn, uv, K, Rn, tn)
+        Rn, tn, Xn, Et = tr["R"], tr["t"], tr["X"], tr["Et"]
         acc = Et < E
         out["trials"].append(int(acc))
         if acc:

@@ -161,3 +161,109 @@ def test_packing_against_hand_made_cases():
     obs, held, stop = rg.pack_problems(v, np.where(v, dd, np.nan), np.isfinite(X).all(axis=1), np.zeros(len(cand), int), 1, 20.0, 3, 700)
     assert np.array_equal(held[0], prob["held"]) and np.array_equal(np.flatnonzero(obs.any(axis=1)), prob["rows"])
     assert np.array_equal(obs[obs.any(axis=1)], ~np.isnan(prob["uv"][:, :, 0])) and (~obs).any() and held[0, 1:].any()
+
+
+# ---- the hand-made cases of the kernel tests (tests/rig_cases.py), proven on the restatement alone ----
+import rig_cases as rc
+
+
+@pytest.mark.parametrize("name", list(rc.CASES))
+def test_case_precondition(name):
+    """Every point has at least two observations among the cameras of the problem (a point without any makes V = 0 and NaN of its
+    whole tile: include/mvmc.h), a held camera other than camera 0 has none, and every free camera but the deliberately empty one has."""
+    mk = rc.CASES[name][0]
+    c = rc.case(name)
+    prob = c["prob"]
+    obs = ~np.isnan(prob["uv"][:, :, 0])
+    assert prob["X"].shape == (mk["N"], 3) and np.isfinite(prob["X"]).all() and prob["uv"].shape == (mk["N"], mk["C"], 2)
+    assert np.array_equal(np.isnan(prob["uv"][:, :, 0]), np.isnan(prob["uv"][:, :, 1]))
+    assert obs.sum(axis=1).min() >= 2
+    held_extra = sorted(mk.get("held_extra", ()))
+    assert np.flatnonzero(prob["held"]).tolist() == [0] + held_extra and prob["stop"] is None
+    per_cam = obs.sum(axis=0)
+    for k in range(mk["C"]):
+        if k in held_extra or k == mk.get("empty"):
+            assert per_cam[k] == 0
+        else:
+            assert per_cam[k] >= 20
+    assert not np.array_equal(c["Rt"][1:], c["Rt_true"][1:]) and np.array_equal(c["Rt"][0], c["Rt_true"][0])
+
+
+@pytest.mark.parametrize("name", list(rc.CASES))
+def test_case_margins(name):
+    """Every decision the device has to reproduce is clear of its threshold (rig_cases.margin_violations): |Et - E| / E >= 1e-6 at
+    every trial, |d|_inf outside [xtol / 10, 10 xtol], pred / E and the accepted reductions outside [ftol / 10, 10 ftol].  Device and
+    restatement agree to ~1e-13 on these, so the equalities of trials and stop in tests/test_gpu_rig_kernels.py cannot fail for
+    rounding reasons.  A case that violates a margin gets another seed, not another margin."""
+    out, trace = rc.reference(name)
+    for t in trace:
+        if not t["bad"]:
+            print(f"  E {t['E']:.6g} mu {t['mu']:.0e} |d|_inf {t['dmax']:.2e} pred / E {t['pred'] / t['E']:.2e} (E - Et) / E {(t['E'] - t['Et']) / t['E']:.2e}")
+    assert rc.margin_violations(name) == []
+    # the restatement's own error on the reduced matrix (V*^-1 by np.linalg.inv: what it is off by shows as asymmetry) is orders below
+    # the 1e-10 the device is gated at: no point's V* is ill-conditioned enough to matter
+    for t in trace:
+        S = t["terms"]["S"]
+        assert np.abs(S - S.T).max() <= 1e-13 * np.abs(S).max() and np.linalg.cond(t["terms"]["Vd"]).max() < 1e5
+    # one look per trial, and one more where the stop came before a trial (xtol, or ftol on the prediction)
+    assert len(trace) in (len(out["trials"]), len(out["trials"]) + 1)
+    if out["stop"] == "max_iter":
+        assert len(trace) == len(out["trials"]) == rc.params(name)["max_iter"]
+
+
+def test_cases_take_their_branches():
+    ref = {n: rc.reference(n) for n in rc.CASES}
+    trials = {n: ref[n][0]["trials"] for n in rc.CASES}
+    stop = {n: ref[n][0]["stop"] for n in rc.CASES}
+    print("\n", {n: ("".join(map(str, trials[n])), stop[n]) for n in rc.CASES})
+    # the shapes: tiles and blocks as the table says
+    shape = {n: (rc.CASES[n][0]["C"], rc.CASES[n][0]["N"]) for n in rc.CASES}
+    assert [shape[n] for n in ("c2", "c3_full", "c4_held_mid", "c5_65", "c6", "c7", "c8")] == \
+        [(2, 70), (3, 64), (4, 100), (5, 65), (6, 61), (7, 199), (8, 130)]
+    for n in ("c2", "c3_full", "c4_held_mid", "c5_65", "c6", "c7", "c8", "maxit_cap"):
+        o = ref[n][0]
+        assert stop[n] in ("ftol", "xtol") and sum(trials[n]) >= 2 and o["cost"][-1] < 0.2 * o["cost"][0]
+        print(f"  {n}: rms {o['rms_before']:.2f} -> {o['rms_after']:.2f} px")
+        assert o["rms_after"] <= np.sqrt(2.0) * PIX_SIGMA                            # down to the 2 px noise of the observations
+    assert rc.case("c4_held_mid")["prob"]["held"].tolist() == [True, False, True, False]
+    assert np.array_equal(ref["c4_held_mid"][0]["Rt"][2], rc.case("c4_held_mid")["Rt"][2])
+    # a rejected trial followed by an accepted one, the first trial rejected (the one-trial tests read a rejection there)
+    s = "".join(map(str, trials["reject"]))
+    assert "01" in s and s[0] == "0" and 6 <= rc.params("reject")["max_iter"] <= 10 and rc.params("reject")["mu0"] == 1e-6
+    acc = np.array(trials["reject"], bool)
+    cost = np.array(ref["reject"][0]["cost"])
+    assert np.all(np.diff(cost)[acc] < 0) and np.all(np.diff(cost)[~acc] == 0)
+    assert all(t["Et"] >= 1.006 * t["E"] for t, a in zip(ref["reject"][1], acc) if not a)
+    # the matrix is not positive definite at every trial: nothing moves
+    o, tr = ref["bad"]
+    c = rc.case("bad")
+    assert trials["bad"] == [0] * rc.params("bad")["max_iter"] and stop["bad"] == "max_iter" and all(t["bad"] for t in tr)
+    assert np.array_equal(o["Rt"], c["Rt"]) and np.array_equal(o["X"], c["prob"]["X"]) and len(set(o["cost"])) == 1
+    mu = rr.LM_MU0
+    for t in tr:                                                     # mu x 10 at every one of them, exactly
+        assert t["mu"] == mu
+        mu *= 10.0
+    e = rc.CASES["bad"][0]["empty"]
+    S = tr[0]["terms"]["S"]
+    q = list(tr[0]["terms"]["free"]).index(e)
+    assert not c["prob"]["held"][e] and np.all(S[6 * q:6 * q + 6] == 0.0)
+    # the three stop rules, each after two accepted trials
+    assert (trials["xtol"], stop["xtol"]) == ([1, 1], "xtol") and rc.params("xtol")["xtol"] == 1e-3
+    assert (trials["ftol"], stop["ftol"]) == ([1, 1], "ftol") and rc.params("ftol")["ftol"] == 1e-4
+    assert (trials["maxit"], stop["maxit"]) == ([1, 1], "max_iter") and rc.params("maxit")["max_iter"] == 2
+    assert (trials["maxit0"], stop["maxit0"], len(ref["maxit0"][0]["cost"])) == ([], "max_iter", 1)
+    assert rc.params("maxit_cap")["max_iter"] == rc.MAX_ITER_CAP and len(trials["maxit_cap"]) < rc.MAX_ITER_CAP
+
+
+def test_trial_is_one_step_of_solve():
+    """solve() with a trace is solve() without, and its first look is trial() at the start values."""
+    c, p = rc.case("c4_held_mid"), rc.params("c4_held_mid")
+    a = rr.solve(c["prob"], c["K"], c["Rt"], **p)
+    b, trace = rc.reference("c4_held_mid")
+    assert np.array_equal(a["Rt"], b["Rt"]) and np.array_equal(a["X"], b["X"]) and a["cost"] == b["cost"] and a["trials"] == b["trials"]
+    t = rr.trial(c["prob"]["X"], c["prob"]["uv"], c["K"], c["Rt"][:, :, :3], c["Rt"][:, :, 3], c["prob"]["held"], p["mu0"])
+    for k in ("dc", "dp", "R", "t", "X"):
+        assert np.array_equal(t[k], trace[0][k])
+    assert (t["Et"], t["pred"], t["dmax"], t["dg"], t["dDd"]) == tuple(trace[0][k] for k in ("Et", "pred", "dmax", "dg", "dDd"))
+    assert t["Et"] == rr.cost(t["X"], c["prob"]["uv"], c["K"], t["R"], t["t"]) and t["pred"] == 0.5 * (t["mu"] * t["dDd"] - t["dg"])
+    assert not t["bad"]
