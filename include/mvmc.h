@@ -641,6 +641,44 @@ int mvmc_rig_step(double* X, double* X_trial, const double* uv, const int32_t* t
                   double* cams, const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points, int n_tiles,
                   int n_seqs, int n_views, int max_iter, double ftol, double xtol, double* part2, mvmcStream_t stream);
 
+/* ---- lens distortion at the door of the pipeline (multiview_motion_capture_amd/lens.py; restated in tests/lens_np.py).  No counterpart
+ * in the reference, whose only projection is project_3d_points_to_image_plane_without_distortion (mv_math_util.py).  Every other entry
+ * point reads keypoints as pinhole pixels of P = K Rt; mvmc_lens_undistort turns a detector's raw pixels into those, once, and
+ * mvmc_lens_distort is the way back (drawing on the raw images).  One pass over the triples, float64 arithmetic, a float32 output is
+ * the float64 result rounded once.
+ *   kps_in, kps_out (F,C,n_points,3) f32|f64 triples (x, y, score), dtype as mvmc_ingest; n_points = P J for any J.  kps_out may be
+ *     kps_in (each lane reads, then writes, its own triple)
+ *   lens (R,C,MVMC_LENS_DOUBLES) f64, one row per (rig, camera): {model, fx, fy, cx, cy, skew, k[0..7], 0, 0}; a row whose model is
+ *     neither MVMC_LENS_BROWN nor MVMC_LENS_FISHEYE is a pinhole row
+ *   rig_of_frame (F) i32 or NULL = rig 0.  A frame whose index lies outside [0, R) reads no row: its triples come out (0,0,0) and
+ *     its dropped row is -1
+ *   dropped (F,C) i32 out, every element written once: scored keypoints of the view without a valid pre-image (undistort); distort
+ *     writes 0 (it drops nothing) or -1
+ * Normalised coordinates y = (v - cy) / fy, x = (u - cx - skew y) / fx; pixels u = fx x + skew y + cx, v = fy y + cy.
+ * BROWN (OpenCV's order k1 k2 p1 p2 k3 k4 k5 k6): r2 = x^2 + y^2, rad = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),
+ *   x' = x rad + 2 p1 x y + p2 (r2 + 2 x^2), y' = y rad + p1 (r2 + 2 y^2) + 2 p2 x y.  The inverse is Newton's iteration in (x, y) with
+ *   the analytic Jacobian from the distorted point: at most MVMC_LENS_MAX_ITER steps, converged when |dx| + |dy| <= 1e-13 (1 + |x| + |y|)
+ *   (x, y after the step).
+ * FISHEYE (cv2.fisheye, Kannala-Brandt k1..k4): theta = atan r, theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+ *   scale theta_d / r (1 at r = 0).  The inverse is Newton's iteration in theta from theta_d, |d| <= 1e-13 (1 + |theta|), then
+ *   r = tan theta.
+ * Accept rule of the inverse, for a triple with score > 0: the iteration converged; the result is finite; at every iterate a step was
+ *   taken from and at the answer the forward Jacobian's determinant (fisheye: d theta_d / d theta) is positive and Brown's rad is
+ *   positive; fisheye: 0 <= theta < MVMC_LENS_FISHEYE_MAX_THETA.  A rejected triple is written (0,0,0) -- OpenPose's "not detected",
+ *   which mvmc_ingest's score test ignores -- and counted.  A triple with score <= 0 and every triple of a pinhole row is copied bit
+ *   for bit; scores always are.
+ * Argument errors return MVMC_ERR_ARG before any HIP call; MVMC_ERR_UNSUPPORTED for more than 128 cameras. ---- */
+#define MVMC_LENS_DOUBLES 16
+#define MVMC_LENS_PINHOLE 0
+#define MVMC_LENS_BROWN 1
+#define MVMC_LENS_FISHEYE 2
+#define MVMC_LENS_MAX_ITER 12
+#define MVMC_LENS_FISHEYE_MAX_THETA 1.5
+int mvmc_lens_undistort(const void* kps_in, int dtype, int n_frames, int n_views, int n_points, const double* lens,
+                        const int32_t* rig_of_frame, int n_rigs, void* kps_out, int32_t* dropped, mvmcStream_t stream);
+int mvmc_lens_distort(const void* kps_in, int dtype, int n_frames, int n_views, int n_points, const double* lens,
+                      const int32_t* rig_of_frame, int n_rigs, void* kps_out, int32_t* dropped, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,7 +62,7 @@ def _check(sequences, tracklets_per_sequence, rounds, max_iter, max_nfev):
         raise ValueError(f"fit_sequences: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
     if int(rounds) < 0 or not 0 <= int(max_iter) <= MAX_ITER_CAP or int(max_nfev) < 1:
         raise ValueError(f"fit_sequences: rounds >= 0, 0 <= max_iter <= {MAX_ITER_CAP} and max_nfev >= 1 required")
-    shapes = check_sequences(sequences)
+    shapes = check_sequences(sequences, "fit_sequences")
     recs = []
     for s, (tl, (F, _, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
         recs.append([_record_arrays(t, F, f"sequence {s}, record {j}") for j, t in enumerate(tl)])

@@ -679,3 +679,60 @@ def rig_step(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: tor
     check(_cabi.load().mvmc_rig_step(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
                                      _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), _stream()),
           "mvmc_rig_step")
+
+
+def _lens_call(name: str, kps: torch.Tensor, lens: torch.Tensor, rig_of_frame, out: Optional[torch.Tensor]):
+    if not isinstance(kps, torch.Tensor) or kps.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{name}: kps must be a float32 or float64 tensor")
+    _req(kps, kps.dtype, "kps")
+    if kps.dim() < 3 or kps.shape[-1] != 3:
+        raise ValueError(f"{name}: expected (F,C,...,3) triples, got {tuple(kps.shape)}")
+    F, Cn = int(kps.shape[0]), int(kps.shape[1])
+    n_points = int(np.prod(kps.shape[2:-1], dtype=np.int64))
+    if Cn < 1 or n_points < 1:
+        raise ValueError(f"{name}: no cameras or no points in {tuple(kps.shape)}")
+    _req(lens, torch.float64, "lens", (None, Cn, _cabi.LENS_DOUBLES))
+    R = int(lens.shape[0])
+    if R < 1:
+        raise ValueError(f"{name}: the lens table holds no rig")
+    rig = None
+    if rig_of_frame is not None:
+        # the rig indices are checked on the host, before anything is launched: a host array as it comes (and uploaded), a device tensor
+        # by reading its extremes back (one small transfer; callers on a hot path pass the host array they built the indices in)
+        if isinstance(rig_of_frame, torch.Tensor) and rig_of_frame.is_cuda:
+            rig = _req(rig_of_frame, torch.int32, "rig_of_frame", (F,))
+            lo, hi = (int(v) for v in torch.aminmax(rig)) if F else (0, 0)
+        else:
+            host = np.ascontiguousarray(np.asarray(rig_of_frame.cpu() if isinstance(rig_of_frame, torch.Tensor) else rig_of_frame))
+            if host.shape != (F,) or host.dtype.kind not in "iu":
+                raise ValueError(f"rig_of_frame: expected ({F},) integers, got {host.dtype} {host.shape}")
+            lo, hi = (int(host.min()), int(host.max())) if F else (0, 0)
+            rig = torch.from_numpy(host.astype(np.int32)).to(kps.device) if lo >= 0 and hi < R else None
+        if lo < 0 or hi >= R:
+            raise ValueError(f"{name}: rig_of_frame holds indices in [{lo}, {hi}], the lens table has rigs 0 .. {R - 1}")
+    if out is None:
+        out = torch.empty_like(kps)
+    else:
+        _req(out, kps.dtype, "out", tuple(kps.shape))
+        if out.device != kps.device:
+            raise ValueError("out: expected a tensor on the device of kps")
+    dropped = torch.empty((F, Cn), dtype=torch.int32, device=kps.device)
+    dt = _cabi.MVMC_F32 if kps.dtype == torch.float32 else _cabi.MVMC_F64
+    if F:
+        check(getattr(_cabi.load(), name)(_p(kps), dt, F, Cn, n_points, _p(lens), _p(rig), R, _p(out), _p(dropped), _stream()), name)
+    return out, dropped
+
+
+def lens_undistort(kps: torch.Tensor, lens: torch.Tensor, rig_of_frame=None, out: Optional[torch.Tensor] = None):
+    """Raw detector pixels -> pinhole pixels (include/mvmc.h: mvmc_lens_undistort).  kps (F,C,...,3) f32|f64 triples (x, y, score), any
+    dimensions between the cameras and the triple (P, J); lens (R,C,16) f64 (lens.lens_table); rig_of_frame (F,) rig of every frame -- a
+    host integer array (checked, uploaded) or an int32 device tensor -- or None: rig 0; out: a tensor like kps, which may be kps itself.
+    -> (kps_out, dropped (F,C) i32: scored keypoints without a valid pre-image, written (0,0,0)).  An index outside the table raises
+    ValueError before anything is launched."""
+    return _lens_call("mvmc_lens_undistort", kps, lens, rig_of_frame, out)
+
+
+def lens_distort(kps: torch.Tensor, lens: torch.Tensor, rig_of_frame=None, out: Optional[torch.Tensor] = None):
+    """Pinhole pixels -> raw pixels, the forward lens model (include/mvmc.h: mvmc_lens_distort); arguments and results as
+    lens_undistort; nothing is dropped."""
+    return _lens_call("mvmc_lens_distort", kps, lens, rig_of_frame, out)

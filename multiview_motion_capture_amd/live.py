@@ -38,8 +38,12 @@ class LiveSessionError(RuntimeError):
         super().__init__("live sessions " + "; ".join(f"{sid}: {e}" for sid, e in sorted(self.errors.items())))
 
 
-def check_open(n_open: int, capacity: int, n_views: int, n_cameras: int) -> None:
-    """LivePool.open_session's checks (host only): the pool's camera count, and a free slot."""
+def check_open(n_open: int, capacity: int, n_views: int, n_cameras: int, calibs=None) -> None:
+    """LivePool.open_session's checks (host only): the pool's camera count, a free slot, and -- given the calibrations -- that none
+    carries a lens model (lens.require_pinhole)."""
+    if calibs is not None:
+        from .lens import require_pinhole
+        require_pinhole(calibs, "LivePool.open_session")
     if n_cameras != n_views:
         raise ValueError(f"open_session: {n_cameras} cameras, the pool's sessions have {n_views} (one pool per camera count)")
     if n_open >= capacity:
@@ -108,7 +112,7 @@ class LivePool:
     # -- sessions ------------------------------------------------------------------------------------------------------------------
     def open_session(self, calibs) -> int:
         """A new session on the rig ``calibs`` (one Calib per camera, in the views' order); returns its sid."""
-        check_open(len(self._sessions), self.capacity, self.C, len(calibs))
+        check_open(len(self._sessions), self.capacity, self.C, len(calibs), calibs)
         hp = HotPath(np.array([c.K for c in calibs]), np.array([c.Rt for c in calibs]), device=self.device)   # (as MvTracker._ensure)
         slot = self._free.pop(0)
         self._ch.set_rig(slot, hp)

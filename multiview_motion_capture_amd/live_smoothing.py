@@ -134,6 +134,8 @@ class LiveSmoother:
         """A new session on the rig ``calibs`` (one Calib per camera); returns its key (host only: the rig is uploaded by the next tick)."""
         if len(calibs) != self.C:
             raise ValueError(f"open_session: {len(calibs)} cameras, the smoother's sessions have {self.C}")
+        from .lens import require_pinhole
+        require_pinhole(calibs, "LiveSmoother.open_session")
         if not self._free_s:
             raise ValueError(f"open_session: all {self.capacity} session slots are taken")
         if key is None:

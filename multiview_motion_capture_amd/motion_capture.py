@@ -41,18 +41,31 @@ class SpatialTimeMatch:
 
 
 def load_calib(cpath: Path) -> Calib:
-    """motion_capture.py:250-272: a calibration file, JSON ("K", "RT", "imgSize") or pickle ("K", "R", "t")."""
+    """motion_capture.py:250-272: a calibration file, JSON ("K", "RT", "imgSize") or pickle ("K", "R", "t").  Beyond the reference: a
+    lens model, from the optional JSON keys "distCoef" (OpenCV's order) and "lensModel" ("brown", the default, or "fisheye") or the
+    optional pickle key "dist" (Brown); without them the result is the reference's pinhole calibration."""
     cpath = Path(cpath)
     if 'pkl' in cpath.suffix:
         with open(str(cpath), 'rb') as fh:
             data = pickle.load(fh)
         rt = np.concatenate([np.array(data["R"]).reshape((3, 3)), np.array(data["t"]).reshape((3, 1))], axis=1)
-        return Calib.from_k_rt(data["K"], rt, (1920, 1080))
+        return Calib.from_k_rt(data["K"], rt, (1920, 1080), lens=_lens_of(data.get("dist"), data.get("lensModel")))
     if 'js' in cpath.suffix:
         with open(str(cpath), 'r') as fh:
             js = json.load(fh)
-        return Calib.from_k_rt(js["K"], js["RT"], js["imgSize"])
+        return Calib.from_k_rt(js["K"], js["RT"], js["imgSize"], lens=_lens_of(js.get("distCoef"), js.get("lensModel")))
     raise ValueError(f'unsupported calibration format. {cpath.name}')
+
+
+def _lens_of(coeffs, model):
+    """load_calib's lens: None without coefficients (a "lensModel" alone says nothing)."""
+    if coeffs is None:
+        return None
+    from .lens import Lens
+    model = "brown" if model is None else str(model).lower()
+    if model not in ("brown", "fisheye"):
+        raise ValueError(f'unsupported lensModel {model!r}: "brown" or "fisheye"')
+    return Lens.from_opencv(coeffs, fisheye=model == "fisheye")
 
 
 def parse_openpose_kps(js_path: Path) -> Dict[int, Pose]:
@@ -259,6 +272,8 @@ class MvTracker:
         self._calm = 0      # consecutive frames a widened tracker has stayed below t_max (update_4d narrows it back after eight)
 
     def _ensure(self, d_frames):
+        from .lens import require_pinhole
+        require_pinhole([f.calib for f in d_frames], "MvTracker.update_4d")
         if self._chain is None:
             from .pipeline import HotPath
             from .tracker import ChainTracker

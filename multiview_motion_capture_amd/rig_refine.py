@@ -72,7 +72,7 @@ def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score,
         raise ValueError(f"refine_rigs: 0 <= max_iter <= {MAX_ITER_CAP} required")
     if not (float(max_px) > 0.0 and float(min_score) >= 0.0 and int(min_cam_obs) >= 0):
         raise ValueError("refine_rigs: max_px > 0, min_score >= 0 and min_cam_obs >= 0 required")
-    shapes = check_sequences(sequences)
+    shapes = check_sequences(sequences, "refine_rigs")
     recs = []
     for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
         if not 2 <= C <= MAX_CAMS:

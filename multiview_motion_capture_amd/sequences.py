@@ -38,9 +38,11 @@ class GroupLayout:
         return int(self.rig_of_chain.shape[0])
 
 
-def check_sequences(sequences: Sequence[SequenceInput]) -> List[Tuple[int, int, int]]:
+def check_sequences(sequences: Sequence[SequenceInput], who: str = "track_sequences") -> List[Tuple[int, int, int]]:
     """(F_s, C_s, P_s) of every sequence; raises ValueError on an empty list or inconsistent shapes.  Keypoint rows are OpenPose-25
-    (what load_openpose_sequence returns) or COCO-17 (the per-frame pickles' poses), the same layout for every sequence."""
+    (what load_openpose_sequence returns) or COCO-17 (the per-frame pickles' poses), the same layout for every sequence.  A calibration
+    with a lens model is refused (lens.require_pinhole, in ``who``'s name): the keypoints are read as pinhole pixels."""
+    from .lens import require_pinhole
     if len(sequences) == 0:
         raise ValueError("track_sequences: no sequences")
     shapes, joints = [], set()
@@ -57,6 +59,7 @@ def check_sequences(sequences: Sequence[SequenceInput]) -> List[Tuple[int, int, 
             raise ValueError(f"sequence {i}: counts must be ({F},{C}), got {counts.shape}")
         if len(calibs) != C:
             raise ValueError(f"sequence {i}: {len(calibs)} calibrations for {C} cameras")
+        require_pinhole(calibs, f"{who}: sequence {i}")
         if C < 1 or P < 1:
             raise ValueError(f"sequence {i}: no cameras or no person slots")
         if counts.size and (counts.min() < 0 or counts.max() > P):

@@ -133,7 +133,7 @@ def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_byte
 def _check(sequences, tracklets_per_sequence):
     if len(tracklets_per_sequence) != len(sequences):
         raise ValueError(f"smooth_sequences: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
-    shapes = check_sequences(sequences)
+    shapes = check_sequences(sequences, "smooth_sequences")
     recs = []
     for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
         if C > MAX_VIEWS:
