@@ -5,15 +5,9 @@
 // before them as frozen history.  No counterpart in the reference.
 //   append  the tick's new rows: d - 1 missing rows and the newest one (a data row from the tracker's table, or missing), a missing row
 //           = a copy of the identity's last row;
-//   per trial, inside the launch: the row blocks of the free rows on the workgroup's four waves (mvmc_smooth_row.h, the offline
-//           smoother's own), the accept / reject decision, the block-banded Cholesky sweep over the free rows -- the frozen history
-//           enters through the gradient's stencils and through the prior's interior coefficients on the first free rows --,
-//           back-substitution, the next trial point.
-// The block row is not the offline kernel's: the 39 x 39 pivot block is factored with lane = row, the row in registers and every
-// column broadcast through v_readlane (no LDS round trip, no barrier per column); the forward substitution runs in the same registers;
-// the two off-diagonal triangular solves run on a wave each with a row per lane in registers and the pivot block read as an LDS
-// broadcast; the five 39 x 39 LDS blocks rotate by pointer instead of being copied; the back-substitution is one wave without a
-// barrier (lane = column of L_tt in registers, d broadcast through v_readlane).
+//   per trial, inside the launch: the row blocks of the free rows on the workgroup's four waves (mvmc_smooth_row.h), the accept /
+//           reject decision, one block-banded solve over the free rows (mvmc_smooth_sweep.h, the sweep the offline smoother runs too),
+//           the next trial point.
 // Every sum runs in a fixed order inside one identity's own lanes: an identity's numbers depend on nothing else in the launch.
 #define MVMC_DEVICE_ONLY
 #include "mvmc_common.h"
@@ -24,8 +18,8 @@
 namespace {
 
 #include "mvmc_smooth_row.h"
+#include "mvmc_smooth_sweep.h"
 
-constexpr int SW_THREADS = 256;
 constexpr int SW_MAXW = MVMC_SMOOTH_WIN_MAX;
 constexpr int SW_RING = MVMC_SMOOTH_WIN_RING;
 constexpr int SW_ROWS = SW_MAXW + 2;                      // window + history
@@ -36,65 +30,20 @@ constexpr int SW_X = 0, SW_XT = SW_ROWS * 68, SW_PER_ITEM = 2 * SW_ROWS * 68;
 constexpr int SW_PER_ROW = 2 * SM_BLK + SM_WORK;
 static_assert(SW_RING >= 2 * SW_MAXW + 2, "ring: a jump of up to W frames keeps the rows that leave the window");
 
-struct SwSweepLds {
-    double B[5][SK2];         // L(t,t-1), L(t,t-2), L(t+1,t-1), L(t+1,t), L(t+2,t) in rotating roles
-    double S[SK2];            // the diagonal block being factored (lower triangle), then L_tt
-    double y[3][SK];          // y_{t-1}, y_{t-2}, b in rotating roles
-    double wv[SK], wa[SK];
-    double red[SW_THREADS], red2[SW_THREADS], red3[SW_THREADS];
-    int colx[SK];
-    int fail;
-};
 union SwLds {
     SmBlkLds blk[4];          // the blocks phase: one row block per wave
-    SwSweepLds sw;            // the sweep (the phases do not overlap in time)
+    SmSweepLds sw;            // the sweep (the phases do not overlap in time)
 };
 static_assert(sizeof(SwLds) <= 160 * 1024, "LDS of one workgroup");
 
-__device__ __forceinline__ double rl64(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
-// fixed-order sum / max over the workgroup (every thread calls)
-__device__ double sw_sum(double* red, double s) {
-    const int tid = threadIdx.x;
-    red[tid] = s;
-    __syncthreads();
-    for (int w = SW_THREADS / 2; w >= 1; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// the window's prior energy: every velocity / acceleration term of the nw rows whose stencil touches a free row (rows >= h)
-__device__ double sw_prior_energy(const double* __restrict__ wv, const double* __restrict__ wa, const int* __restrict__ colx,
-                                  double* red, const double* __restrict__ x, int nw, int h) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nw * SK; i += SW_THREADS) {
-        const int t = i / SK, q = i - t * SK, cx = colx[q];
-        if (t >= 1 && t >= h) {
-            const double dv = x[t * 68 + cx] - x[(t - 1) * 68 + cx];
-            s += wv[q] * dv * dv;
-        }
-        if (t >= 1 && t + 1 < nw) {
-            const double da = (x[(t + 1) * 68 + cx] - 2.0 * x[t * 68 + cx]) + x[(t - 1) * 68 + cx];
-            s += wa[q] * da * da;
-        }
-    }
-    return 0.5 * sw_sum(red, s);
-}
-
-__global__ void __launch_bounds__(SW_THREADS) smooth_window_kernel(
+__global__ void __launch_bounds__(SM_THREADS) smooth_window_kernel(
     Ik1Tables T, const double* __restrict__ kps17, const double* __restrict__ Pmats, int C, int Pmax, int n_rigs,
     const int32_t* __restrict__ items, const double* __restrict__ new_params, const int32_t* __restrict__ new_members, int n_new,
     double* __restrict__ rows, int32_t* __restrict__ members, int32_t* __restrict__ count, int n_slots, int W, int n_iter,
     double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* __restrict__ info,
     double* __restrict__ work, int work_rows) {
     __shared__ SwLds LL;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, it = blockIdx.x;
+    const int tid = threadIdx.x, wave = tid >> 6, it = blockIdx.x;
     const int32_t* im = items + (size_t)it * SW_ITEM;
     const int slot = uni((int)im[0]), rig = uni((int)im[1]), d = uni((int)im[2]), is_data = uni((int)im[3]), reset = uni((int)im[4]);
     const int src = uni((int)im[5]), f0 = uni((int)im[6]), row_lo = uni((int)im[7]);
@@ -135,17 +84,17 @@ __global__ void __launch_bounds__(SW_THREADS) smooth_window_kernel(
     double* xt = work + (size_t)it * SW_PER_ITEM + SW_XT;
     double* rowwk = work + (size_t)gridDim.x * SW_PER_ITEM + (size_t)row_lo * SW_PER_ROW;   // this item's W rows
     __syncthreads();
-    for (int i = tid; i < nw * 68; i += SW_THREADS) {
+    for (int i = tid; i < nw * 68; i += SM_THREADS) {
         const int t = i / 68, c = i - t * 68;
         const double v = ring[((lo + t) % SW_RING) * 68 + c];
         x[i] = v;
         xt[i] = v;
     }
-    SwSweepLds& L = LL.sw;
+    SmSweepLds& L = LL.sw;
     const double* Prig = Pmats + (size_t)rig * C * 12;
     // per free row r (0..m-1): blocks buffer b at rowwk + r SW_PER_ROW + b SM_BLK, the factor after them
     auto blocks_of = [&](int r, int b) -> double* { return rowwk + (size_t)r * SW_PER_ROW + (size_t)b * SM_BLK; };
-    auto factor_of = [&](int r) -> double* { return rowwk + (size_t)r * SW_PER_ROW + 2 * SM_BLK; };
+    double* fac = rowwk + 2 * SM_BLK;
     __syncthreads();
     // the row blocks of the free rows at the point p into buffer b: a row per wave at a time
     auto eval_blocks = [&](const double* p, int b) {
@@ -155,228 +104,32 @@ __global__ void __launch_bounds__(SW_THREADS) smooth_window_kernel(
                          blocks_of(r, b));
         __syncthreads();
     };
-    auto sweep_tables = [&]() {   // (the blocks phase overwrote them)
-        if (tid < SK) {
-            const int a = T.act[0][tid];
-            L.colx[tid] = a;
-            L.wv[tid] = a < 3 ? root_vel : ang_vel;
-            L.wa[tid] = a < 3 ? root_acc : ang_acc;
-        }
-        __syncthreads();
-    };
-    auto data_energy = [&](int b) -> double {
-        double s = 0.0;
-        for (int r = tid; r < m; r += SW_THREADS) s += blocks_of(r, b)[SKH + SK];
-        return sw_sum(L.red, s);
-    };
-
     eval_blocks(x, 0);
-    sweep_tables();
+    sm_sweep_tables(L, T, root_vel, root_acc, ang_vel, ang_acc);   // (the blocks phase overwrote them)
     int cur = 0, trials = 0, n_acc = 0, why = 1;
     double mu = mu0;
-    double Ed = data_energy(0), Ep = sw_prior_energy(L.wv, L.wa, L.colx, L.red, x, nw, h);
+    double Ed = sm_data_energy(L, blocks_of(0, 0), SW_PER_ROW, m), Ep = sm_prior_energy(L, x, nw, h);
     if (tid == 0) { inf[0] = Ed; inf[1] = Ep; }
 
     for (int iter = 0; iter < n_iter; ++iter) {
-        // ---- forward sweep over the free rows: L y = -g ----
-        int iP1 = 0, iP2 = 1, iQ = 2, iN1 = 3, iN2 = 4, iy1 = 0, iy2 = 1, ib = 2;
-        for (int i = tid; i < SK2; i += SW_THREADS) { L.B[0][i] = 0.0; L.B[1][i] = 0.0; L.B[2][i] = 0.0; }
-        if (tid < SK) { L.y[0][tid] = 0.0; L.y[1][tid] = 0.0; }
-        if (tid == 0) L.fail = 0;
-        __syncthreads();
-        for (int r = 0; r < m; ++r) {
-            const int t = h + r;                       // the row's index among the nw rows (the prior's coefficients and stencils)
-            const double* bt = blocks_of(r, cur);
-            double* wt = factor_of(r);
-            const double *P1 = L.B[iP1], *P2 = L.B[iP2], *Q = L.B[iQ], *y1 = L.y[iy1], *y2 = L.y[iy2];
-            double *N1 = L.B[iN1], *N2 = L.B[iN2], *bb = L.y[ib];
-            // phase A: S = A_tt + mu diag(A_tt) - P1 P1^T - P2 P2^T (lower); b = -g_t - P1 y1 - P2 y2; N1 = A_{t+1,t} - Q P1^T; N2 = A_{t+2,t}
-            for (int i = tid; i < SKH; i += SW_THREADS) {
-                int rr = 0;
-                while ((rr + 1) * (rr + 2) / 2 <= i) ++rr;
-                const int cc = i - rr * (rr + 1) / 2;
-                double a = bt[sm_up(cc, rr)];
-                if (rr == cc) {
-                    a += L.wv[rr] * sm_cv(t, t, nw) + L.wa[rr] * sm_ca(t, t, nw);
-                    wt[W_D + rr] = a;
-                    a += mu * a;
-                }
-                double s1 = 0.0, s2 = 0.0;
-                if (r >= 1)
-                    for (int q = 0; q < SK; ++q) s1 += P1[rr * SK + q] * P1[cc * SK + q];
-                if (r >= 2)
-                    for (int q = 0; q < SK; ++q) s2 += P2[rr * SK + q] * P2[cc * SK + q];
-                L.S[rr * SK + cc] = (a - s1) - s2;
-            }
-            if (tid >= 192 && tid < 192 + SK) {
-                const int q0 = tid - 192;
-                const double g = bt[SKH + q0] + sm_prior_grad(x, t, nw, L.colx[q0], L.wv[q0], L.wa[q0]);
-                wt[W_G + q0] = g;
-                double s1 = 0.0, s2 = 0.0;
-                for (int q = 0; q < SK; ++q) s1 += P1[q0 * SK + q] * y1[q];
-                for (int q = 0; q < SK; ++q) s2 += P2[q0 * SK + q] * y2[q];
-                bb[q0] = (-g - s1) - s2;
-            }
-            if (r + 1 < m)
-                for (int i = tid; i < SK2; i += SW_THREADS) {
-                    const int rr = i / SK, cc = i - rr * SK;
-                    const double a = rr == cc ? L.wv[rr] * sm_cv(t + 1, t, nw) + L.wa[rr] * sm_ca(t + 1, t, nw) : 0.0;
-                    double s1 = 0.0;
-                    if (r >= 1)
-                        for (int q = 0; q < SK; ++q) s1 += Q[rr * SK + q] * P1[cc * SK + q];
-                    N1[i] = a - s1;
-                    N2[i] = (r + 2 < m && rr == cc) ? L.wa[rr] * sm_ca(t + 2, t, nw) : 0.0;
-                }
-            __syncthreads();
-            // phase B, wave 0: Cholesky of S with lane = row, the row in registers, each column broadcast through v_readlane; the
-            // forward substitution of b in the same registers
-            if (wave == 0) {
-                double a[SK];
-                const int row = lane < SK ? lane : SK - 1;
-#pragma unroll
-                for (int c = 0; c < SK; ++c) a[c] = (lane < SK && c <= lane) ? L.S[row * SK + c] : (c == lane ? 1.0 : 0.0);
-                double bv = lane < SK ? bb[row] : 0.0;
-                int bad = 0;
-#pragma unroll
-                for (int j = 0; j < SK; ++j) {
-                    const double piv = rl64(a[j], j);
-                    if (!(piv > 0.0 && piv < __longlong_as_double(0x7ff0000000000000LL))) bad = 1;
-                    const double rt = piv > 0.0 ? sqrt(piv) : 0.0;
-                    const double l = lane == j ? rt : a[j] / rt;
-                    a[j] = l;
-#pragma unroll
-                    for (int k = j + 1; k < SK; ++k) a[k] -= l * rl64(l, k);
-                }
-#pragma unroll
-                for (int j = 0; j < SK; ++j) {
-                    const double yj = rl64(bv / a[j], j);
-                    if (lane == j) bv = yj;
-                    if (lane > j) bv -= a[j] * yj;
-                }
-                if (lane < SK) {
-#pragma unroll
-                    for (int c = 0; c < SK; ++c)
-                        if (c <= lane) L.S[lane * SK + c] = a[c];
-                    bb[lane] = bv;
-                    wt[W_Y + lane] = bv;
-                }
-                if (bad && lane == 0) L.fail = 1;
-            }
-            __syncthreads();
-            // phase C: N1 <- N1 L^-T on wave 0, N2 <- N2 L^-T on wave 1 (a row per lane in registers, L read as an LDS broadcast);
-            // waves 2 and 3 write L_tt to the factor
-            if (wave < 2 && r + 1 < m && (wave == 0 || r + 2 < m)) {
-                double* Nw = wave == 0 ? N1 : N2;
-                const int row = lane < SK ? lane : SK - 1;
-                double v[SK];
-#pragma unroll
-                for (int c = 0; c < SK; ++c) v[c] = Nw[row * SK + c];
-#pragma unroll
-                for (int c = 0; c < SK; ++c) {
-                    double s = v[c];
-#pragma unroll
-                    for (int q = 0; q < c; ++q) s -= v[q] * L.S[c * SK + q];
-                    v[c] = s / L.S[c * SK + c];
-                }
-                if (lane < SK) {
-#pragma unroll
-                    for (int c = 0; c < SK; ++c) Nw[lane * SK + c] = v[c];
-                }
-            } else if (wave >= 2) {
-                for (int i = tid - 128; i < SKH; i += 128) {
-                    int rr = 0;
-                    while ((rr + 1) * (rr + 2) / 2 <= i) ++rr;
-                    wt[i] = L.S[rr * SK + (i - rr * (rr + 1) / 2)];
-                }
-            }
-            __syncthreads();
-            // the factor's off-diagonal blocks to the workspace (read only from here on), and the roles rotate by index
-            for (int i = tid; i < SK2; i += SW_THREADS) {
-                wt[W_L1 + i] = N1[i];
-                wt[W_L2 + i] = N2[i];
-            }
-            const int oP1 = iP1, oP2 = iP2, oy2 = iy2;
-            iP2 = iQ; iP1 = iN1; iQ = iN2; iN1 = oP1; iN2 = oP2;
-            iy2 = iy1; iy1 = ib; ib = oy2;
-        }
-        __syncthreads();
-        // ---- back substitution on wave 0, no barrier: L^T d = y; lane = column of L_tt in registers, d broadcast by v_readlane ----
-        if (wave == 0) {
-            double d1 = 0.0, d2 = 0.0;
-            const int col = lane < SK ? lane : SK - 1;
-            for (int r = m - 1; r >= 0; --r) {
-                const double* wt = factor_of(r);
-                double bv = wt[W_Y + col];
-                if (r + 1 < m) {
-                    double s1 = 0.0;
-#pragma unroll
-                    for (int q = 0; q < SK; ++q) s1 += wt[W_L1 + q * SK + col] * rl64(d1, q);
-                    bv -= s1;
-                }
-                if (r + 2 < m) {
-                    double s2 = 0.0;
-#pragma unroll
-                    for (int q = 0; q < SK; ++q) s2 += wt[W_L2 + q * SK + col] * rl64(d2, q);
-                    bv -= s2;
-                }
-                double c[SK];
-#pragma unroll
-                for (int j = 0; j < SK; ++j) c[j] = j >= col ? wt[sm_lo(j, col)] : 1.0;
-#pragma unroll
-                for (int j = SK - 1; j >= 0; --j) {
-                    const double dj = rl64(bv / c[j], j);
-                    if (lane == j) bv = dj;
-                    if (lane < j) bv -= c[j] * dj;
-                }
-                d2 = d1;
-                d1 = lane < SK ? bv : 0.0;
-                if (lane < SK) factor_of(r)[W_Y + lane] = bv;
-            }
-        }
-        __syncthreads();
-        // ---- predicted reduction (-d.g + mu d^T diag(A) d) / 2, |d|_inf; then the trial point ----
-        double sg = 0.0, sd = 0.0, dm = 0.0;
-        for (int i = tid; i < m * SK; i += SW_THREADS) {
-            const int r = i / SK, q = i - r * SK;
-            const double* wt = factor_of(r);
-            const double dd = wt[W_Y + q];
-            sg += dd * wt[W_G + q];
-            sd += dd * dd * wt[W_D + q];
-            dm = fmax(dm, fabs(dd));
-        }
-        L.red[tid] = sg;
-        L.red2[tid] = sd;
-        L.red3[tid] = dm;
-        __syncthreads();
-        for (int w = SW_THREADS / 2; w >= 1; w >>= 1) {
-            if (tid < w) {
-                L.red[tid] += L.red[tid + w];
-                L.red2[tid] += L.red2[tid + w];
-                L.red3[tid] = fmax(L.red3[tid], L.red3[tid + w]);
-            }
-            __syncthreads();
-        }
-        const double E = Ed + Ep;
-        const double pred = 0.5 * (-L.red[0] + mu * L.red2[0]);
-        const double dmax = L.red3[0];
-        const int fail = L.fail;
-        __syncthreads();
-        if (fail || !(dmax == dmax) || dmax == __longlong_as_double(0x7ff0000000000000LL)) { why = 5; break; }
+        const SmStep st = sm_sweep(L, blocks_of(0, cur), SW_PER_ROW, fac, SW_PER_ROW, x, m, h, nw, mu);
+        const double E = Ed + Ep, pred = st.pred, dmax = st.dmax;
+        if (st.fail || !(dmax == dmax) || dmax == __longlong_as_double(0x7ff0000000000000LL)) { why = 5; break; }
         if (dmax < xtol) { why = 2; break; }
         if (pred < ftol * E) { why = 3; break; }
-        for (int i = tid; i < m * SK; i += SW_THREADS) {
+        for (int i = tid; i < m * SK; i += SM_THREADS) {
             const int r = i / SK, q = i - r * SK, at = (h + r) * 68 + L.colx[q];
-            xt[at] = x[at] + factor_of(r)[W_Y + q];
+            xt[at] = x[at] + fac[(size_t)r * SW_PER_ROW + W_Y + q];
         }
         eval_blocks(xt, 1 - cur);
-        sweep_tables();
-        const double Etd = data_energy(1 - cur), Etp = sw_prior_energy(L.wv, L.wa, L.colx, L.red, xt, nw, h);
+        sm_sweep_tables(L, T, root_vel, root_acc, ang_vel, ang_acc);   // (the blocks phase overwrote them)
+        const double Etd = sm_data_energy(L, blocks_of(0, 1 - cur), SW_PER_ROW, m), Etp = sm_prior_energy(L, xt, nw, h);
         const double Et = Etd + Etp;
         const bool acc = Et < E;
         if (tid == 0) inf[8 + trials] = acc ? 1.0 : 0.0;
         ++trials;
         if (acc) {
-            for (int i = tid; i < nw * 68; i += SW_THREADS) x[i] = xt[i];
+            for (int i = tid; i < nw * 68; i += SM_THREADS) x[i] = xt[i];
             cur = 1 - cur;
             mu /= 10.0;
             ++n_acc;
@@ -385,14 +138,14 @@ __global__ void __launch_bounds__(SW_THREADS) smooth_window_kernel(
             __syncthreads();
             if (E - Et < ftol * E) { why = 4; break; }
         } else {
-            for (int i = tid; i < nw * 68; i += SW_THREADS) xt[i] = x[i];
+            for (int i = tid; i < nw * 68; i += SM_THREADS) xt[i] = x[i];
             mu *= 10.0;
             __syncthreads();
         }
     }
     __syncthreads();
     // the free rows back into the ring
-    for (int i = tid; i < m * 68; i += SW_THREADS) {
+    for (int i = tid; i < m * 68; i += SM_THREADS) {
         const int r = i / 68, c = i - r * 68;
         ring[((lo + h + r) % SW_RING) * 68 + c] = x[(h + r) * 68 + c];
     }
@@ -422,7 +175,7 @@ extern "C" int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* k
     if (work_doubles < mvmc_smooth_window_work_doubles(n_items, window)) return MVMC_ERR_ARG;
     Ik1Tables T;
     if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(smooth_window_kernel, dim3(n_items), dim3(SW_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max,
+    hipLaunchKernelGGL(smooth_window_kernel, dim3(n_items), dim3(SM_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max,
                        n_rigs, items, new_params, new_members, n_new, rows, members, count, n_slots, window, n_iter, root_vel, root_acc,
                        ang_vel, ang_acc, mu0, ftol, xtol, info, work, n_items * window);
     MVMC_CHECK_LAUNCH();
