@@ -679,6 +679,48 @@ int mvmc_lens_undistort(const void* kps_in, int dtype, int n_frames, int n_views
 int mvmc_lens_distort(const void* kps_in, int dtype, int n_frames, int n_views, int n_points, const double* lens,
                       const int32_t* rig_of_frame, int n_rigs, void* kps_out, int32_t* dropped, mvmcStream_t stream);
 
+/* ---- calibration of every sequence's rig from one person walking the volume (multiview_motion_capture_amd/rig_init.py; restated in
+ * tests/rig_init_np.py).  No counterpart in the reference.  The relative pose of every camera pair from two-view geometry; the pose
+ * graph, the bundle adjustment (mvmc_rig_*) and the metric scale follow on the host side.  Sequences of any frame and camera counts
+ * share every launch; one wave per pair (or per pair and hypothesis), sums in a fixed order, no atomics: a pair's numbers depend on
+ * nothing else in the launch.
+ *   xn (n_rows,17,2) f64: the normalised coordinates K^-1 (u, v, 1) of the ONE pose of a (frame, view), NaN where the joint is not
+ *     usable (no or several poses in the view, score too low); the row of (sequence s, frame f, view c) is seq[s][0] + f C_s + c
+ *   seq (S,4) i32: first row, frames F_s, cameras C_s, 0;  pair (Q,4) i32: sequence, a, b (a != b), first frame slot: the pair owns
+ *     the F_s frame slots from there of mom, cnt and usable, and 17 times as many correspondence slots (frame f, joint j at f 17 + j)
+ *     of mask and points.  A pair row that does not fit n_rows / n_slots / its sequence is skipped.
+ * mvmc_pair_moments -> norm (Q,MVMC_RIGINIT_NORM_DOUBLES) f64: centroid x, y and scale (mean distance -> sqrt 2) of side a, of side
+ *   b, the number of correspondences, 0;  mom (n_slots,45) f64: per frame the upper triangle (row-major) of sum r r^T over its common
+ *   joints in joint order, r = (ub ua, ub va, ub, vb ua, vb va, vb, ua, va, 1) in Hartley-normalised coordinates: the row of
+ *   x_b^T E x_a = 0, E row-major;  cnt (n_slots) i32 the frame's common joints;  usable (n_slots) i32: the pair's frames with
+ *   cnt >= 1 in frame order, then -1;  n_usable (Q) i32.
+ * mvmc_pair_consensus: hypothesis h of a pair sums mom over the sample_frames frames usable[floor(u[h][k] n_usable)] (u (H,m) f64 in
+ *   [0, 1), duplicates allowed, summed in k order), takes the eigenvector of the smallest eigenvalue (cyclic Jacobi, fixed sweeps),
+ *   E = T_b^T Ehat T_a scaled to Frobenius norm 1 -> E (Q,H,9) f64, and count (Q,H) i32: the correspondences with Sampson distance
+ *   < thr[q] (thr (Q) f64).  A pair with n_usable < sample_frames: E = 0, count = 0.
+ * mvmc_pair_refit: the hypothesis with the largest count (ties: lowest index) is round 0; every round: the moment matrix over the
+ *   inliers of the current E, its null vector, denormalised and projected onto the essential matrices (singular values 1, 1, 0);
+ *   the refit round with the most inliers (ties: the earliest) -- round 0 when there is no refit round or the best one has fewer than
+ *   9/10 of round 0's inliers (a collapsed refit) -- is decomposed: t = +-u2, first the sign that makes its largest component
+ *   positive; R = U W V^T and U W^T V^T, the larger trace first; candidates (R0,t), (R0,-t), (R1,t), (R1,-t); the inliers are
+ *   triangulated with mvmc_dlt's arithmetic for [I|0], [R|t]; the candidate with the most points in front of both cameras wins (ties:
+ *   lowest index) -> pose (Q,MVMC_RIGINIT_POSE_DOUBLES) f64: R (9), t (3, unit), E (9), the hypothesis, the round, the inliers, the
+ *   four votes, the candidate, 0 0 0;  round_count (Q,MVMC_RIGINIT_MAX_ROUNDS+1) i32, -1 for rounds not made;  mask (n_slots 17) i32;
+ *   points (n_slots 17,3) f64 in camera a's frame, NaN where not an inlier.  A pair without a hypothesis with an inlier: all zero.
+ * Argument errors return MVMC_ERR_ARG before any HIP call. ---- */
+#define MVMC_RIGINIT_NORM_DOUBLES 8
+#define MVMC_RIGINIT_POSE_DOUBLES 32
+#define MVMC_RIGINIT_MAX_ROUNDS 8
+#define MVMC_RIGINIT_MAX_SAMPLE 32
+int mvmc_pair_moments(const double* xn, const int32_t* seq, const int32_t* pair, int n_seqs, int n_pairs, int n_rows, int n_slots,
+                      double* norm, double* mom, int32_t* cnt, int32_t* usable, int32_t* n_usable, mvmcStream_t stream);
+int mvmc_pair_consensus(const double* xn, const int32_t* seq, const int32_t* pair, int n_seqs, int n_pairs, int n_rows, int n_slots,
+                        const double* norm, const double* mom, const int32_t* usable, const int32_t* n_usable, const double* u,
+                        const double* thr, int n_hyp, int sample_frames, double* E, int32_t* count, mvmcStream_t stream);
+int mvmc_pair_refit(const double* xn, const int32_t* seq, const int32_t* pair, int n_seqs, int n_pairs, int n_rows, int n_slots,
+                    const double* norm, const double* E, const int32_t* count, const double* thr, int n_hyp, int refit_rounds,
+                    double* pose, int32_t* round_count, int32_t* mask, double* points, mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

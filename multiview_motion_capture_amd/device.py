@@ -681,6 +681,71 @@ def rig_step(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: tor
           "mvmc_rig_step")
 
 
+def _pair_req(xn, seq, pair):
+    _req(xn, torch.float64, "xn", (None, 17, 2))
+    _req(seq, torch.int32, "seq", (None, 4))
+    _req(pair, torch.int32, "pair", (None, 4))
+    return int(seq.shape[0]), int(pair.shape[0]), int(xn.shape[0])
+
+
+def pair_moments(xn: torch.Tensor, seq: torch.Tensor, pair: torch.Tensor, n_slots: int):
+    """Rig calibration, per camera pair (include/mvmc.h: mvmc_pair_moments).  xn (rows,17,2) normalised coordinates, NaN = not usable;
+    seq (S,4) i32 first row, frames, cameras, 0; pair (Q,4) i32 sequence, a, b, first frame slot; n_slots: frame slots of all pairs
+    -> norm (Q,8), mom (n_slots,45), cnt (n_slots,) i32, usable (n_slots,) i32, n_usable (Q,) i32."""
+    S, Q, R = _pair_req(xn, seq, pair)
+    n_slots = int(n_slots)
+    d = xn.device
+    norm = torch.zeros((Q, _cabi.RIGINIT_NORM_DOUBLES), dtype=torch.float64, device=d)
+    mom = torch.zeros((n_slots, 45), dtype=torch.float64, device=d)
+    cnt = torch.zeros((n_slots,), dtype=torch.int32, device=d)
+    usable = torch.full((n_slots,), -1, dtype=torch.int32, device=d)
+    n_usable = torch.zeros((Q,), dtype=torch.int32, device=d)
+    check(_cabi.load().mvmc_pair_moments(_p(xn), _p(seq), _p(pair), S, Q, R, n_slots, _p(norm), _p(mom), _p(cnt), _p(usable),
+                                         _p(n_usable), _stream()), "mvmc_pair_moments")
+    return norm, mom, cnt, usable, n_usable
+
+
+def pair_consensus(xn: torch.Tensor, seq: torch.Tensor, pair: torch.Tensor, norm: torch.Tensor, mom: torch.Tensor, usable: torch.Tensor,
+                   n_usable: torch.Tensor, u: torch.Tensor, thr: torch.Tensor):
+    """The hypotheses of every pair (include/mvmc.h: mvmc_pair_consensus).  u (H,m) f64 in [0, 1): the frame samples; thr (Q,) f64 the
+    Sampson thresholds -> E (Q,H,9) f64, count (Q,H) i32."""
+    S, Q, R = _pair_req(xn, seq, pair)
+    n_slots = int(mom.shape[0])
+    _req(norm, torch.float64, "norm", (Q, _cabi.RIGINIT_NORM_DOUBLES))
+    _req(mom, torch.float64, "mom", (n_slots, 45))
+    _req(usable, torch.int32, "usable", (n_slots,))
+    _req(n_usable, torch.int32, "n_usable", (Q,))
+    _req(u, torch.float64, "u", (None, None))
+    _req(thr, torch.float64, "thr", (Q,))
+    H, m = int(u.shape[0]), int(u.shape[1])
+    E = torch.zeros((Q, H, 9), dtype=torch.float64, device=xn.device)
+    count = torch.zeros((Q, H), dtype=torch.int32, device=xn.device)
+    check(_cabi.load().mvmc_pair_consensus(_p(xn), _p(seq), _p(pair), S, Q, R, n_slots, _p(norm), _p(mom), _p(usable), _p(n_usable),
+                                           _p(u), _p(thr), H, m, _p(E), _p(count), _stream()), "mvmc_pair_consensus")
+    return E, count
+
+
+def pair_refit(xn: torch.Tensor, seq: torch.Tensor, pair: torch.Tensor, n_slots: int, norm: torch.Tensor, E: torch.Tensor,
+               count: torch.Tensor, thr: torch.Tensor, refit_rounds: int):
+    """The pose of every pair from its best hypothesis (include/mvmc.h: mvmc_pair_refit) -> pose (Q,32) f64, round_count (Q,9) i32,
+    mask (n_slots 17,) i32, points (n_slots 17, 3) f64 in the frame of the pair's first camera (NaN: not an inlier)."""
+    S, Q, R = _pair_req(xn, seq, pair)
+    n_slots = int(n_slots)
+    _req(norm, torch.float64, "norm", (Q, _cabi.RIGINIT_NORM_DOUBLES))
+    _req(E, torch.float64, "E", (Q, None, 9))
+    H = int(E.shape[1])
+    _req(count, torch.int32, "count", (Q, H))
+    _req(thr, torch.float64, "thr", (Q,))
+    d = xn.device
+    pose = torch.zeros((Q, _cabi.RIGINIT_POSE_DOUBLES), dtype=torch.float64, device=d)
+    rounds = torch.zeros((Q, _cabi.RIGINIT_MAX_ROUNDS + 1), dtype=torch.int32, device=d)
+    mask = torch.zeros((n_slots * 17,), dtype=torch.int32, device=d)
+    pts = torch.full((n_slots * 17, 3), float("nan"), dtype=torch.float64, device=d)
+    check(_cabi.load().mvmc_pair_refit(_p(xn), _p(seq), _p(pair), S, Q, R, n_slots, _p(norm), _p(E), _p(count), _p(thr), H,
+                                       int(refit_rounds), _p(pose), _p(rounds), _p(mask), _p(pts), _stream()), "mvmc_pair_refit")
+    return pose, rounds, mask, pts
+
+
 def _lens_call(name: str, kps: torch.Tensor, lens: torch.Tensor, rig_of_frame, out: Optional[torch.Tensor]):
     if not isinstance(kps, torch.Tensor) or kps.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"{name}: kps must be a float32 or float64 tensor")

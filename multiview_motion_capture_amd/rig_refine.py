@@ -134,6 +134,67 @@ def _moved(Rt_in, Rt_out):
     return out
 
 
+def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, t0):
+    """Steps b - e on the candidates of a group of S sequences of C cameras: what refine_rigs does after its selection, and what
+    rig_init.calibrate_rigs polishes with.  obs_d (n,C,3) f64 device: u, v, score per candidate and camera (None: no candidate);
+    rig_c (n,) i32 device: the candidate's sequence; Pm_d (S,C,3,4) device; Kin (S,C,3,3), Rtin (S,C,3,4) host; lap(key, t0) -> t1 the
+    caller's stopwatch ("start", "trials").  -> dict: the host gates' arrays (dist, seq_of, obs, held, is_pt, n_pts, n_obs, run), the
+    one read-back (cams_h (S,C,21), info_h, ctl_h), the device's start values X0_d and final points X_d with dev_pt (their candidates),
+    and t0."""
+    import torch
+
+    from . import _cabi
+    from . import device as dev
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+    n_cand = 0 if obs_d is None else int(obs_d.shape[0])
+    X0_d = None
+    if n_cand:
+        # the points and distances stay on the device; the host gates on the distances alone
+        X0_d, dist_d = dev.rig_start(obs_d, rig_c, Pm_d, float(min_score))
+        dist, seq_of = dist_d.cpu().numpy(), rig_c.cpu().numpy().astype(np.int64)
+        x_ok = torch.isfinite(X0_d[:, :3]).all(dim=1).cpu().numpy()
+    else:
+        dist, seq_of, x_ok = np.zeros((0, C)), np.zeros((0,), np.int64), np.zeros((0,), bool)
+    obs, held, stop0 = pack_problems(~np.isnan(dist), dist, x_ok, seq_of, S, float(max_px), int(min_views), int(min_cam_obs))
+    is_pt = obs.any(axis=1)
+    n_pts = np.bincount(seq_of[is_pt], minlength=S)
+    n_obs = _per_camera(seq_of, obs, S)
+    run = stop0 == 0
+    dev_pt = is_pt & run[seq_of]                                            # points of the sequences that are solved
+    tile, seq = tile_tables(np.where(run, n_pts, 0))
+    slot = np.where(held, -1, np.cumsum(~held, axis=1) - 1).astype(np.int32)
+    cams = np.concatenate([Kin.reshape(S, C, 9), Rtin[:, :, :, :3].reshape(S, C, 9), Rtin[:, :, :, 3]], axis=2)
+    info = np.zeros((S, _cabi.RIG_INFO_DOUBLES))
+    info[:, 8:8 + MAX_ITER_CAP] = -1.0
+    ctl = np.zeros((S, 4), np.int32)
+    ctl[:, 0] = stop0
+    if n_cand:
+        pt_d = T(dev_pt)
+        X_d = X0_d[pt_d][:, :3].contiguous()
+        uv_d = torch.where(T(obs[dev_pt])[:, :, None], obs_d[pt_d][:, :, :2], torch.full((), float("nan"), dtype=torch.float64, device=d))
+        uv_d = uv_d.contiguous()
+    else:
+        X_d, uv_d = torch.zeros((0, 3), dtype=torch.float64, device=d), torch.zeros((0, C, 2), dtype=torch.float64, device=d)
+    t0 = lap("start", t0)
+    Xt_d = X_d.clone()
+    tile_d, seq_d, slot_d, cams_d, info_d, ctl_d = T(tile), T(seq), T(slot), T(cams), T(info), T(ctl)
+    camt_d = cams_d.clone()
+    part, part2, red = dev.rig_work(tile.shape[0], S, C, d)
+    if run.any():
+        for _ in range(max(int(max_iter), 1)):
+            dev.rig_accumulate(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant)
+            if int(max_iter):
+                dev.rig_step(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, LM_FTOL, LM_XTOL,
+                             part2)
+    t0 = lap("trials", t0)
+    back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()]).cpu().numpy()   # the one read-back
+    cams_h = back[:S * C * 21].reshape(S, C, 21)
+    info_h = back[S * C * 21:S * C * 21 + info.size].reshape(S, -1)
+    ctl_h = back[S * C * 21 + info.size:].reshape(S, 4).astype(np.int64)
+    return dict(t0=t0, dist=dist, seq_of=seq_of, obs=obs, held=held, is_pt=is_pt, n_pts=n_pts, n_obs=n_obs, run=run, cams_h=cams_h,
+                info_h=info_h, ctl_h=ctl_h, X0_d=X0_d, X_d=X_d, dev_pt=dev_pt)
+
+
 def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], max_iter: int = 10,
                 max_px: float = body_fit.MAX_DIST, min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100,
                 frame_step: int = 1, device="cuda:0", timings: Optional[dict] = None, variant: int = 1,
@@ -212,49 +273,11 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
             rig_c = T(np.repeat(rig_of[take], 17))[is_cand].contiguous()
             n_cand = int(obs_d.shape[0])
         t0 = lap("select", t0)
-        if n_cand:
-            # the points and distances stay on the device; the host gates on the distances alone
-            X0_d, dist_d = dev.rig_start(obs_d, rig_c, Pm_d, float(min_score))
-            dist, seq_of = dist_d.cpu().numpy(), rig_c.cpu().numpy().astype(np.int64)
-            x_ok = torch.isfinite(X0_d[:, :3]).all(dim=1).cpu().numpy()
-        else:
-            dist, seq_of, x_ok = np.zeros((0, C)), np.zeros((0,), np.int64), np.zeros((0,), bool)
-        obs, held, stop0 = pack_problems(~np.isnan(dist), dist, x_ok, seq_of, S, float(max_px), int(min_views), int(min_cam_obs))
-        is_pt = obs.any(axis=1)
-        n_pts = np.bincount(seq_of[is_pt], minlength=S)
-        n_obs = _per_camera(seq_of, obs, S)
-        run = stop0 == 0
-        dev_pt = is_pt & run[seq_of]                                            # points of the sequences that are solved
-        tile, seq = tile_tables(np.where(run, n_pts, 0))
-        slot = np.where(held, -1, np.cumsum(~held, axis=1) - 1).astype(np.int32)
-        cams = np.concatenate([Kin.reshape(S, C, 9), Rtin[:, :, :, :3].reshape(S, C, 9), Rtin[:, :, :, 3]], axis=2)
-        info = np.zeros((S, _cabi.RIG_INFO_DOUBLES))
-        info[:, 8:8 + MAX_ITER_CAP] = -1.0
-        ctl = np.zeros((S, 4), np.int32)
-        ctl[:, 0] = stop0
-        if n_cand:
-            pt_d = T(dev_pt)
-            X_d = X0_d[pt_d][:, :3].contiguous()
-            uv_d = torch.where(T(obs[dev_pt])[:, :, None], obs_d[pt_d][:, :, :2], torch.full((), float("nan"), dtype=torch.float64, device=d))
-            uv_d = uv_d.contiguous()
-        else:
-            X_d, uv_d = torch.zeros((0, 3), dtype=torch.float64, device=d), torch.zeros((0, C, 2), dtype=torch.float64, device=d)
-        t0 = lap("start", t0)
-        Xt_d = X_d.clone()
-        tile_d, seq_d, slot_d, cams_d, info_d, ctl_d = T(tile), T(seq), T(slot), T(cams), T(info), T(ctl)
-        camt_d = cams_d.clone()
-        part, part2, red = dev.rig_work(tile.shape[0], S, C, d)
-        if run.any():
-            for _ in range(max(int(max_iter), 1)):
-                dev.rig_accumulate(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant)
-                if int(max_iter):
-                    dev.rig_step(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, LM_FTOL, LM_XTOL,
-                                 part2)
-        t0 = lap("trials", t0)
-        back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()]).cpu().numpy()   # the one read-back
-        cams_h = back[:S * C * 21].reshape(S, C, 21)
-        info_h = back[S * C * 21:S * C * 21 + info.size].reshape(S, -1)
-        ctl_h = back[S * C * 21 + info.size:].reshape(S, 4).astype(np.int64)
+        g = solve_group(obs_d if n_cand else None, rig_c if n_cand else None, Pm_d if n_cand else None, Kin, Rtin, S, C, d, max_iter,
+                        max_px, min_score, min_views, min_cam_obs, variant, lap, t0)
+        t0, dist, seq_of, obs, held, is_pt, n_pts, n_obs, run = (g[k] for k in ("t0", "dist", "seq_of", "obs", "held", "is_pt", "n_pts",
+                                                                                "n_obs", "run"))
+        cams_h, info_h, ctl_h, X0_d = g["cams_h"], g["info_h"], g["ctl_h"], g["X0_d"]
         if problems is not None and n_cand:
             cand, X0 = obs_d.cpu().numpy(), X0_d.cpu().numpy()
         for r, i in enumerate(ids):
