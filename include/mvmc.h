@@ -640,6 +640,30 @@ int mvmc_rig_accumulate(const double* X, const double* uv, const int32_t* tile, 
 int mvmc_rig_step(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
                   double* cams, const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points, int n_tiles,
                   int n_seqs, int n_views, int max_iter, double ftol, double xtol, double* part2, mvmcStream_t stream);
+/* The same two halves of a trial with a robust loss (restated in tests/rig_robust_np.py).  For an observation with plain residual
+ * (ru, rv): s^2 = ru^2 + rv^2, delta = loss_px > 0,
+ *   MVMC_RIG_LOSS_HUBER   rho = 1/2 s^2, w = 1 for s <= delta; otherwise rho = delta (s - 1/2 delta), w = delta / s
+ *   MVMC_RIG_LOSS_CAUCHY  rho = 1/2 delta^2 log1p(s^2 / delta^2), w = 1 / (1 + s^2 / delta^2)
+ * E = sum rho replaces 1/2 sum r^2 wherever a cost is read or written (info, the decision); at every linearisation the observation's
+ * Jacobian rows and residual are multiplied by sqrt(w) (iteratively reweighted, no second-order correction), and the step and its
+ * predicted reduction are those of the weighted model.  Every buffer, layout and precondition is that of the entries above; the
+ * iteration converges linearly, so ftol and xtol are the caller's to choose.  MVMC_RIG_LOSS_NONE runs the code of the entries above
+ * (loss_px is not read); a loss outside these three, or with a loss a loss_px that is not a finite number > 0: MVMC_ERR_ARG.
+ * mvmc_rig_weights: w (N,C) f64 out, the weight of every observation at (X, cams) -- 1 with MVMC_RIG_LOSS_NONE -- and NaN where the
+ * camera does not observe the point; rows of points outside every tile are not written. */
+#define MVMC_RIG_LOSS_NONE 0
+#define MVMC_RIG_LOSS_HUBER 1
+#define MVMC_RIG_LOSS_CAUCHY 2
+int mvmc_rig_accumulate_robust(const double* X, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                               const double* cams, double* cams_trial, int32_t* ctl, double* info, int n_points, int n_tiles, int n_seqs,
+                               int n_views, int max_iter, double mu0, int variant, double* part, double* red, int loss, double loss_px,
+                               mvmcStream_t stream);
+int mvmc_rig_step_robust(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                         double* cams, const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points,
+                         int n_tiles, int n_seqs, int n_views, int max_iter, double ftol, double xtol, double* part2, int loss,
+                         double loss_px, mvmcStream_t stream);
+int mvmc_rig_weights(const double* X, const double* uv, const int32_t* tile, const double* cams, int n_points, int n_tiles, int n_seqs,
+                     int n_views, int loss, double loss_px, double* w, mvmcStream_t stream);
 
 /* ---- lens distortion at the door of the pipeline (multiview_motion_capture_amd/lens.py; restated in tests/lens_np.py).  No counterpart
  * in the reference, whose only projection is project_3d_points_to_image_plane_without_distortion (mv_math_util.py).  Every other entry

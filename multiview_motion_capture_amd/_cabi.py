@@ -29,6 +29,7 @@ RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
 RIG_TILE, RIG_MAX_CAMS, RIG_MAX_ITER, RIG_CAM_DOUBLES, RIG_INFO_DOUBLES = 64, 8, 24, 21, 64
 LENS_DOUBLES, LENS_PINHOLE, LENS_BROWN, LENS_FISHEYE, LENS_MAX_ITER, LENS_FISHEYE_MAX_THETA = 16, 0, 1, 2, 12, 1.5
 RIGINIT_NORM_DOUBLES, RIGINIT_POSE_DOUBLES, RIGINIT_MAX_ROUNDS, RIGINIT_MAX_SAMPLE = 8, 32, 8, 32
+RIG_LOSS_NONE, RIG_LOSS_HUBER, RIG_LOSS_CAUCHY = 0, 1, 2                                              # MVMC_RIG_LOSS_*
 RIG_STOP = {0: "running", 1: "xtol", 2: "ftol", 3: "few_cameras", 4: "few_points", 5: "max_iter"}    # MVMC_RIG_STOP_*
 
 # every symbol declared in include/mvmc.h
@@ -40,6 +41,7 @@ SYMBOLS = (
     "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
+    "mvmc_rig_accumulate_robust", "mvmc_rig_step_robust", "mvmc_rig_weights",
     "mvmc_lens_undistort", "mvmc_lens_distort",
     "mvmc_pair_moments", "mvmc_pair_consensus", "mvmc_pair_refit",
 )
@@ -158,6 +160,9 @@ def load():
         "mvmc_rig_start": [vp, vp, vp, i32, i32, i32, f64, vp, vp, vp],
         "mvmc_rig_accumulate": [vp] * 9 + [i32] * 5 + [f64, i32, vp, vp, vp],
         "mvmc_rig_step": [vp] * 11 + [i32] * 5 + [f64, f64, vp, vp],
+        "mvmc_rig_accumulate_robust": [vp] * 9 + [i32] * 5 + [f64, i32, vp, vp, i32, f64, vp],
+        "mvmc_rig_step_robust": [vp] * 11 + [i32] * 5 + [f64, f64, vp, i32, f64, vp],
+        "mvmc_rig_weights": [vp] * 4 + [i32] * 5 + [f64, vp, vp],
         "mvmc_lens_undistort": [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp],
         "mvmc_lens_distort": [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp],
         "mvmc_pair_moments": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],

@@ -11,6 +11,10 @@
 //   decide    one workgroup per sequence: accept / reject, the gauge rescale, mu, the stop rules.
 // The tiles of a sequence are cut from its own points, every sum has a fixed order and there are no atomics: a sequence's numbers
 // depend on nothing else in the launch.  A sequence that has stopped (ctl[0] != 0) idles.
+// Robust loss (the _robust entries; restated in tests/rig_robust_np.py): rg_obs, rg_point and the two tile kernels take the loss as a
+// compile-time parameter.  With a loss an observation's rows a, b, ju, jv and its residual are multiplied by sqrt(w) as the lane forms
+// them and the tile's E is the sum of rho; everything staged in LDS, part, red, the solve and the decision are what they are without
+// one.  LOSS = MVMC_RIG_LOSS_NONE is the arithmetic without a loss, operation for operation.
 #include "mvmc_common.h"
 #include "mvmc_dlt_point.h"
 
@@ -41,8 +45,10 @@ __device__ __forceinline__ int rg_q7(int i, int j) { return i * 7 - i * (i - 1) 
 __device__ __forceinline__ double rg_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // one observation: residual, the point rows a, b of the Jacobian (R^T du, R^T dv), and y = R X, du, dv for the camera rows
-struct RgObs { double ru, rv, a[3], b[3], y[3], du[3], dv[3]; };
-__device__ __forceinline__ void rg_obs(const double* __restrict__ cam, const double* X, double ou, double ov, RgObs& o) {
+// with a loss: rho of the plain residual, and ru, rv, a, b, du, dv (so ju, jv) times sqrt(w)
+struct RgObs { double ru, rv, a[3], b[3], y[3], du[3], dv[3], rho; };
+template <int LOSS>
+__device__ __forceinline__ void rg_obs(const double* __restrict__ cam, const double* X, double ou, double ov, double delta, RgObs& o) {
     const double* K = cam;
     const double* R = cam + 9;
     const double* t = cam + 18;
@@ -55,6 +61,22 @@ __device__ __forceinline__ void rg_obs(const double* __restrict__ cam, const dou
     o.ru = u - ou; o.rv = v - ov;
 #pragma unroll
     for (int k = 0; k < 3; ++k) { o.du[k] = (K[k] - u * K[6 + k]) / p[2]; o.dv[k] = (K[3 + k] - v * K[6 + k]) / p[2]; }
+    if constexpr (LOSS != MVMC_RIG_LOSS_NONE) {
+        const double s2 = o.ru * o.ru + o.rv * o.rv;
+        double sw;
+        if constexpr (LOSS == MVMC_RIG_LOSS_HUBER) {
+            const double s = sqrt(s2);
+            if (s <= delta) { o.rho = 0.5 * s2; sw = 1.0; }
+            else { o.rho = delta * (s - 0.5 * delta); sw = sqrt(delta / s); }
+        } else {
+            const double q = s2 / (delta * delta);
+            o.rho = 0.5 * delta * delta * log1p(q);
+            sw = sqrt(1.0 / (1.0 + q));
+        }
+        o.ru *= sw; o.rv *= sw;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { o.du[k] *= sw; o.dv[k] *= sw; }
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         o.a[k] = R[k] * o.du[0] + R[3 + k] * o.du[1] + R[6 + k] * o.du[2];
@@ -69,10 +91,12 @@ __device__ __forceinline__ void rg_cam_rows(const RgObs& o, double* ju, double* 
     for (int k = 0; k < 3; ++k) { ju[3 + k] = o.du[k]; jv[3 + k] = o.dv[k]; }
 }
 
-// the point's block at (X, cams): V (upper, 6), g_p, sum r^2; then V* = V + mu diag V = L L^T.  l = {l00, l10, l11, l20, l21, l22}
+// the point's block at (X, cams): V (upper, 6), g_p, sum r^2 (with a loss: sum rho); then V* = V + mu diag V = L L^T.
+// l = {l00, l10, l11, l20, l21, l22}
 struct RgPoint { double V[6], g[3], rr, l[6]; };
+template <int LOSS>
 __device__ __forceinline__ void rg_point(const double* __restrict__ cams, const double* __restrict__ uvp, int C, const double* X, double mu,
-                                         RgPoint& P) {
+                                         double delta, RgPoint& P) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) P.V[k] = 0.0;
     P.g[0] = P.g[1] = P.g[2] = 0.0;
@@ -81,12 +105,13 @@ __device__ __forceinline__ void rg_point(const double* __restrict__ cams, const 
         const double ou = uvp[2 * c], ov = uvp[2 * c + 1];
         if (!(ou == ou)) continue;
         RgObs o;
-        rg_obs(cams + c * RG_CAM, X, ou, ov, o);
+        rg_obs<LOSS>(cams + c * RG_CAM, X, ou, ov, delta, o);
         P.V[0] += o.a[0] * o.a[0] + o.b[0] * o.b[0]; P.V[1] += o.a[0] * o.a[1] + o.b[0] * o.b[1]; P.V[2] += o.a[0] * o.a[2] + o.b[0] * o.b[2];
         P.V[3] += o.a[1] * o.a[1] + o.b[1] * o.b[1]; P.V[4] += o.a[1] * o.a[2] + o.b[1] * o.b[2]; P.V[5] += o.a[2] * o.a[2] + o.b[2] * o.b[2];
 #pragma unroll
         for (int k = 0; k < 3; ++k) P.g[k] += o.a[k] * o.ru + o.b[k] * o.rv;
-        P.rr += o.ru * o.ru + o.rv * o.rv;
+        if constexpr (LOSS == MVMC_RIG_LOSS_NONE) P.rr += o.ru * o.ru + o.rv * o.rv;
+        else P.rr += o.rho;
     }
     const double v00 = P.V[0] + mu * P.V[0], v11 = P.V[3] + mu * P.V[3], v22 = P.V[5] + mu * P.V[5];
     P.l[0] = sqrt(v00);
@@ -142,13 +167,14 @@ __global__ void __launch_bounds__(256) rig_start_kernel(const double* __restrict
 
 // ---- the tile's part of the reduced system ----
 // part (PD per tile): the lower block triangle of [Y; z^T] [Y; z^T]^T in 16 x 16 blocks (block (bi, bj), bj <= bi, at bi (bi + 1) / 2
-// + bj, row-major), then per slot the 28 products of the rows (J_c; r) (upper triangle, rg_q7), then E = 1/2 sum r^2 of the tile.
-template <bool MFMA>
+// + bj, row-major), then per slot the 28 products of the rows (J_c; r) (upper triangle, rg_q7), then E = 1/2 sum r^2 of the tile
+// (with a loss: sum rho).
+template <bool MFMA, int LOSS>
 __global__ void __launch_bounds__(64) rig_accum_kernel(const double* __restrict__ X, const double* __restrict__ uv,
                                                        const int32_t* __restrict__ tile, const int32_t* __restrict__ slot,
                                                        const double* __restrict__ cams, const int32_t* __restrict__ ctl,
                                                        const double* __restrict__ info, int N, int S, int C, double mu0,
-                                                       double* __restrict__ part) {
+                                                       double delta, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) double rg_lds[];
     const RgDims D = rg_dims(C);
     double* sY = rg_lds;
@@ -169,7 +195,7 @@ __global__ void __launch_bounds__(64) rig_accum_kernel(const double* __restrict_
         const double Xp[3] = {X[(size_t)i * 3], X[(size_t)i * 3 + 1], X[(size_t)i * 3 + 2]};
         const double* uvp = uv + (size_t)i * C * 2;
         RgPoint P;
-        rg_point(cm, uvp, C, Xp, mu, P);
+        rg_point<LOSS>(cm, uvp, C, Xp, mu, delta, P);
         rr = P.rr;
         double z[3];
         rg_fwd(P.l, P.g, z);
@@ -179,7 +205,7 @@ __global__ void __launch_bounds__(64) rig_accum_kernel(const double* __restrict_
             const double ou = uvp[2 * c], ov = uvp[2 * c + 1];
             if (q < 0 || q >= D.nf || !(ou == ou)) continue;
             RgObs o;
-            rg_obs(cm + c * RG_CAM, Xp, ou, ov, o);
+            rg_obs<LOSS>(cm + c * RG_CAM, Xp, ou, ov, delta, o);
             double ju[6], jv[6];
             rg_cam_rows(o, ju, jv);
 #pragma unroll
@@ -230,7 +256,8 @@ __global__ void __launch_bounds__(64) rig_accum_kernel(const double* __restrict_
         for (int k = 0; k < 2 * RG_TILE; ++k) acc = fma(ra[k], rb[k], acc);
         out[D.nblk * 256 + e] = acc;
     }
-    const double E = 0.5 * wave_sum(rr);
+    double E = wave_sum(rr);
+    if constexpr (LOSS == MVMC_RIG_LOSS_NONE) E = 0.5 * E;
     if (lane == 0) out[D.nblk * 256 + 28 * D.nf] = E;
 }
 
@@ -397,11 +424,13 @@ __global__ void __launch_bounds__(256) rig_solve_kernel(const int32_t* __restric
 }
 
 // ---- the points' steps, the trial points and the trial cost.  part2 (4 per tile): E_trial, d_p . g_p, d_p^T diag(V) d_p, |d_p|_inf ----
+template <int LOSS>
 __global__ void __launch_bounds__(64) rig_backsub_kernel(const double* __restrict__ X, double* __restrict__ Xt, const double* __restrict__ uv,
                                                          const int32_t* __restrict__ tile, const int32_t* __restrict__ slot,
                                                          const double* __restrict__ cams, const double* __restrict__ camt,
                                                          const int32_t* __restrict__ ctl, const double* __restrict__ info,
-                                                         const double* __restrict__ red, int N, int S, int C, double* __restrict__ part2) {
+                                                         const double* __restrict__ red, int N, int S, int C, double delta,
+                                                         double* __restrict__ part2) {
     const RgDims D = rg_dims(C);
     const int lane = threadIdx.x & 63, tl = blockIdx.x;
     const int s = uni((int)tile[4 * tl]), lo = uni((int)tile[4 * tl + 1]), n = uni((int)tile[4 * tl + 2]);
@@ -418,14 +447,14 @@ __global__ void __launch_bounds__(64) rig_backsub_kernel(const double* __restric
         const double Xp[3] = {X[(size_t)i * 3], X[(size_t)i * 3 + 1], X[(size_t)i * 3 + 2]};
         const double* uvp = uv + (size_t)i * C * 2;
         RgPoint P;
-        rg_point(cm, uvp, C, Xp, mu, P);
+        rg_point<LOSS>(cm, uvp, C, Xp, mu, delta, P);
         double rhs[3] = {-P.g[0], -P.g[1], -P.g[2]};
         for (int c = 0; c < C; ++c) {
             const int q = sl[c];
             const double ou = uvp[2 * c], ov = uvp[2 * c + 1];
             if (q < 0 || q >= D.nf || !(ou == ou)) continue;
             RgObs o;
-            rg_obs(cm + c * RG_CAM, Xp, ou, ov, o);
+            rg_obs<LOSS>(cm + c * RG_CAM, Xp, ou, ov, delta, o);
             double ju[6], jv[6];
             rg_cam_rows(o, ju, jv);
             double su = 0.0, sv = 0.0;
@@ -445,11 +474,13 @@ __global__ void __launch_bounds__(64) rig_backsub_kernel(const double* __restric
             const double ou = uvp[2 * c], ov = uvp[2 * c + 1];
             if (!(ou == ou)) continue;
             RgObs o;
-            rg_obs(ct + c * RG_CAM, Xn, ou, ov, o);
-            Et += o.ru * o.ru + o.rv * o.rv;
+            rg_obs<LOSS>(ct + c * RG_CAM, Xn, ou, ov, delta, o);
+            if constexpr (LOSS == MVMC_RIG_LOSS_NONE) Et += o.ru * o.ru + o.rv * o.rv;
+            else Et += o.rho;
         }
     }
-    Et = 0.5 * wave_sum(Et);
+    Et = wave_sum(Et);
+    if constexpr (LOSS == MVMC_RIG_LOSS_NONE) Et = 0.5 * Et;
     dg = wave_sum(dg);
     dDd = wave_sum(dDd);
     dmax = wave_max_dpp(dmax);
@@ -544,6 +575,40 @@ __global__ void __launch_bounds__(256) rig_decide_kernel(double* __restrict__ X,
     }
 }
 
+// ---- the weights of the loss at (X, cams): w (N,C), NaN where the camera does not observe the point; points outside every tile are
+// not written ----
+template <int LOSS>
+__global__ void __launch_bounds__(64) rig_weights_kernel(const double* __restrict__ X, const double* __restrict__ uv,
+                                                         const int32_t* __restrict__ tile, const double* __restrict__ cams, int N, int S, int C,
+                                                         double delta, double* __restrict__ w) {
+    const int lane = threadIdx.x & 63, tl = blockIdx.x;
+    const int s = uni((int)tile[4 * tl]), lo = uni((int)tile[4 * tl + 1]), n = uni((int)tile[4 * tl + 2]);
+    if (s < 0 || s >= S || lo < 0 || n < 0 || n > RG_TILE || lo + n > N) return;
+    if (lane >= n) return;
+    const int i = lo + lane;
+    const double* cm = cams + (size_t)s * C * RG_CAM;
+    const double Xp[3] = {X[(size_t)i * 3], X[(size_t)i * 3 + 1], X[(size_t)i * 3 + 2]};
+    const double* uvp = uv + (size_t)i * C * 2;
+    for (int c = 0; c < C; ++c) {
+        const double ou = uvp[2 * c], ov = uvp[2 * c + 1];
+        double wc = rg_nan();
+        if (ou == ou) {
+            RgObs o;
+            rg_obs<MVMC_RIG_LOSS_NONE>(cm + c * RG_CAM, Xp, ou, ov, delta, o);
+            const double s2 = o.ru * o.ru + o.rv * o.rv;
+            if constexpr (LOSS == MVMC_RIG_LOSS_HUBER) {
+                const double sr = sqrt(s2);
+                wc = sr <= delta ? 1.0 : delta / sr;
+            } else if constexpr (LOSS == MVMC_RIG_LOSS_CAUCHY) {
+                wc = 1.0 / (1.0 + s2 / (delta * delta));
+            } else {
+                wc = 1.0;
+            }
+        }
+        w[(size_t)i * C + c] = wc;
+    }
+}
+
 size_t rg_accum_lds(int C) {
     const RgDims D = rg_dims(C);
     return ((size_t)D.Mp * RG_LD + (size_t)7 * D.nf * RG_LDJ) * sizeof(double);
@@ -551,6 +616,75 @@ size_t rg_accum_lds(int C) {
 size_t rg_solve_lds(int C) {
     const RgDims D = rg_dims(C);
     return ((size_t)D.PD + (size_t)D.M * D.M + 4 * D.M) * sizeof(double);
+}
+
+bool rg_loss_ok(int loss, double loss_px) {
+    if (loss < MVMC_RIG_LOSS_NONE || loss > MVMC_RIG_LOSS_CAUCHY) return false;
+    return loss == MVMC_RIG_LOSS_NONE || (loss_px > 0.0 && loss_px <= 1.7976931348623157e308);   // (NaN fails both)
+}
+
+template <bool MFMA, int LOSS>
+int rg_launch_accum(hipStream_t st, size_t la, int n_tiles, const double* X, const double* uv, const int32_t* tile, const int32_t* slot,
+                    const double* cams, const int32_t* ctl, const double* info, int n_points, int n_seqs, int n_views, double mu0,
+                    double delta, double* part) {
+    if (la > 65536 && hipFuncSetAttribute((const void*)rig_accum_kernel<MFMA, LOSS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)la) !=
+                          hipSuccess)
+        return MVMC_ERR_LAUNCH;
+    if (n_tiles > 0) {
+        hipLaunchKernelGGL((rig_accum_kernel<MFMA, LOSS>), dim3(n_tiles), dim3(64), la, st, X, uv, tile, slot, cams, ctl, info, n_points,
+                           n_seqs, n_views, mu0, delta, part);
+        MVMC_CHECK_LAUNCH();
+    }
+    return MVMC_OK;
+}
+
+int rg_accumulate(const double* X, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot, const double* cams,
+                  double* cams_trial, int32_t* ctl, double* info, int n_points, int n_tiles, int n_seqs, int n_views, int max_iter,
+                  double mu0, int variant, double* part, double* red, int loss, double loss_px, mvmcStream_t stream) {
+    if (n_points < 0 || n_tiles < 0 || n_seqs < 0 || n_views < 2 || n_views > MVMC_RIG_MAX_CAMS || max_iter < 0 ||
+        max_iter > MVMC_RIG_MAX_ITER || variant < 0 || variant > 1 || !rg_loss_ok(loss, loss_px))
+        return MVMC_ERR_ARG;
+    if (n_seqs == 0) return MVMC_OK;
+    if (!X || !uv || !tile || !seq || !slot || !cams || !cams_trial || !ctl || !info || !part || !red) return MVMC_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t la = rg_accum_lds(n_views), ls = rg_solve_lds(n_views);
+    if (ls > 65536 && hipFuncSetAttribute((const void*)rig_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls) != hipSuccess)
+        return MVMC_ERR_LAUNCH;
+    int rc;
+#define RG_ACCUM(MF, LS) rg_launch_accum<MF, LS>(st, la, n_tiles, X, uv, tile, slot, cams, ctl, info, n_points, n_seqs, n_views, mu0, loss_px, part)
+    if (loss == MVMC_RIG_LOSS_HUBER) rc = variant ? RG_ACCUM(true, MVMC_RIG_LOSS_HUBER) : RG_ACCUM(false, MVMC_RIG_LOSS_HUBER);
+    else if (loss == MVMC_RIG_LOSS_CAUCHY) rc = variant ? RG_ACCUM(true, MVMC_RIG_LOSS_CAUCHY) : RG_ACCUM(false, MVMC_RIG_LOSS_CAUCHY);
+    else rc = variant ? RG_ACCUM(true, MVMC_RIG_LOSS_NONE) : RG_ACCUM(false, MVMC_RIG_LOSS_NONE);
+#undef RG_ACCUM
+    if (rc != MVMC_OK) return rc;
+    hipLaunchKernelGGL(rig_solve_kernel, dim3(n_seqs), dim3(256), ls, st, seq, slot, cams, cams_trial, ctl, info, part, red, n_tiles,
+                       n_views, max_iter, mu0);
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
+}
+
+int rg_step(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot, double* cams,
+            const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points, int n_tiles, int n_seqs, int n_views,
+            int max_iter, double ftol, double xtol, double* part2, int loss, double loss_px, mvmcStream_t stream) {
+    if (n_points < 0 || n_tiles < 0 || n_seqs < 0 || n_views < 2 || n_views > MVMC_RIG_MAX_CAMS || max_iter < 0 ||
+        max_iter > MVMC_RIG_MAX_ITER || !rg_loss_ok(loss, loss_px))
+        return MVMC_ERR_ARG;
+    if (n_seqs == 0) return MVMC_OK;
+    if (!X || !X_trial || !uv || !tile || !seq || !slot || !cams || !cams_trial || !ctl || !info || !red || !part2) return MVMC_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_tiles > 0) {
+#define RG_BACKSUB(LS) hipLaunchKernelGGL(rig_backsub_kernel<LS>, dim3(n_tiles), dim3(64), 0, st, X, X_trial, uv, tile, slot, cams, cams_trial, \
+                                          ctl, info, red, n_points, n_seqs, n_views, loss_px, part2)
+        if (loss == MVMC_RIG_LOSS_HUBER) RG_BACKSUB(MVMC_RIG_LOSS_HUBER);
+        else if (loss == MVMC_RIG_LOSS_CAUCHY) RG_BACKSUB(MVMC_RIG_LOSS_CAUCHY);
+        else RG_BACKSUB(MVMC_RIG_LOSS_NONE);
+#undef RG_BACKSUB
+        MVMC_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(rig_decide_kernel, dim3(n_seqs), dim3(256), 0, st, X, X_trial, seq, slot, cams, cams_trial, ctl, info, part2,
+                       n_points, n_tiles, n_views, max_iter, ftol, xtol);
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
 }
 
 }  // namespace
@@ -580,49 +714,50 @@ extern "C" int mvmc_rig_accumulate(const double* X, const double* uv, const int3
                                    const double* cams, double* cams_trial, int32_t* ctl, double* info, int n_points, int n_tiles,
                                    int n_seqs, int n_views, int max_iter, double mu0, int variant, double* part, double* red,
                                    mvmcStream_t stream) {
-    if (n_points < 0 || n_tiles < 0 || n_seqs < 0 || n_views < 2 || n_views > MVMC_RIG_MAX_CAMS || max_iter < 0 ||
-        max_iter > MVMC_RIG_MAX_ITER || variant < 0 || variant > 1)
-        return MVMC_ERR_ARG;
-    if (n_seqs == 0) return MVMC_OK;
-    if (!X || !uv || !tile || !seq || !slot || !cams || !cams_trial || !ctl || !info || !part || !red) return MVMC_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t la = rg_accum_lds(n_views), ls = rg_solve_lds(n_views);
-    const void* fa = variant ? (const void*)rig_accum_kernel<true> : (const void*)rig_accum_kernel<false>;
-    if (la > 65536 && hipFuncSetAttribute(fa, hipFuncAttributeMaxDynamicSharedMemorySize, (int)la) != hipSuccess) return MVMC_ERR_LAUNCH;
-    if (ls > 65536 && hipFuncSetAttribute((const void*)rig_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ls) != hipSuccess)
-        return MVMC_ERR_LAUNCH;
-    if (n_tiles > 0) {
-        if (variant)
-            hipLaunchKernelGGL(rig_accum_kernel<true>, dim3(n_tiles), dim3(64), la, st, X, uv, tile, slot, cams, ctl, info, n_points, n_seqs,
-                               n_views, mu0, part);
-        else
-            hipLaunchKernelGGL(rig_accum_kernel<false>, dim3(n_tiles), dim3(64), la, st, X, uv, tile, slot, cams, ctl, info, n_points,
-                               n_seqs, n_views, mu0, part);
-        MVMC_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(rig_solve_kernel, dim3(n_seqs), dim3(256), ls, st, seq, slot, cams, cams_trial, ctl, info, part, red, n_tiles,
-                       n_views, max_iter, mu0);
-    MVMC_CHECK_LAUNCH();
-    return MVMC_OK;
+    return rg_accumulate(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, n_points, n_tiles, n_seqs, n_views, max_iter, mu0, variant,
+                         part, red, MVMC_RIG_LOSS_NONE, 0.0, stream);
 }
 
 extern "C" int mvmc_rig_step(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
                              double* cams, const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points,
                              int n_tiles, int n_seqs, int n_views, int max_iter, double ftol, double xtol, double* part2,
                              mvmcStream_t stream) {
-    if (n_points < 0 || n_tiles < 0 || n_seqs < 0 || n_views < 2 || n_views > MVMC_RIG_MAX_CAMS || max_iter < 0 ||
-        max_iter > MVMC_RIG_MAX_ITER)
+    return rg_step(X, X_trial, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_points, n_tiles, n_seqs, n_views, max_iter, ftol,
+                   xtol, part2, MVMC_RIG_LOSS_NONE, 0.0, stream);
+}
+
+extern "C" int mvmc_rig_accumulate_robust(const double* X, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                                          const double* cams, double* cams_trial, int32_t* ctl, double* info, int n_points, int n_tiles,
+                                          int n_seqs, int n_views, int max_iter, double mu0, int variant, double* part, double* red,
+                                          int loss, double loss_px, mvmcStream_t stream) {
+    return rg_accumulate(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, n_points, n_tiles, n_seqs, n_views, max_iter, mu0, variant,
+                         part, red, loss, loss_px, stream);
+}
+
+extern "C" int mvmc_rig_step_robust(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq,
+                                    const int32_t* slot, double* cams, const double* cams_trial, int32_t* ctl, double* info,
+                                    const double* red, int n_points, int n_tiles, int n_seqs, int n_views, int max_iter, double ftol,
+                                    double xtol, double* part2, int loss, double loss_px, mvmcStream_t stream) {
+    return rg_step(X, X_trial, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_points, n_tiles, n_seqs, n_views, max_iter, ftol,
+                   xtol, part2, loss, loss_px, stream);
+}
+
+extern "C" int mvmc_rig_weights(const double* X, const double* uv, const int32_t* tile, const double* cams, int n_points, int n_tiles,
+                                int n_seqs, int n_views, int loss, double loss_px, double* w, mvmcStream_t stream) {
+    if (n_points < 0 || n_tiles < 0 || n_seqs < 0 || n_views < 2 || n_views > MVMC_RIG_MAX_CAMS || !rg_loss_ok(loss, loss_px))
         return MVMC_ERR_ARG;
-    if (n_seqs == 0) return MVMC_OK;
-    if (!X || !X_trial || !uv || !tile || !seq || !slot || !cams || !cams_trial || !ctl || !info || !red || !part2) return MVMC_ERR_ARG;
+    if (n_tiles == 0 || n_seqs == 0) return MVMC_OK;
+    if (!X || !uv || !tile || !cams || !w) return MVMC_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    if (n_tiles > 0) {
-        hipLaunchKernelGGL(rig_backsub_kernel, dim3(n_tiles), dim3(64), 0, st, X, X_trial, uv, tile, slot, cams, cams_trial, ctl, info, red,
-                           n_points, n_seqs, n_views, part2);
-        MVMC_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(rig_decide_kernel, dim3(n_seqs), dim3(256), 0, st, X, X_trial, seq, slot, cams, cams_trial, ctl, info, part2,
-                       n_points, n_tiles, n_views, max_iter, ftol, xtol);
+    if (loss == MVMC_RIG_LOSS_HUBER)
+        hipLaunchKernelGGL(rig_weights_kernel<MVMC_RIG_LOSS_HUBER>, dim3(n_tiles), dim3(64), 0, st, X, uv, tile, cams, n_points, n_seqs,
+                           n_views, loss_px, w);
+    else if (loss == MVMC_RIG_LOSS_CAUCHY)
+        hipLaunchKernelGGL(rig_weights_kernel<MVMC_RIG_LOSS_CAUCHY>, dim3(n_tiles), dim3(64), 0, st, X, uv, tile, cams, n_points, n_seqs,
+                           n_views, loss_px, w);
+    else
+        hipLaunchKernelGGL(rig_weights_kernel<MVMC_RIG_LOSS_NONE>, dim3(n_tiles), dim3(64), 0, st, X, uv, tile, cams, n_points, n_seqs,
+                           n_views, loss_px, w);
     MVMC_CHECK_LAUNCH();
     return MVMC_OK;
 }

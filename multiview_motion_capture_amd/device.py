@@ -681,6 +681,48 @@ def rig_step(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: tor
           "mvmc_rig_step")
 
 
+def rig_accumulate_robust(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
+                          cams: torch.Tensor, cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, max_iter: int, mu0: float,
+                          part: torch.Tensor, red: torch.Tensor, variant: int = 1, loss: int = 0, loss_px: float = 0.0) -> None:
+    """rig_accumulate with a robust loss (include/mvmc.h: mvmc_rig_accumulate_robust): loss 0 none, 1 Huber, 2 Cauchy at loss_px."""
+    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
+    _req(part, torch.float64, "part", (None, int(_cabi.load().mvmc_rig_part_doubles(Cn))))
+    if part.shape[0] < T:
+        raise ValueError(f"part: {part.shape[0]} rows for {T} tiles")
+    check(_cabi.load().mvmc_rig_accumulate_robust(_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
+                                                  N, T, S, Cn, int(max_iter), float(mu0), int(variant), _p(part), _p(red), int(loss),
+                                                  float(loss_px), _stream()), "mvmc_rig_accumulate_robust")
+
+
+def rig_step_robust(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
+                    cams: torch.Tensor, cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, red: torch.Tensor, max_iter: int,
+                    ftol: float, xtol: float, part2: torch.Tensor, loss: int = 0, loss_px: float = 0.0) -> None:
+    """rig_step with a robust loss (include/mvmc.h: mvmc_rig_step_robust): the trial cost and every cost in info are sum rho."""
+    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
+    _req(X_trial, torch.float64, "X_trial", (N, 3))
+    _req(part2, torch.float64, "part2", (None, 4))
+    if part2.shape[0] < T:
+        raise ValueError(f"part2: {part2.shape[0]} rows for {T} tiles")
+    check(_cabi.load().mvmc_rig_step_robust(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl),
+                                            _p(info), _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), int(loss),
+                                            float(loss_px), _stream()), "mvmc_rig_step_robust")
+
+
+def rig_weights(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, cams: torch.Tensor, loss: int, loss_px: float) -> torch.Tensor:
+    """The loss's weight of every observation at (X, cams) (include/mvmc.h: mvmc_rig_weights) -> w (N,C) f64, NaN where the camera
+    does not observe the point (and on points outside every tile)."""
+    N, Cn = uv.shape[:2]
+    S = cams.shape[0]
+    _req(X, torch.float64, "X", (N, 3))
+    _req(uv, torch.float64, "uv", (N, Cn, 2))
+    _req(tile, torch.int32, "tile", (None, 4))
+    _req(cams, torch.float64, "cams", (S, Cn, _cabi.RIG_CAM_DOUBLES))
+    w = torch.full((N, Cn), float("nan"), dtype=torch.float64, device=X.device)
+    check(_cabi.load().mvmc_rig_weights(_p(X), _p(uv), _p(tile), _p(cams), N, int(tile.shape[0]), S, Cn, int(loss), float(loss_px), _p(w),
+                                        _stream()), "mvmc_rig_weights")
+    return w
+
+
 def _pair_req(xn, seq, pair):
     _req(xn, torch.float64, "xn", (None, 17, 2))
     _req(seq, torch.int32, "seq", (None, 4))

@@ -16,7 +16,9 @@ association.  The walk must COVER the volume: a person who wanders 0.2 m around 
      in front of both cameras, and those points;
   5. pose graph (host): Prim's maximum spanning tree from camera 0 over the pairs with >= ``min_pair_inliers`` inliers; the scale of
      every edge after the first from the median ratio of the depths two edges give the same points; composition;
-  6. polish: rig_refine's bundle adjustment (camera 0 held) on the walk's own points, a (frame, joint) that >= 2 views see;
+  6. polish: rig_refine's bundle adjustment (camera 0 held) on the walk's own points, a (frame, joint) that >= 2 views see; by
+     default plain least squares behind the ``polish_px`` gate, with ``polish_loss="huber" | "cauchy"`` rig_refine's robust loss at
+     ``polish_loss_px`` pixels, which keeps detections with exchanged limbs that pass the gate from pulling on the rig;
   7. metric scale from ``baseline=(i, j, metres)`` or, without one, from the limb lengths of the default skeleton -- an average-adult
      assumption good to about +-10 %, stated and not measured; ``world="floor"`` turns the result upright: +z the mean direction hips
      -> shoulders, z = 0 at the median of the lower ankle, x camera 0's optical axis along the floor, the origin below camera 0.
@@ -36,7 +38,7 @@ import numpy as np
 
 from . import body_fit
 from .common import Calib
-from .rig_refine import MAX_CAMS, MAX_ITER_CAP, STOP, RigRefinement, _moved, solve_group
+from .rig_refine import LOSS_PX, MAX_CAMS, MAX_ITER_CAP, STOP, RigRefinement, _moved, check_loss, robust_fields, solve_group
 
 MAX_SAMPLE, MAX_ROUNDS = 32, 8            # include/mvmc.h: MVMC_RIGINIT_MAX_SAMPLE, MVMC_RIGINIT_MAX_ROUNDS
 MIN_COMMON = 10                           # points two edges must share for a scale
@@ -84,8 +86,9 @@ def _cameras(cams, who):
 
 
 def check_calibrate(sequences, hypotheses, sample_frames, inlier_px, min_score, min_pair_inliers, refit_rounds, polish_iter, polish_px,
-                    baseline, world):
+                    baseline, world, polish_loss=None, polish_loss_px=LOSS_PX, polish_ftol=None):
     """The input checks of calibrate_rigs, before any device work: ValueError, or (per sequence (F, C, P), cameras, baselines)."""
+    check_loss("calibrate_rigs", polish_loss, polish_loss_px, polish_ftol, None)
     if len(sequences) == 0:
         raise ValueError("calibrate_rigs: no sequences")
     if not 1 <= int(hypotheses) <= 65535:
@@ -241,15 +244,18 @@ def finish(Rt, X, baseline=None, world="camera0"):
 def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_frames: int = 8, inlier_px: float = 6.0,
                    min_score: float = body_fit.MIN_SCORE, min_pair_inliers: int = 100, refit_rounds: int = 3, polish_iter: int = 10,
                    polish_px: float = body_fit.MAX_DIST, baseline=None, world: str = "camera0", seed: int = 0, device="cuda:0",
-                   timings: Optional[dict] = None, detail: Optional[list] = None) -> List[RigCalibration]:
+                   timings: Optional[dict] = None, detail: Optional[list] = None, polish_loss: Optional[str] = None,
+                   polish_loss_px: float = LOSS_PX, polish_ftol: Optional[float] = None) -> List[RigCalibration]:
     """Calibrate the rig of every sequence -- (kps25 (F_s,C_s,P_s,25|17,3), counts (F_s,C_s), cameras: per view a Calib, whose Rt is
     ignored, or (K, (w, h))) -- from the one person who walks through it.  -> one RigCalibration per sequence; a rig that cannot be
     calibrated comes back with ``stop`` saying why and calibs None.  baseline: (i, j, metres) for every sequence, or a list with one
     such tuple or None per sequence.  timings: a dict that receives the seconds spent in {"observe", "pairs", "graph", "polish"}
     (synchronising between the parts).  detail: a list that receives per sequence what the kernels returned for its pairs -- what the
-    tests compare."""
+    tests compare.  polish_loss: None (plain least squares, the code path without these arguments), "huber" or "cauchy" at
+    polish_loss_px pixels (rig_refine's loss); polish_ftol: the polish's ftol, None = the body fit's constant.  With a loss the polish
+    makes more trials (it converges linearly) and ``polish`` carries the loss's fields; rms_px stays the plain rms."""
     shapes, cams, bases = check_calibrate(sequences, hypotheses, sample_frames, inlier_px, min_score, min_pair_inliers, refit_rounds,
-                                          polish_iter, polish_px, baseline, world)
+                                          polish_iter, polish_px, baseline, world, polish_loss, polish_loss_px, polish_ftol)
     import torch
 
     from . import device as dev
@@ -346,11 +352,13 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
         Rtin = np.array([Rt_tree[s] for s in ids])
         any_c = obs.shape[0] > 0
         g = solve_group(T(obs) if any_c else None, T(rig_c) if any_c else None, T(np.einsum("scij,scjk->scik", Kin, Rtin)) if any_c else None,
-                        Kin, Rtin, n, C, d, int(polish_iter), float(polish_px), float(min_score), 2, int(min_pair_inliers), 1, lap, t0)
+                        Kin, Rtin, n, C, d, int(polish_iter), float(polish_px), float(min_score), 2, int(min_pair_inliers), 1, lap, t0,
+                        polish_loss, polish_loss_px, polish_ftol, None)
         t0 = g["t0"]
         X_run = g["X_d"].cpu().numpy()
         X0 = g["X0_d"].cpu().numpy()[:, :3] if any_c else np.zeros((0, 3))
         x_lo = np.concatenate([[0], np.cumsum(np.bincount(g["seq_of"][g["dev_pt"]], minlength=n))])
+        w_lo = np.concatenate([[0], np.cumsum(np.where(g["run"], g["n_pts"], 0))])
         for r, s in enumerate(ids):
             m = g["seq_of"] == r
             Rt_new = np.concatenate([g["cams_h"][r, :, 9:18].reshape(C, 3, 3), g["cams_h"][r, :, 18:21, None]], axis=2)
@@ -367,11 +375,13 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
                 cost, trials = (np.array([e0]) if n_o else np.zeros(0)), []
                 rb = ra = float(np.sqrt(2.0 * e0 / n_o)) if n_o else float("nan")
                 Xp = X0[m & g["is_pt"]]
+            rob = robust_fields(g, r, w_lo, n_o, polish_loss, polish_loss_px, False) if polish_loss is not None else {}
+            rb, ra = rob.pop("rms", (rb, ra))
             wh = [w for _, w in cams[s]]
             pol = RigRefinement(calibs=[Calib.from_k_rt(Ks[s][c].copy(), Rt_new[c].copy(), wh[c]) for c in range(C)], rms_before=rb,
                                 rms_after=ra, n_points=int(g["n_pts"][r]), n_obs=n_o, obs_per_camera=g["n_obs"][r].copy(),
                                 held=g["held"][r].copy(), cost=cost, trials=trials, stop=STOP[int(g["ctl_h"][r, 0])],
-                                moved=_moved(Rtin[r], Rt_new))
+                                moved=_moved(Rtin[r], Rt_new), **rob)
             X = np.full((cand[r].shape[0], 3), np.nan)
             X[np.flatnonzero(is_c[r])[g["is_pt"][m]]] = Xp
             Rt_fin, X_fin, src = finish(Rt_new, X.reshape(-1, 17, 3), bases[s], world)

@@ -12,17 +12,24 @@ calibration a day old) by a bundle adjustment over the keypoints of the people t
   c. cameras: camera 0 is held; a camera with fewer than ``min_cam_obs`` observations is held too -- it is not moved at all, not even
      by the gauge rescale, so its observations leave the problem (points are checked against ``min_views`` once more; one pass).
      Fewer than two free cameras or fewer than 3 points: the input rig comes back with ``stop`` saying so;
-  d. Levenberg-Marquardt with the body fit's rules on E = 1/2 sum r^2 (plain pixel reprojection, unweighted, NO robust loss: the two
+  d. Levenberg-Marquardt with the body fit's rules on E = 1/2 sum r^2 (plain pixel reprojection, unweighted; by default the two
      gates are the only outlier handling); unknowns: every point, and per free camera a rotation increment (R <- exp([w]x) R) and a
-     translation increment.  The points are eliminated by a Schur complement; the reduced camera system is solved by Cholesky;
+     translation increment.  The points are eliminated by a Schur complement; the reduced camera system is solved by Cholesky.
+     ``loss="huber" | "cauchy"`` (opt-in) puts a robust loss behind the two gates: with s the length of an observation's residual
+     and delta = ``loss_px``, Huber has rho = 1/2 s^2, w = 1 for s <= delta and rho = delta (s - 1/2 delta), w = delta / s beyond;
+     Cauchy has rho = 1/2 delta^2 log1p(s^2 / delta^2), w = 1 / (1 + s^2 / delta^2).  E = sum rho is then the cost of every rule, and
+     at every linearisation the observation's Jacobian rows and residual are multiplied by sqrt(w) (iteratively reweighted, no
+     second-order correction).  The reweighted iteration converges linearly: it makes more trials, and ``ftol`` around 1e-5 .. 1e-8
+     stops it cleanly where the default 1e-12 runs to ``max_iter``;
   e. after every accepted trial the camera centres and points are scaled about camera 0's centre so that the distance from camera 0
      to the first free camera keeps its input length (an exact gauge move).
 
 It does not touch intrinsics or distortion, does no time synchronisation and is no calibration from scratch: the input rig must be
 good enough for the tracker to produce records.
 
-Device code: csrc/mvmc_rigfit.hip (include/mvmc.h: mvmc_rig_start, mvmc_rig_accumulate, mvmc_rig_step); NumPy restatement:
-tests/rig_refine_np.py.  Sequences with the same number of cameras share every launch, each with its own rig; there is no host
+Device code: csrc/mvmc_rigfit.hip (include/mvmc.h: mvmc_rig_start, mvmc_rig_accumulate, mvmc_rig_step; with a loss
+mvmc_rig_accumulate_robust, mvmc_rig_step_robust, mvmc_rig_weights); NumPy restatement: tests/rig_refine_np.py, with a loss
+tests/rig_robust_np.py.  Sequences with the same number of cameras share every launch, each with its own rig; there is no host
 synchronisation between the trials and one read-back per group.
 """
 from __future__ import annotations
@@ -42,6 +49,8 @@ TILE = 64            # include/mvmc.h: MVMC_RIG_TILE
 MAX_CAMS = 8         # MVMC_RIG_MAX_CAMS
 MAX_ITER_CAP = 24    # MVMC_RIG_MAX_ITER
 STOP = {0: "running", 1: "xtol", 2: "ftol", 3: "few_cameras", 4: "few_points", 5: "max_iter"}   # MVMC_RIG_STOP_*
+LOSS = {None: 0, "huber": 1, "cauchy": 2}    # MVMC_RIG_LOSS_*
+LOSS_PX = 6.0        # three times a 2 px detector noise; a choice, not a tuned optimum
 
 
 @dataclass
@@ -57,11 +66,30 @@ class RigRefinement:
     trials: list                 # 1 accepted / 0 rejected
     stop: str                    # "ftol", "xtol", "max_iter", "few_cameras", "few_points"
     moved: np.ndarray            # (C, 2): rotation angle (rad) and centre displacement (m)
+    # filled only with a loss.  cost then holds the robust E = sum rho; rms_before and rms_after stay the PLAIN rms over the problem's
+    # observations, comparable with a call without a loss
+    loss: Optional[str] = None
+    loss_px: Optional[float] = None
+    downweighted: Optional[np.ndarray] = None   # (C,) share of the camera's observations with final w < 0.5 (NaN without any)
+    weights: Optional[np.ndarray] = None        # (N, C) final w, NaN where not observed; only with return_weights=True
 
 
-def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step):
+def check_loss(who, loss, loss_px, ftol, xtol):
+    """The checks of the robust-loss arguments, before any device work: ValueError."""
+    if loss not in LOSS:
+        raise ValueError(f'{who}: loss is None, "huber" or "cauchy"')
+    if loss is not None and not (np.isfinite(float(loss_px)) and float(loss_px) > 0.0):
+        raise ValueError(f"{who}: loss_px must be a finite number > 0")
+    for name, v in (("ftol", ftol), ("xtol", xtol)):
+        if v is not None and not (np.isfinite(float(v)) and float(v) >= 0.0):
+            raise ValueError(f"{who}: {name} must be None or a finite number >= 0")
+
+
+def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step, loss=None,
+                 loss_px=LOSS_PX, ftol=None, xtol=None):
     """The input checks of refine_rigs, before any device work: ValueError, or (shapes, per sequence the records' (frames, params,
     joints) arrays)."""
+    check_loss("refine_rigs", loss, loss_px, ftol, xtol)
     if len(tracklets_per_sequence) != len(sequences):
         raise ValueError(f"refine_rigs: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
     if int(min_views) < 2:
@@ -134,13 +162,14 @@ def _moved(Rt_in, Rt_out):
     return out
 
 
-def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, t0):
+def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, t0, loss=None,
+                loss_px=LOSS_PX, ftol=None, xtol=None):
     """Steps b - e on the candidates of a group of S sequences of C cameras: what refine_rigs does after its selection, and what
     rig_init.calibrate_rigs polishes with.  obs_d (n,C,3) f64 device: u, v, score per candidate and camera (None: no candidate);
     rig_c (n,) i32 device: the candidate's sequence; Pm_d (S,C,3,4) device; Kin (S,C,3,3), Rtin (S,C,3,4) host; lap(key, t0) -> t1 the
     caller's stopwatch ("start", "trials").  -> dict: the host gates' arrays (dist, seq_of, obs, held, is_pt, n_pts, n_obs, run), the
     one read-back (cams_h (S,C,21), info_h, ctl_h), the device's start values X0_d and final points X_d with dev_pt (their candidates),
-    and t0."""
+    and t0.  With a loss also e_plain (S,2): the plain 1/2 sum r^2 before and after, and w_h (points of dev_pt, C): the final weights."""
     import torch
 
     from . import _cabi
@@ -180,35 +209,79 @@ def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_sc
     tile_d, seq_d, slot_d, cams_d, info_d, ctl_d = T(tile), T(seq), T(slot), T(cams), T(info), T(ctl)
     camt_d = cams_d.clone()
     part, part2, red = dev.rig_work(tile.shape[0], S, C, d)
-    if run.any():
+    ftol, xtol = LM_FTOL if ftol is None else float(ftol), LM_XTOL if xtol is None else float(xtol)
+    extra = []
+
+    def plain_cost():
+        # 1/2 sum r^2 at (X, cams): an accumulate without a loss and without a trial on a control block of its own
+        ctl2, info2 = T(ctl), T(info)
+        dev.rig_accumulate(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d.clone(), ctl2, info2, 0, LM_MU0, part, torch.zeros_like(red),
+                           variant)
+        return info2[:, 0]
+
+    if run.any() and loss is None:
         for _ in range(max(int(max_iter), 1)):
             dev.rig_accumulate(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant)
             if int(max_iter):
-                dev.rig_step(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, LM_FTOL, LM_XTOL,
-                             part2)
+                dev.rig_step(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, ftol, xtol, part2)
+    elif run.any():
+        code, px = LOSS[loss], float(loss_px)
+        extra.append(plain_cost())
+        for _ in range(max(int(max_iter), 1)):
+            dev.rig_accumulate_robust(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant,
+                                      code, px)
+            if int(max_iter):
+                dev.rig_step_robust(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, ftol, xtol,
+                                    part2, code, px)
+        extra.append(plain_cost())
+        extra.append(dev.rig_weights(X_d, uv_d, tile_d, cams_d, code, px).reshape(-1))
     t0 = lap("trials", t0)
-    back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()]).cpu().numpy()   # the one read-back
+    back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()] + extra).cpu().numpy()   # the one read-back
     cams_h = back[:S * C * 21].reshape(S, C, 21)
     info_h = back[S * C * 21:S * C * 21 + info.size].reshape(S, -1)
-    ctl_h = back[S * C * 21 + info.size:].reshape(S, 4).astype(np.int64)
-    return dict(t0=t0, dist=dist, seq_of=seq_of, obs=obs, held=held, is_pt=is_pt, n_pts=n_pts, n_obs=n_obs, run=run, cams_h=cams_h,
+    n_fix = S * C * 21 + info.size + 4 * S
+    ctl_h = back[S * C * 21 + info.size:n_fix].reshape(S, 4).astype(np.int64)
+    robust = {}
+    if extra:
+        robust = dict(e_plain=back[n_fix:n_fix + 2 * S].reshape(2, S).T, w_h=back[n_fix + 2 * S:].reshape(-1, C))
+    return dict(**robust, t0=t0, dist=dist, seq_of=seq_of, obs=obs, held=held, is_pt=is_pt, n_pts=n_pts, n_obs=n_obs, run=run, cams_h=cams_h,
                 info_h=info_h, ctl_h=ctl_h, X0_d=X0_d, X_d=X_d, dev_pt=dev_pt)
+
+
+def robust_fields(g, r, w_lo, n_o, loss, loss_px, return_weights):
+    """The RigRefinement fields a loss adds for sequence r of solve_group's result g (w_lo (S + 1,): its rows of g["w_h"]): loss,
+    loss_px, downweighted, weights, and for a solved sequence rms = the plain (rms_before, rms_after)."""
+    C = g["held"].shape[1]
+    out = dict(loss=loss, loss_px=float(loss_px), downweighted=np.full(C, np.nan), weights=None)
+    if g["run"][r] and "w_h" in g:
+        w = g["w_h"][w_lo[r]:w_lo[r + 1]]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["downweighted"] = (w < 0.5).sum(axis=0) / (~np.isnan(w)).sum(axis=0)
+        if return_weights:
+            out["weights"] = w.copy()
+        out["rms"] = tuple(float(np.sqrt(2.0 * e / n_o)) for e in g["e_plain"][r])
+    return out
 
 
 def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], max_iter: int = 10,
                 max_px: float = body_fit.MAX_DIST, min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100,
                 frame_step: int = 1, device="cuda:0", timings: Optional[dict] = None, variant: int = 1,
-                problems: Optional[list] = None) -> List[RigRefinement]:
+                problems: Optional[list] = None, loss: Optional[str] = None, loss_px: float = LOSS_PX, ftol: Optional[float] = None,
+                xtol: Optional[float] = None, return_weights: bool = False) -> List[RigRefinement]:
     """Refine the rig of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows track_sequences
     takes -- from its MvTracklet records.  -> one RigRefinement per sequence; the inputs are not touched.
     timings: a dict that receives the seconds spent in {"select", "start", "trials", "records"} (synchronising between the parts).
     variant: 1 the tile products on the matrix cores, 0 as FMAs.  problems: a list that receives, per sequence, the packed problem
-    (dict X0 (N,3), uv (N,C,2), cand (n,C,3), rows (N,): the candidates that became points) -- what the tests compare."""
+    (dict X0 (N,3), uv (N,C,2), cand (n,C,3), rows (N,): the candidates that became points) -- what the tests compare.
+    loss: None (the plain least squares, the code path without these arguments), "huber" or "cauchy" at loss_px pixels, behind the
+    two max_px gates; the records then carry loss, loss_px, downweighted and (return_weights=True) weights, their cost is the robust
+    E, and rms_before / rms_after stay the plain rms.  ftol, xtol: the stop tolerances, None = the body fit's constants."""
     if len(sequences) == 0:
         if len(tracklets_per_sequence):
             raise ValueError("refine_rigs: records without sequences")
         return []
-    shapes, recs = check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step)
+    shapes, recs = check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step, loss,
+                                loss_px, ftol, xtol)
     import torch
 
     from . import _cabi
@@ -274,12 +347,13 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
             n_cand = int(obs_d.shape[0])
         t0 = lap("select", t0)
         g = solve_group(obs_d if n_cand else None, rig_c if n_cand else None, Pm_d if n_cand else None, Kin, Rtin, S, C, d, max_iter,
-                        max_px, min_score, min_views, min_cam_obs, variant, lap, t0)
+                        max_px, min_score, min_views, min_cam_obs, variant, lap, t0, loss, loss_px, ftol, xtol)
         t0, dist, seq_of, obs, held, is_pt, n_pts, n_obs, run = (g[k] for k in ("t0", "dist", "seq_of", "obs", "held", "is_pt", "n_pts",
                                                                                 "n_obs", "run"))
         cams_h, info_h, ctl_h, X0_d = g["cams_h"], g["info_h"], g["ctl_h"], g["X0_d"]
         if problems is not None and n_cand:
             cand, X0 = obs_d.cpu().numpy(), X0_d.cpu().numpy()
+        w_lo = np.concatenate([[0], np.cumsum(np.where(run, n_pts, 0))])
         for r, i in enumerate(ids):
             Rt_new = np.concatenate([cams_h[r, :, 9:18].reshape(C, 3, 3), cams_h[r, :, 18:21, None]], axis=2)
             n_o = int(n_obs[r].sum())
@@ -293,10 +367,12 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
                 e0 = 0.5 * float(np.sum(dd * dd))
                 cost, trials = (np.array([e0]) if n_o else np.zeros(0)), []
                 rb = ra = float(np.sqrt(2.0 * e0 / n_o)) if n_o else float("nan")
+            rob = robust_fields(g, r, w_lo, n_o, loss, loss_px, return_weights) if loss is not None else {}
+            rb, ra = rob.pop("rms", (rb, ra))
             calibs = [Calib.from_k_rt(np.array(c.K, np.float64), Rt_new[k].copy(), c.img_wh_size) for k, c in enumerate(sequences[i][2])]
             out[i] = RigRefinement(calibs=calibs, rms_before=rb, rms_after=ra, n_points=int(n_pts[r]), n_obs=n_o,
                                    obs_per_camera=n_obs[r].copy(), held=held[r].copy(), cost=cost, trials=trials,
-                                   stop=STOP[int(ctl_h[r, 0])], moved=_moved(Rtin[r], Rt_new))
+                                   stop=STOP[int(ctl_h[r, 0])], moved=_moved(Rtin[r], Rt_new), **rob)
             if problems is not None and n_cand:
                 m = seq_of == r
                 pr = is_pt[m]
@@ -310,7 +386,9 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
 
 def refine_rig(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, max_iter: int = 10, max_px: float = body_fit.MAX_DIST,
                min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100, frame_step: int = 1, device="cuda:0",
-               timings: Optional[dict] = None) -> RigRefinement:
+               timings: Optional[dict] = None, loss: Optional[str] = None, loss_px: float = LOSS_PX, ftol: Optional[float] = None,
+               xtol: Optional[float] = None, return_weights: bool = False) -> RigRefinement:
     """refine_rigs for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> RigRefinement."""
     return refine_rigs([(kps, counts, calibs)], [tracklets], max_iter=max_iter, max_px=max_px, min_score=min_score, min_views=min_views,
-                       min_cam_obs=min_cam_obs, frame_step=frame_step, device=device, timings=timings)[0]
+                       min_cam_obs=min_cam_obs, frame_step=frame_step, device=device, timings=timings, loss=loss, loss_px=loss_px,
+                       ftol=ftol, xtol=xtol, return_weights=return_weights)[0]
