@@ -268,18 +268,23 @@ def fk(params: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None, want_G=Fal
     return (joints, G) if want_G else joints
 
 
-_IK_SCRATCH = {}
+_STREAM_BUFFERS = {}
+
+
+def stream_buffer(name: str, n: int, tail: tuple, dev) -> torch.Tensor:
+    """The f64 device workspace ``name`` of (device, current stream): at least n rows of shape ``tail``, grown on demand and never read
+    by the host."""
+    key = (name, str(dev), torch.cuda.current_stream(dev).cuda_stream)
+    buf = _STREAM_BUFFERS.get(key)
+    if buf is None or buf.shape[0] < n:
+        buf = torch.empty((n,) + tuple(tail), dtype=torch.float64, device=dev)
+        _STREAM_BUFFERS[key] = buf
+    return buf
 
 
 def _ik_scratch(n_problems: int, dev) -> torch.Tensor:
-    """Workspace of the IK kernel's eigensolver fallback (include/mvmc.h: MVMC_IK_SCRATCH_DOUBLES per problem).
-    One buffer per (device, stream), grown on demand and never read by the host."""
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    buf = _IK_SCRATCH.get(key)
-    if buf is None or buf.shape[0] < n_problems:
-        buf = torch.empty((n_problems, _cabi.IK_SCRATCH_DOUBLES), dtype=torch.float64, device=dev)
-        _IK_SCRATCH[key] = buf
-    return buf
+    """Workspace of the IK kernel's eigensolver fallback (include/mvmc.h: MVMC_IK_SCRATCH_DOUBLES per problem)."""
+    return stream_buffer("ik", n_problems, (_cabi.IK_SCRATCH_DOUBLES,), dev)
 
 
 def ik_solve(kps17: torch.Tensor, Pmats: torch.Tensor, members: torch.Tensor,
@@ -451,21 +456,13 @@ def smooth_step(x: torch.Tensor, x_trial: torch.Tensor, blk: torch.Tensor, id_lo
           "mvmc_smooth_step")
 
 
-_SW_WORK = {}
-
-
 def smooth_window_work(n_items: int, window: int, dev) -> torch.Tensor:
-    """Workspace of mvmc_smooth_window for ``n_items`` identities of one tick: one buffer per (device, stream), sized by the identities
-    active in the tick and grown on demand (include/mvmc.h: mvmc_smooth_window_work_doubles)."""
+    """Workspace of mvmc_smooth_window for ``n_items`` identities of one tick, sized by the identities active in the tick
+    (include/mvmc.h: mvmc_smooth_window_work_doubles)."""
     need = int(_cabi.load().mvmc_smooth_window_work_doubles(int(n_items), int(window)))
     if need < 0:
         raise ValueError(f"smooth_window: no workspace for {n_items} items of window {window}")
-    key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
-    buf = _SW_WORK.get(key)
-    if buf is None or buf.numel() < need:
-        buf = torch.empty((max(need, 1),), dtype=torch.float64, device=dev)
-        _SW_WORK[key] = buf
-    return buf
+    return stream_buffer("smooth_window", max(need, 1), (), dev)
 
 
 def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, new_params: torch.Tensor, new_members: torch.Tensor,

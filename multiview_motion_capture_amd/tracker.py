@@ -8,16 +8,125 @@ associate_tracking does (motion_capture.py:829-835).
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import device as dev
+from . import _cabi, device as dev
 from .pipeline import HotPath
 
 T_WIDE = 16   # tracklet slots of the repair tier (include/mvmc.h: the stitch and the widest association variant hold 16)
+
+
+class ChainFlags:
+    """The chain kernel's flag words by name.  The comment of mvmcChainBuffers.flags in include/mvmc.h is the specification; this is its
+    one restatement on the Python side.  ``words`` is a torch tensor or a NumPy array (it is only sliced) of n_chains chains."""
+    CLUSTER, TRACKS, GRAPH, IK_PAIR, RIG = 1, 2, 4, 8, 16     # the bits of a void word (run_chains' overflow word: the first three)
+    REPAIRABLE = CLUSTER | TRACKS | GRAPH                      # what repair_chains' wider tables take
+
+    def __init__(self, words, n_chains: int):
+        B = n_chains
+        self.words, self.B, self._v0 = words, B, B + 4
+
+    @staticmethod
+    def length(n_chains: int, n_parts: int) -> int:
+        return n_chains * (n_parts + 1) + 8
+
+    done = property(lambda s: s.words[:s.B])                  # the chains' hand-over counters
+    timeout = property(lambda s: s.words[s.B])                # != 0: a workgroup waited for its predecessor in vain
+    graph = property(lambda s: s.words[s.B + 1])              # != 0: a graph beyond the layout's association variant
+    capacity = property(lambda s: s.words[s.B + 2])           # the void bits of all chains but GRAPH, or'ed
+    status = property(lambda s: s.words[s.B:s.B + 3])         # the three above: what a shard sends along (parallel.run_sharded)
+    void = property(lambda s: s.words[s._v0:s._v0 + s.B])     # per chain: non-zero voids the chain's results
+    tickets = property(lambda s: s.words[s._v0 + s.B])        # the ticket counter (the ready queue follows it)
+
+    def host(self) -> "ChainFlags":
+        """Device words, up to the ticket counter, on the host: one transfer (synchronises)."""
+        return ChainFlags(self.words[:self._v0 + self.B + 1].cpu().numpy(), self.B)
+
+
+def void_verdict(timeout: int, bits: int, n_void: int, who: str) -> Optional[Exception]:
+    """What a launch's words mean to its caller ``who``: the exception to raise, or None.  timeout: the time-out word; bits: the void
+    words of the chains, or'ed; n_void: how many are non-zero.  A RuntimeError is the kernel's own failure; a ValueError is data beyond
+    a table (the reference has no such caps), which wider tables take -- update_4d replays the frame, repair_chains the chains."""
+    F = ChainFlags
+    if timeout:
+        return RuntimeError(f"{who}: a hand-over between the workgroups of a chain timed out; results are void")
+    if bits & F.IK_PAIR:
+        return RuntimeError(f"{who}: internal: a meeting of two IK waves timed out (mvmc_ik_pair.h); results are void")
+    if bits & F.RIG:
+        return ValueError(f"{who}: a chain's rig index is outside [0, n_rigs): no calibration was read, its tables are empty "
+                          f"({n_void} chain(s) void)")
+    if bits & F.GRAPH:
+        return ValueError(f"{who}: a frame's graph has more nodes than the association kernel holds (the chain kernel's small layout: "
+                          f"24 without, 32 with tracklets; 80 otherwise) in {n_void} chain(s); repair_chains / run_chains take such data")
+    if bits & (F.CLUSTER | F.TRACKS):
+        what = [m for bit, m in ((F.CLUSTER, "a cluster, a member or a view block did not fit (k_max / v_max / the frame's poses)"),
+                                 (F.TRACKS, "more than t_max live tracklets")) if bits & bit]
+        return ValueError(f"{who}: capacity exceeded (" + "; ".join(what) + f") in {n_void} chain(s): their results are void")
+    return None
+
+
+def _verdict_of(timeout, void: np.ndarray, who: str) -> Optional[Exception]:
+    return void_verdict(int(timeout), int(np.bitwise_or.reduce(void)), int(np.count_nonzero(void)), who)
+
+
+def _raise_if_void(timeout, void: np.ndarray, who: str) -> None:
+    exc = _verdict_of(timeout, void, who)
+    if exc is not None:
+        raise exc
+
+
+def chain_workspace(B: int, n_out: int, C: int, P: int, T: int, K: int, V: int, d, want_info: bool, flags) -> dict:
+    """The chain kernel's own buffers -- every pointer of mvmcChainBuffers but the frames, the calibration and the tracker state -- for B
+    chains and n_out output frames.  flags: the tensor, or the length of one to allocate (ChainFlags.length)."""
+    N, NS, NP = C * P, T + C * P, T + K
+    f64, i32 = torch.float64, torch.int32
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=d)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)
+    return dict(
+        seed_table=dev.als_seed_table(_cabi.MAX_NODES * _cabi.MAX_NODES, d),
+        S_sp=e((B, N, N), torch.float32), W_st=e((B, NS, NS), f64), group_counts=e((B, C + 1), i32),
+        labels_sp=e((B, N), i32), labels_st=e((B, NS), i32), n_clusters_sp=z((B,), i32), n_clusters_st=z((B,), i32),
+        iters_sp=z((B,), i32), iters_st=z((B,), i32), members=e((B, NP, V), i32), n_members=z((B, NP), i32),
+        cold=e((B, NP), torch.uint8), init=e((B, NP, 68), f64), status=e((B, T), i32), n_new=e((B,), i32),
+        ik_params=e((B, NP, 68), f64), ik_joints=e((B, NP, 18, 3), f64), ik_info=e((B, NP, 8), f64),
+        ik_scratch=dev.stream_buffer("chain_ik", B, (8, _cabi.IK_SCRATCH_DOUBLES), d),
+        out_params=e((n_out, T, 68), f64), out_joints=e((n_out, T, 18, 3), f64), out_meta=e((n_out, T, 4), i32),
+        out_n_tracks=e((n_out,), i32), out_info=e((n_out, NP, 8), f64) if want_info else None,
+        out_als_iters=e((n_out,), i32) if want_info else None, out_phase_cycles=e((B, 8), f64) if want_info else None,
+        flags=z((flags,), i32) if isinstance(flags, int) else flags)
+
+
+def fill_chain_buffers(ints: dict, tensors: dict) -> "_cabi.MvmcChainBuffers":
+    """mvmcChainBuffers of ``ints`` (name -> int) and ``tensors`` (name -> tensor, or None: the explicit NULL).  Every field is named."""
+    buf = _cabi.MvmcChainBuffers()
+    odd = (set(ints) ^ set(buf._INTS)) | (set(tensors) ^ set(buf._PTRS))
+    if odd:
+        raise ValueError(f"a chain buffer is not named or not known: {sorted(odd)}")
+    for name in buf._INTS:
+        setattr(buf, name, int(ints[name]))
+    for name in buf._PTRS:
+        setattr(buf, name, None if tensors[name] is None else tensors[name].data_ptr())
+    return buf
+
+
+def launch_chain(skeleton, buf, d, rig_of_chain: Optional[torch.Tensor] = None, n_rigs: int = 1,
+                 active: Optional[torch.Tensor] = None) -> None:
+    """One launch of the chain kernel on d's current stream: mvmc_chain_run_sessions with ``active``, mvmc_chain_run_rigs with
+    ``rig_of_chain`` alone, mvmc_chain_run with neither (include/mvmc.h: the three are one kernel)."""
+    lib, sk, bf = _cabi.load(), ctypes.byref(skeleton), ctypes.byref(buf)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(d).cuda_stream)
+    rig = None if rig_of_chain is None else ctypes.c_void_p(rig_of_chain.data_ptr())
+    if active is not None:
+        _cabi.check(lib.mvmc_chain_run_sessions(sk, bf, rig, n_rigs, ctypes.c_void_p(active.data_ptr()), stream), "mvmc_chain_run_sessions")
+    elif rig is not None:
+        _cabi.check(lib.mvmc_chain_run_rigs(sk, bf, rig, n_rigs, stream), "mvmc_chain_run_rigs")
+    else:
+        _cabi.check(lib.mvmc_chain_run(sk, bf, stream), "mvmc_chain_run")
 
 
 def default_caps(n_views: int, p_max: int):
@@ -57,7 +166,7 @@ class ChainTracker:
                   ("slot_src", (B, T), torch.int32), ("overflow", (B,), torch.int32),
                   # the chain kernel's flag words of step_fused (mvmc_chain_run, n_parts = 1): in the same allocation, so that
                   # read_back() brings state and verdict to the host in ONE transfer
-                  ("cflags", (2 * B + 8,), torch.int32))
+                  ("cflags", (ChainFlags.length(B, 1),), torch.int32))
         offs, total = {}, 0
         for name, shape, dt in layout:
             nbytes = int(torch.Size(shape).numel()) * (8 if dt == torch.float64 else 4)
@@ -65,11 +174,16 @@ class ChainTracker:
             total += (nbytes + 15) & ~15
         self._flat = torch.zeros((total,), dtype=torch.uint8, device=d)
         self._layout = offs
-        for name, (o, nb, shape, dt) in offs.items():
-            setattr(self, name, self._flat[o:o + nb].view(dt).view(shape))
+        for name in offs:
+            setattr(self, name, self._field(self._flat, name))
         self.slot_src.fill_(-1)
         self.frame_idx = torch.arange(B, dtype=torch.int32, device=d)
-        self._host = None   # pinned host mirror of _flat (+ the chain kernel's time-out words), allocated by read_back()
+        # two pinned host mirrors of _flat, allocated by read_back() and written alternately: the one NOT written by a call holds the
+        # state after the last frame that went through, i.e. the state in front of this one -- what restore_previous() brings back
+        # without a per-frame device snapshot
+        self._host = None
+        self._host_good = -1   # index of the mirror that holds the last good state (-1: none yet)
+        self._host_prev = -1   # _host_good as the last read_back() found it: the mirror of the frame before (restore_rows())
         self._fused = None  # workspaces of step_fused (allocated on first use)
         self._fused_args = None   # (key, MvmcChainBuffers) of the last step_fused call: the struct is rebuilt only when a pointer changes
         self._in = None     # pinned host staging + device buffers of one frame's inputs (frame_inputs())
@@ -86,6 +200,11 @@ class ChainTracker:
             self.rig_stack = stack_rigs(rigs, C)
             self.rig_of_chain = torch.from_numpy(check_rig_of_chain(np.arange(B), B, B)).to(d)
             self.active = torch.ones((B,), dtype=torch.uint8, device=d)
+
+    def _field(self, flat: torch.Tensor, name: str) -> torch.Tensor:
+        """Field ``name`` of ``flat``, a buffer laid out as _flat is (the state itself, a snapshot or a host mirror)."""
+        o, nb, shape, dt = self._layout[name]
+        return flat[o:o + nb].view(dt).view(shape)
 
     def set_rig(self, b: int, hp: HotPath) -> None:
         """Row b of the rig stack := hp's calibration (a live session opening on chain b)."""
@@ -141,7 +260,6 @@ class ChainTracker:
             out.update(D=D, W=W, st=st, sp=sp, group_counts=gc)
         return out
 
-
     def frame_inputs(self):
         """Staging for the per-frame driver (MvTracker.update_4d): ONE pinned host buffer and ONE device buffer that hold a frame's
         keypoints (B,C,P,17,3) f64 and counts (B,C) i32 side by side -- the caller fills the NumPy views `kps_np` / `cnt_np`, calls
@@ -175,86 +293,49 @@ class ChainTracker:
         for a caller that ends the frame with read_back(), which then reads them where the launch left them.
         A tracker with rigs runs mvmc_chain_run_sessions: chain b on rig row b, and only the chains whose byte in ``active`` ((B) u8 device,
         default: the tracker's own `active`) is non-zero -- an idle chain's state and words are left as they were."""
-        import ctypes as C
-        from . import _cabi
-        B, Cn, P, T, K, V = self.B, self.C, self.P, self.T, self.K, self.V
-        d = kps17.device
-        N, NS, NP = Cn * P, T + Cn * P, T + K
+        B, d = self.B, kps17.device
         if self._fused is None:
-            f64, i32 = torch.float64, torch.int32
-            e = lambda shape, dt: torch.empty(shape, dtype=dt, device=d)
-            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)
-            self._fused = dict(
-                seed_table=dev.als_seed_table(_cabi.MAX_NODES * _cabi.MAX_NODES, d),
-                S_sp=e((B, N, N), torch.float32), W_st=e((B, NS, NS), f64), group_counts=e((B, Cn + 1), i32),
-                labels_sp=e((B, N), i32), labels_st=e((B, NS), i32), n_clusters_sp=z((B,), i32), n_clusters_st=z((B,), i32),
-                iters_sp=z((B,), i32), iters_st=z((B,), i32), members=e((B, NP, V), i32), n_members=z((B, NP), i32),
-                cold=e((B, NP), torch.uint8),
-                init=e((B, NP, 68), f64), status=e((B, T), i32), n_new=e((B,), i32), ik_params=e((B, NP, 68), f64),
-                ik_joints=e((B, NP, 18, 3), f64), ik_info=e((B, NP, 8), f64), ik_scratch=_chain_scratch(B, d),
-                out_params=e((B, T, 68), f64), out_joints=e((B, T, 18, 3), f64), out_meta=e((B, T, 4), i32),
-                out_n_tracks=e((B,), i32), flags=self.cflags)
+            self._fused = chain_workspace(B, B, self.C, self.P, self.T, self.K, self.V, d, False, self.cflags)
         w = self._fused
         # the argument struct: every pointer in it but the frame's inputs belongs to this tracker, and the per-frame driver hands in
         # the same input buffers every frame (frame_inputs()) -- built once, rebuilt when an input pointer changes
-        sessions = self.rig_stack is not None or active is not None
-        if sessions and active is None:
+        if active is None and self.rig_stack is not None:
             active = self.active
         Pm, Fm, F2 = self.rig_stack if self.rig_stack is not None else (self.hp.P, self.hp.F, self.F2)
         key = (kps17.data_ptr(), counts.data_ptr(), self.nfev_cold, self.nfev_warm, Pm.data_ptr(), Fm.data_ptr(), F2.data_ptr(),
                None if active is None else active.data_ptr())
         if self._fused_args is None or self._fused_args[0] != key:
-            t = dict(w, kps17=kps17, counts=counts, Pmats=Pm, Fmats=Fm, F2=F2, params=self.params,
-                     joints=self.joints, meta=self.meta, n_tracks=self.n_tracks, next_id=self.next_id, n_dead=self.n_dead,
-                     slot_src=self.slot_src, out_info=None, out_als_iters=None, out_phase_cycles=None)
-            buf = _cabi.MvmcChainBuffers()
-            for name, val in dict(n_chains=B, chain_len=1, n_views=Cn, p_max=P, t_max=T, k_max=K, v_max=V,
-                                  max_nfev_cold=self.nfev_cold, max_nfev_warm=self.nfev_warm, n_inits=3,
-                                  seed_len=w["seed_table"].numel(), n_parts=1, force_big=0, hand_over=0).items():
-                setattr(buf, name, int(val))
-            for name in _cabi.MvmcChainBuffers._PTRS:
-                ten = t[name]
-                setattr(buf, name, None if ten is None else ten.data_ptr())
-            self._fused_args = (key, buf)
-        buf = self._fused_args[1]
-        stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-        if sessions:
-            if active.dtype != torch.uint8 or active.numel() != B or active.device != d:
-                raise ValueError(f"ChainTracker.step_fused: active must be ({B},) uint8 on {d}")
-            rig, n_rigs = (None, 1) if self.rig_of_chain is None else (self.rig_of_chain.data_ptr(), B)
-            _cabi.check(_cabi.load().mvmc_chain_run_sessions(C.byref(self.hp.skeleton), C.byref(buf), C.c_void_p(rig), n_rigs,
-                                                             C.c_void_p(active.data_ptr()), stream), "mvmc_chain_run_sessions")
-        else:
-            _cabi.check(_cabi.load().mvmc_chain_run(C.byref(self.hp.skeleton), C.byref(buf), stream), "mvmc_chain_run")
+            ints = dict(n_chains=B, chain_len=1, n_views=self.C, p_max=self.P, t_max=self.T, k_max=self.K, v_max=self.V,
+                        max_nfev_cold=self.nfev_cold, max_nfev_warm=self.nfev_warm, n_inits=3, seed_len=w["seed_table"].numel(),
+                        n_parts=1, force_big=0, hand_over=0)
+            state = {name: getattr(self, name) for name in self._STATE}
+            self._fused_args = (key, fill_chain_buffers(ints, dict(w, kps17=kps17, counts=counts, Pmats=Pm, Fmats=Fm, F2=F2, **state)))
+        if active is not None and (active.dtype != torch.uint8 or active.numel() != B or active.device != d):
+            raise ValueError(f"ChainTracker.step_fused: active must be ({B},) uint8 on {d}")
+        launch_chain(self.hp.skeleton, self._fused_args[1], d, self.rig_of_chain, 1 if self.rig_of_chain is None else B, active)
         # the launch zeroes its flag words: fold this frame's per-chain void words into the tracker's own (read by check())
+        void = ChainFlags(self.cflags, B).void
         self._void_pending = not fold_void
         if fold_void:
-            self.overflow |= w["flags"][B + 4:2 * B + 4]
+            self.overflow |= void
         return dict(members=w["members"], n_members=w["n_members"], status=w["status"], n_new=w["n_new"], ik_params=w["ik_params"],
-                    ik_joints=w["ik_joints"], ik_info=w["ik_info"], flags=w["flags"], void=w["flags"][B + 4:2 * B + 4], n_chains=B,
-                    chain_len=1)
+                    ik_joints=w["ik_joints"], ik_info=w["ik_info"], flags=w["flags"], void=void, n_chains=B, chain_len=1)
 
     def check(self) -> None:
         """Raise if a capacity was exceeded since the last call (synchronises), and clear the words: the report is per call, so a
         caller that restores the state it saved before the frame (snapshot / restore) can go on -- MvTracker.update_4d does, with a
         wider table.  The reference has no such caps, so a frame that hits one is not tracked the way the reference would."""
-        ov = int(self.overflow.max()) if self.overflow.numel() else 0
+        void, timeout = self.overflow.cpu().numpy(), 0
         if self._fused is not None:
-            B = self.B
-            fl = self._fused["flags"][B:B + 4].cpu().tolist()
-            self._fused["flags"][B:B + 4].zero_()
+            fl = ChainFlags(self.cflags, self.B)
+            host = fl.host()
+            fl.status.zero_()
+            timeout = host.timeout
             if self._void_pending:      # (step_fused(fold_void=False) left the frame's void words where the launch wrote them)
-                ov |= int(np.bitwise_or.reduce(self._fused["flags"][B + 4:2 * B + 4].cpu().numpy())) if B else 0
-                self._void_pending = False
-            if fl[0]:
-                raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
+                void = void | host.void
+        self._void_pending = False
         self.overflow.zero_()
-        if ov:
-            what = [m for bit, m in ((1, "a cluster, a member or a view block did not fit (k_max / v_max / the frame's poses)"),
-                                     (2, "more than t_max live tracklets"),
-                                     (4, "a graph larger than the association kernel holds"),
-                                     (8, "internal: a meeting of two IK waves timed out (mvmc_ik_pair.h)")) if ov & bit]
-            raise ValueError("ChainTracker: capacity exceeded (" + "; ".join(what) + "): the frame's results are void")
+        _raise_if_void(timeout, void, "ChainTracker")
 
     _STATE = ("params", "joints", "meta", "n_tracks", "next_id", "n_dead", "slot_src")
 
@@ -267,70 +348,63 @@ class ChainTracker:
         self.overflow.zero_()
 
     def read_back(self, raise_on_void: bool = True):
-        """The state on the host after ONE transfer and ONE synchronisation (the per-frame driver's end of frame: check() and four
-        tensor reads took six round trips): dict of NumPy views (params, joints, meta, n_tracks, ..., overflow, cflags) of one of two
-        pinned buffers (the call after next overwrites it).  Raises like check(); the words that made it raise are cleared on the device
-        (nothing is cleared on a frame that went through: the next launch zeroes its own words).
-        raise_on_void=False (the live session pool): a void chain does not raise -- out["void"] holds every chain's void word (the
-        launch's, or'ed with the tracker's own), the mirror is marked good all the same, and the caller brings the void chains' rows
-        back with restore_rows().  A hand-over time-out still raises."""
+        """The state on the host after ONE transfer and ONE synchronisation (the per-frame driver's end of frame): dict of NumPy views
+        (params, joints, meta, n_tracks, ..., overflow, cflags) of one of two pinned buffers (the call after next overwrites it), and
+        ``void``: every chain's void word, the launch's or'ed with the tracker's own.  Raises like check() if one is set; the words
+        that made it raise are cleared on the device (nothing is cleared on a frame that went through: the next launch zeroes its own).
+        raise_on_void=False (the live session pool): a void chain does not raise -- the mirror is marked good all the same, and the
+        caller brings the chains of non-zero out["void"] back with restore_rows().  A hand-over time-out still raises."""
         n, B = self._flat.numel(), self.B
         if self._host is None:
-            # two pinned mirrors, written alternately: the one NOT written by this call holds the state after the last frame that went
-            # through, i.e. the state in front of this one -- what restore_previous() brings back without a per-frame device snapshot
             self._host = [torch.empty((n,), dtype=torch.uint8).pin_memory() for _ in range(2)]
-            self._host_good = -1         # index of the mirror that holds the last good state (-1: none yet)
         cur = 1 - self._host_good if self._host_good >= 0 else 0
         self._host_prev = self._host_good
         h = self._host[cur]
         h[:n].copy_(self._flat, non_blocking=True)          # (state AND the chain kernel's flag words: `cflags` is part of _flat)
-        fl = self.cflags[B:2 * B + 4] if self._fused is not None else None
         torch.cuda.current_stream(self._flat.device).synchronize()
-        out = {name: h[o:o + nb].view(dt).view(shape).numpy() for name, (o, nb, shape, dt) in self._layout.items()}
-        words = out["cflags"][B:2 * B + 4] if fl is not None else None
-        if not raise_on_void:
-            void = out["overflow"].copy()
-            if words is not None and self._void_pending:
-                void |= words[4:]
-            out["void"] = void
-            self._void_pending = False
-            if void.any():
-                self.overflow.zero_()
-            if words is not None and int(words[0]):
-                fl.zero_()
-                raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
-            self._host_good = cur
-            return out
-        ov = int(out["overflow"].max()) if out["overflow"].size else 0
-        if words is not None and self._void_pending:
-            ov |= int(np.bitwise_or.reduce(words[4:])) if B else 0       # (step_fused(fold_void=False): read where the launch left them)
-            self._void_pending = False
+        out = {name: self._field(h, name).numpy() for name in self._layout}
+        void, timeout = out["overflow"].copy(), 0
+        if self._fused is not None:
+            host = ChainFlags(out["cflags"], B)
+            timeout = host.timeout
+            if self._void_pending:      # (step_fused(fold_void=False): read where the launch left them)
+                void |= host.void
+        self._void_pending = False
+        out["void"] = void
         # clear what was set -- on the device only when something WAS set (the next launch zeroes its own words anyway): the common
         # frame ends with one transfer, one synchronisation and no further kernel
-        if ov:
+        if timeout or void.any():
             self.overflow.zero_()
-        if words is not None and int(words[0]):
-            fl.zero_()
-            raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
-        if ov:
-            what = [m for bit, m in ((1, "a cluster, a member or a view block did not fit (k_max / v_max / the frame's poses)"),
-                                     (2, "more than t_max live tracklets"),
-                                     (4, "a graph larger than the association kernel holds"),
-                                     (8, "internal: a meeting of two IK waves timed out (mvmc_ik_pair.h)")) if ov & bit]
-            raise ValueError("ChainTracker: capacity exceeded (" + "; ".join(what) + "): the frame's results are void")
+            if timeout:
+                fl = ChainFlags(self.cflags, B)
+                fl.status.zero_(); fl.void.zero_()
+            _raise_if_void(timeout, void if raise_on_void else void[:0], "ChainTracker")
         self._host_good = cur
         return out
 
     @property
     def has_previous(self) -> bool:
         """Whether read_back() has left a host mirror of the state after the last good frame (restore_previous())."""
-        return self._host is not None and self._host_good >= 0
+        return self._host_good >= 0
 
     def restore_previous(self) -> None:
         """The state after the last frame that read_back() returned for -- the state in front of a frame that has just failed --
         back onto the device, from the pinned mirror (the per-frame driver then needs no device snapshot in front of every frame)."""
         self._flat.copy_(self._host[self._host_good][:self._flat.numel()], non_blocking=True)
         self.overflow.zero_()
+
+    def _write_rows(self, rows, source) -> None:
+        """Rows ``rows`` of every state field and of the overflow word := source(name, shape of the rows, dtype), a host tensor -- on the
+        device and in the host mirror marked good, if there is one."""
+        rows_h = torch.from_numpy(rows)
+        rows_d = rows_h.to(self._flat.device)
+        good = self._host[self._host_good] if self.has_previous else None
+        for name in self._STATE + ("overflow",):
+            _, _, shape, dt = self._layout[name]
+            src = source(name, (rows.size,) + tuple(shape[1:]), dt)
+            getattr(self, name)[rows_d] = src.to(rows_d.device)
+            if good is not None:
+                self._field(good, name)[rows_h] = src
 
     def restore_rows(self, rows, snap: Optional[torch.Tensor] = None) -> None:
         """Per-chain restore_previous(), for a read_back(raise_on_void=False) that found some chains void: the rows of ``rows`` come back,
@@ -340,65 +414,46 @@ class ChainTracker:
         rows = np.asarray(rows, dtype=np.int64).reshape(-1)
         if rows.size == 0:
             return
-        if snap is None and (self._host is None or getattr(self, "_host_prev", -1) < 0):
+        if snap is None and self._host_prev < 0:
             raise ValueError("ChainTracker.restore_rows: no host mirror of an earlier frame and no snapshot")
-        d = self._flat.device
-        rows_d = torch.from_numpy(rows).to(d)
-        good = self._host[self._host_good] if self.has_previous else None
-        for name in self._STATE + ("overflow",):
-            o, nb, shape, dt = self._layout[name]
-            if name == "overflow":
-                src = torch.zeros((rows.size,), dtype=dt)
-            elif snap is not None:
-                src = snap[o:o + nb].view(dt).view(shape)[rows_d].cpu()
-            else:
-                src = self._host[self._host_prev][o:o + nb].view(dt).view(shape)[torch.from_numpy(rows)]
-            getattr(self, name)[rows_d] = src.to(d)
-            if good is not None:
-                good[o:o + nb].view(dt).view(shape)[torch.from_numpy(rows)] = src
+        before = snap if snap is not None else self._host[self._host_prev]
+        at = torch.from_numpy(rows).to(before.device)
+        self._write_rows(rows, lambda name, shape, dt: torch.zeros(shape, dtype=dt) if name == "overflow"
+                         else self._field(before, name)[at].cpu())
 
     def put_rows(self, rows, state: dict) -> None:
         """Rows ``rows`` of the state := ``state`` (field -> host array of len(rows) rows; fields not named are reset to a fresh
         tracker's: zeros, slot_src -1), on the device and in the host mirror marked good, if there is one."""
-        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
-        d = self._flat.device
-        rows_d = torch.from_numpy(rows).to(d)
-        good = self._host[self._host_good] if self.has_previous else None
-        for name in self._STATE + ("overflow",):
-            o, nb, shape, dt = self._layout[name]
-            if name in state:
-                src = torch.as_tensor(np.ascontiguousarray(state[name])).to(dt).reshape((rows.size,) + tuple(shape[1:]))
-            else:
-                src = torch.full((rows.size,) + tuple(shape[1:]), -1 if name == "slot_src" else 0, dtype=dt)
-            getattr(self, name)[rows_d] = src.to(d)
-            if good is not None:
-                good[o:o + nb].view(dt).view(shape)[torch.from_numpy(rows)] = src
+        self._write_rows(np.asarray(rows, dtype=np.int64).reshape(-1), lambda name, shape, dt:
+                         torch.as_tensor(np.ascontiguousarray(state[name])).to(dt).reshape(shape) if name in state
+                         else torch.full(shape, -1 if name == "slot_src" else 0, dtype=dt))
 
     def state_rows(self, rows) -> dict:
         """Rows ``rows`` of the device state (every field of _STATE) as host arrays (synchronises)."""
         idx = torch.as_tensor(np.asarray(rows, dtype=np.int64).reshape(-1)).to(self._flat.device)
         return {name: getattr(self, name)[idx].cpu().numpy() for name in self._STATE}
 
+    def _resized(self, t_max: int) -> "ChainTracker":
+        """A tracker of t_max tracklet slots (no rigs) holding this one's state, as many slots of it as both have."""
+        r = ChainTracker(self.hp, self.B, self.P, t_max, nfev_cold=self.nfev_cold, nfev_warm=self.nfev_warm)
+        T = min(self.T, t_max)
+        for name in ("params", "joints", "meta", "slot_src"):
+            getattr(r, name)[:, :T] = getattr(self, name)[:, :T]
+        for name in ("n_tracks", "next_id", "n_dead"):
+            getattr(r, name).copy_(getattr(self, name))
+        r.frame_idx = self.frame_idx
+        return r
+
     def widened(self, t_max: int) -> "ChainTracker":
         """A tracker with t_max tracklet slots (> the present number) holding this tracker's state."""
-        w = ChainTracker(self.hp, self.B, self.P, t_max, nfev_cold=self.nfev_cold, nfev_warm=self.nfev_warm)
-        T = self.T
-        w.params[:, :T], w.joints[:, :T], w.meta[:, :T], w.slot_src[:, :T] = self.params, self.joints, self.meta, self.slot_src
-        w.n_tracks.copy_(self.n_tracks); w.next_id.copy_(self.next_id); w.n_dead.copy_(self.n_dead)
-        w.frame_idx = self.frame_idx
-        return w
+        return self._resized(t_max)
 
     def narrowed(self, t_max: int) -> "ChainTracker":
-        """The inverse of widened(): a tracker with t_max slots holding this one's first t_max (the caller has checked that no chain
-        has more live tracklets than that) -- back on the tables the chain kernel runs on once a crowded scene has thinned out."""
+        """The inverse of widened(): a tracker with t_max slots holding this one's first t_max (no chain may have more live tracklets
+        than that) -- back on the tables the chain kernel runs on once a crowded scene has thinned out."""
         if int(self.n_tracks.max()) > t_max:      # (live tracklets occupy the first n_tracks slots: track_commit compacts the table)
             raise ValueError(f"ChainTracker.narrowed: a chain has more than {t_max} live tracklets")
-        n = ChainTracker(self.hp, self.B, self.P, t_max, nfev_cold=self.nfev_cold, nfev_warm=self.nfev_warm)
-        n.params.copy_(self.params[:, :t_max]); n.joints.copy_(self.joints[:, :t_max]); n.meta.copy_(self.meta[:, :t_max])
-        n.slot_src.copy_(self.slot_src[:, :t_max])
-        n.n_tracks.copy_(self.n_tracks); n.next_id.copy_(self.next_id); n.n_dead.copy_(self.n_dead)
-        n.frame_idx = self.frame_idx
-        return n
+        return self._resized(t_max)
 
     @property
     def fused_ok(self) -> bool:
@@ -497,8 +552,6 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
     rigs / rig_of_chain: a calibration per chain (mvmc_chain_run_rigs) -- ``rigs`` is a sequence of HotPath, one per rig, all with the
     cameras of ``kps``; chain b uses rigs[rig_of_chain[b]] (a host integer array of length B, checked here).  ``hp`` still supplies the
     skeleton.  With rigs=None the call is exactly the one-rig launch (mvmc_chain_run)."""
-    import ctypes as C
-    from . import _cabi
     F, Cn, P = kps.shape[:3]
     L = chain_len
     if F % L:
@@ -509,74 +562,53 @@ def run_chains_fused(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tens
     roc = None if rigs is None else check_rig_of_chain(rig_of_chain, B, len(rigs))
     if parts is None:
         parts = L   # one workgroup per chain-frame: the finest hand-over, the best balance
-    # tracklet slots: 8 on the SMALL layout (views x people <= 40: its association variants hold rank 16), 16 on the BIG one (C8 P8),
-    # whose workgroup takes a frame with a ninth tracklet (rank 18, 73 nodes) through its generic association variant in place
-    T = t_max if t_max is not None else (T_WIDE if Cn * P > 40 else 8)
-    k_def, v_def = default_caps(Cn, P)
-    K = k_max or k_def
-    V = v_max or v_def
-    N, NS, NP = Cn * P, T + Cn * P, T + K
-    kps17, cnt = dev.ingest(kps, counts)
-    d = kps.device
-    if rigs is None:
-        Pm, Fm, F2 = hp.P, hp.F, dev.fmats_from_projections(hp.P)
-    else:
-        Pm, Fm, F2 = stack_rigs(rigs, Cn)
-    seed = dev.als_seed_table(_cabi.MAX_NODES * _cabi.MAX_NODES, d)
-    f64, i32 = torch.float64, torch.int32
-    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)
-    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=d)
-    t = dict(
-        kps17=kps17, counts=cnt, Pmats=Pm, Fmats=Fm, F2=F2, seed_table=seed,
-        params=z((B, T, 68), f64), joints=z((B, T, 18, 3), f64), meta=z((B, T, 4), i32), n_tracks=z((B,), i32),
-        next_id=z((B,), i32), n_dead=z((B,), i32), slot_src=torch.full((B, T), -1, dtype=i32, device=d),
-        S_sp=e((B, N, N), torch.float32), W_st=e((B, NS, NS), f64), group_counts=e((B, Cn + 1), i32),
-        labels_sp=e((B, N), i32), labels_st=e((B, NS), i32), n_clusters_sp=z((B,), i32), n_clusters_st=z((B,), i32),
-        iters_sp=z((B,), i32), iters_st=z((B,), i32), members=e((B, NP, V), i32), n_members=z((B, NP), i32),
-        cold=e((B, NP), torch.uint8),
-        init=e((B, NP, 68), f64), status=e((B, T), i32), n_new=e((B,), i32), ik_params=e((B, NP, 68), f64),
-        ik_joints=e((B, NP, 18, 3), f64), ik_info=e((B, NP, 8), f64), ik_scratch=_chain_scratch(B, d),
-        out_params=e((F, T, 68), f64), out_joints=e((F, T, 18, 3), f64), out_meta=e((F, T, 4), i32), out_n_tracks=e((F,), i32),
-        out_info=e((F, NP, 8), f64) if want_info else None, out_als_iters=e((F,), i32) if want_info else None,
-        flags=z((B * (parts + 1) + 8,), torch.int32),
-        out_phase_cycles=e((B, 8), f64) if want_info else None)
     if parts > 1 and L % parts:
         raise ValueError("run_chains_fused: parts must divide the chain length")
     if hand_over is None:
         hand_over = "ticket"
     if hand_over not in ("static", "queue", "ticket"):
         raise ValueError("run_chains_fused: hand_over must be 'ticket', 'static' or 'queue'")
-    buf = _cabi.MvmcChainBuffers()
-    for name, val in dict(n_chains=B, chain_len=L, n_views=Cn, p_max=P, t_max=T, k_max=K, v_max=V, max_nfev_cold=nfev_cold,
-                          max_nfev_warm=nfev_warm, n_inits=3, seed_len=seed.numel(), n_parts=parts, force_big=int(force_big),
-                          hand_over={"static": 0, "queue": 1, "ticket": 2}[hand_over]).items():
-        setattr(buf, name, int(val))
-    for name, ten in t.items():
-        setattr(buf, name, None if ten is None else ten.data_ptr())
+    # tracklet slots: 8 on the SMALL layout (views x people <= 40: its association variants hold rank 16), 16 on the BIG one (C8 P8),
+    # whose workgroup takes a frame with a ninth tracklet (rank 18, 73 nodes) through its generic association variant in place
+    T = t_max if t_max is not None else (T_WIDE if Cn * P > 40 else 8)
+    k_def, v_def = default_caps(Cn, P)
+    K = k_max or k_def
+    V = v_max or v_def
+    kps17, cnt = dev.ingest(kps, counts)
+    d = kps.device
+    if rigs is None:
+        Pm, Fm, F2 = hp.P, hp.F, dev.fmats_from_projections(hp.P)
+    else:
+        Pm, Fm, F2 = stack_rigs(rigs, Cn)
+    f64, i32 = torch.float64, torch.int32
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=d)
+    t = dict(chain_workspace(B, F, Cn, P, T, K, V, d, want_info, ChainFlags.length(B, parts)),
+             kps17=kps17, counts=cnt, Pmats=Pm, Fmats=Fm, F2=F2,
+             params=z((B, T, 68), f64), joints=z((B, T, 18, 3), f64), meta=z((B, T, 4), i32), n_tracks=z((B,), i32),
+             next_id=z((B,), i32), n_dead=z((B,), i32), slot_src=torch.full((B, T), -1, dtype=i32, device=d))
+    ints = dict(n_chains=B, chain_len=L, n_views=Cn, p_max=P, t_max=T, k_max=K, v_max=V, max_nfev_cold=nfev_cold,
+                max_nfev_warm=nfev_warm, n_inits=3, seed_len=t["seed_table"].numel(), n_parts=parts, force_big=int(force_big),
+                hand_over={"static": 0, "queue": 1, "ticket": 2}[hand_over])
+    buf = fill_chain_buffers(ints, t)
     rig_dev = None if roc is None else torch.from_numpy(roc).to(d)
     if kernel_events is not None:
         k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         k0.record()
-    stream = C.c_void_p(torch.cuda.current_stream(d).cuda_stream)
-    if rigs is None:
-        _cabi.check(_cabi.load().mvmc_chain_run(C.byref(hp.skeleton), C.byref(buf), stream), "mvmc_chain_run")
-    else:
-        _cabi.check(_cabi.load().mvmc_chain_run_rigs(C.byref(hp.skeleton), C.byref(buf), C.c_void_p(rig_dev.data_ptr()), len(rigs),
-                                                     stream), "mvmc_chain_run_rigs")
-        t["rig_of_chain"] = rig_dev
+    launch_chain(hp.skeleton, buf, d, rig_dev, 1 if rigs is None else len(rigs))
     if kernel_events is not None:
         k1.record()
         kernel_events.append((k0, k1))
-    # void_words: {a hand-over timed out, a graph too large for the layout's association, a capacity exceeded} -- non-zero = the step is
+    # void_words: {a hand-over time-out, a graph too large for the layout's association, a capacity exceeded} -- non-zero = the step is
     # void unless repair_chains clears it; parallel.run_sharded sends them along, so every rank learns of a void step from the gathered
     # messages instead of each rank reading its own words back before the collective
+    fl = ChainFlags(t["flags"], B)
     res = dict(params=t["out_params"], joints=t["out_joints"], meta=t["out_meta"], n_tracks=t["out_n_tracks"],
-               n_dead=t["n_dead"], next_id=t["next_id"], flags=t["flags"], void=t["flags"][B + 4:2 * B + 4],
-               void_words=t["flags"][B:B + 3], n_chains=B, chain_len=L, _keepalive=t)
+               n_dead=t["n_dead"], next_id=t["next_id"], flags=t["flags"], void=fl.void, void_words=fl.status, n_chains=B,
+               chain_len=L, _keepalive=dict(t, rig_of_chain=rig_dev))
     if rigs is not None:
         res["rigs"], res["rig_of_chain"] = list(rigs), roc
     if want_info:
-        res["ik_info"] = t["out_info"].view(B, L, NP, 8)
+        res["ik_info"] = t["out_info"].view(B, L, T + K, 8)
         res["als_iters"] = t["out_als_iters"].view(B, L)
         res["phase_cycles"] = t["out_phase_cycles"]
     return res
@@ -616,32 +648,14 @@ def stack_rigs(rigs: Sequence[HotPath], n_views: int):
 
 
 def check_chain_flags(res) -> None:
-    """Raise if a run_chains_fused / run_chains result is void (synchronises): a hand-over timed out, a frame's graph was larger
-    than the chain kernel's association variant holds, or a capacity (t_max; k_max / v_max when the caller passed smaller ones than
-    default_caps) was exceeded -- the reference has no such caps.  repair_chains re-runs the chains concerned with wider tables."""
-    if "flags" not in res:      # run_chains: per-chain words {1: clusters / views, 2: tracklet table, 4: graph too large}
-        ov = int(res["overflow"].max()) if res["overflow"].numel() else 0
-        if ov:
-            raise ValueError(f"run_chains: capacity exceeded (word {ov}: 1 = k_max / v_max, 2 = t_max, 4 = graph larger than the "
-                             "association kernel holds): results are void")
+    """Raise if a run_chains_fused / run_chains result is void (synchronises), as void_verdict says: a hand-over time-out, a frame's
+    graph larger than the chain kernel's association variant holds, or a capacity (t_max; k_max / v_max when the caller passed smaller
+    ones than default_caps) exceeded.  repair_chains re-runs the chains concerned with wider tables."""
+    if "flags" not in res:      # run_chains: per-chain words of the same bits (CLUSTER, TRACKS, GRAPH), no hand-over
+        _raise_if_void(0, res["overflow"].cpu().numpy(), "run_chains")
         return
-    B = res["n_chains"]
-    fl = res["flags"][B:B + 4].cpu().tolist()
-    if fl[0]:
-        raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
-    void = res["flags"][B + 4:2 * B + 4]
-    ov = int(void.max()) if B else 0
-    if ov & 8:
-        raise RuntimeError("mvmc_chain_run: a meeting of two IK waves timed out (mvmc_ik_pair.h); results are void")
-    if ov & 16:
-        raise ValueError(f"mvmc_chain_run_rigs: the rig index of {int(((void & 16) != 0).sum())} chain(s) is outside [0, n_rigs): "
-                         "no calibration was read, their tables are empty")
-    if ov & 4:
-        raise ValueError("mvmc_chain_run: a frame's graph has more nodes than the chain kernel's layout supports (small layout: 24 "
-                         "without, 32 with tracklets); repair_chains / run_chains take such data")
-    if ov:
-        raise ValueError("mvmc_chain_run: capacity exceeded (" + ("a cluster, a member or a view block did not fit; " if ov & 1 else "")
-                         + ("more than t_max live tracklets" if ov & 2 else "") + f") in {int((void != 0).sum())} chain(s): their results are void")
+    fl = ChainFlags(res["flags"], res["n_chains"]).host()
+    _raise_if_void(fl.timeout, fl.void, "mvmc_chain_run")
 
 
 def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor], res, nfev_cold=50, nfev_warm=5,
@@ -650,21 +664,15 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
     more live tracklets than t_max, a graph beyond the layout's association variant -- are run again through the per-stage entry
     points with t_wide tracklet slots (association on up to 80 nodes, rank 32), and their rows of ``res`` (run_chains_fused's result,
     same kps / counts) are replaced; the per-frame tables are widened to the slots the repaired chains need.  Synchronises (it reads
-    the void words); returns the number of chains repaired.  Raises if a hand-over timed out or a chain exceeds the repair tier too.
+    the void words); returns the number of chains repaired.  Raises after a hand-over time-out or if a chain exceeds the repair tier too.
     big_first: chains voided by the SMALL layout go through the chain kernel's BIG layout first (one launch), see below.
     A result of several rigs (run_chains_fused(..., rigs, rig_of_chain)) is repaired with each chain's own calibration; a chain whose
-    rig index was out of range (void bit 4) has nothing to repair: raises."""
+    rig index was out of range (void bit RIG) has nothing to repair: raises."""
     B, L = res["n_chains"], res["chain_len"]
-    fl = res["flags"][B:B + 4].cpu().tolist()
-    if fl[0]:
-        raise RuntimeError("mvmc_chain_run: a hand-over between the workgroups of a chain timed out; results are void")
-    if fl[2] & 8:
-        raise RuntimeError("mvmc_chain_run: a meeting of two IK waves timed out (mvmc_ik_pair.h); results are void")
-    if fl[2] & 16:
-        raise ValueError("mvmc_chain_run_rigs: a chain's rig index is outside [0, n_rigs); such a chain is not repaired")
-    if not (fl[1] or fl[2]):
-        return 0
-    idx = torch.nonzero(res["void"]).flatten()
+    fl = ChainFlags(res["flags"], B)
+    host = fl.host()
+    _raise_if_void(host.timeout, host.void & ~ChainFlags.REPAIRABLE, "repair_chains")     # (what wider tables do not mend)
+    idx = torch.from_numpy(np.nonzero(host.void)[0]).to(res["flags"].device)
     n = int(idx.numel())
     if n == 0:
         return 0
@@ -682,8 +690,8 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
         # measured in tests/test_gpu_capacity_flags.py).  What is beyond that too falls through to the per-stage entry points below.
         big = run_chains_fused(hp, k5, c5, L, t_max=t_wide, nfev_cold=nfev_cold, nfev_warm=nfev_warm, force_big=True, rigs=rigs,
                                rig_of_chain=roc)
-        bfl = big["flags"][n:n + 4].cpu().tolist()
-        if not bfl[0] and int(big["void"].max()) == 0:
+        bh = ChainFlags(big["flags"], n).host()
+        if _verdict_of(bh.timeout, bh.void, "repair_chains") is None:
             sub = dict(params=big["params"], joints=big["joints"], meta=big["meta"], n_tracks=big["n_tracks"], n_dead=big["n_dead"],
                        next_id=big["next_id"])
     if sub is None:
@@ -691,10 +699,7 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
             sub = run_chains(hp, k5, c5, L, t_max=t_wide, nfev_cold=nfev_cold, nfev_warm=nfev_warm)
         else:
             sub = _run_chains_by_rig(rigs, roc, k5, c5, L, t_wide, nfev_cold, nfev_warm)
-        ov = int(sub["overflow"].max())
-        if ov:
-            raise ValueError(f"repair_chains: a chain exceeds the repair tier as well (word {ov}: 2 = more than {t_wide} live tracklets, "
-                             "4 = a graph of more than 80 nodes)")
+        _raise_if_void(0, sub["overflow"].cpu().numpy(), f"repair_chains: the repair tier (t_max = {t_wide}) as well")
     T = res["params"].shape[1]
     need = int(sub["n_tracks"].max())
     if need > T:   # widen the per-frame tables (rare: the repaired chains hold more tracklets than the tables have slots)
@@ -710,8 +715,8 @@ def repair_chains(hp: HotPath, kps: torch.Tensor, counts: Optional[torch.Tensor]
     res["n_tracks"].view(B, L)[idx] = sub["n_tracks"].view(n, L)
     res["n_dead"][idx] = sub["n_dead"]
     res["next_id"][idx] = sub["next_id"]
-    res["void"][idx] = 0
-    res["flags"][B + 1:B + 3] = 0
+    fl.void[idx] = 0
+    fl.status[1:] = 0      # (graph and capacity: mended)
     res["repaired"] = idx
     return n
 
@@ -742,14 +747,3 @@ def _run_chains_by_rig(rigs, roc: np.ndarray, kps: torch.Tensor, counts: Optiona
 
 
 _PER_FRAME = ("params", "joints", "meta", "n_tracks")
-_CHAIN_SCRATCH = {}
-
-
-def _chain_scratch(n_chains: int, d) -> torch.Tensor:
-    key = (str(d), torch.cuda.current_stream(d).cuda_stream)
-    buf = _CHAIN_SCRATCH.get(key)
-    if buf is None or buf.shape[0] < n_chains:
-        from . import _cabi
-        buf = torch.empty((n_chains, 8, _cabi.IK_SCRATCH_DOUBLES), dtype=torch.float64, device=d)
-        _CHAIN_SCRATCH[key] = buf
-    return buf

@@ -91,6 +91,23 @@ def test_idle_chains_write_nothing_and_active_chains_equal_a_launch_of_only_them
     assert torch.equal(tr.params[at], ref["params"][last]) and torch.equal(tr.meta[at], ref["meta"][last])
 
 
+def test_a_bad_rig_index_on_an_active_chain_is_named_by_check():
+    """Two chains of one frame (C5 P4), a rig per chain, both active, chain 1 with rig index 5 of 2: the kernel checks the index and
+    reads nothing; check() raises the ValueError that names the rig index, once (the report is per call)."""
+    from multiview_motion_capture_amd import device as dev, synth
+    from multiview_motion_capture_amd.pipeline import HotPath
+    from multiview_motion_capture_amd.tracker import ChainTracker
+    data = synth.generate(2, 5, 4, 20270501, chain_len=1)
+    hp = HotPath(data["K"], data["Rt"], device=D)
+    k17, c17 = dev.ingest(torch.from_numpy(data["kps25"]).to(D), torch.from_numpy(data["counts"]).to(D))
+    tr = ChainTracker(hp, 2, 4, rigs=[hp, hp])
+    tr.rig_of_chain[1] = 5
+    tr.step_fused(k17, c17, fold_void=False)
+    with pytest.raises(ValueError, match="rig index"):
+        tr.check()
+    tr.check()
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # 2. the pool against solo update_4d, tick by tick
 # ----------------------------------------------------------------------------------------------------------------------------------
