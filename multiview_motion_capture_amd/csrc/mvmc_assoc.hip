@@ -327,6 +327,117 @@ __device__ inline void gauss_jordan(double* M, int r, int ld) {
     }
 }
 
+// ---- what every form of the matcher shares: the head (graph size, rank, reject rule) and the tail (X_bin, closure, labels) ----
+// The forms below (als_gen_graph, als2_kernel, als4_graph, als5_graph) differ in their iteration only.
+struct AlsHead { int n, r; bool ok; };
+
+// Head: thread 0 walks the graph's group counts, fills sGid (node -> group) and publishes n = number of nodes and
+// r = min(n, 2 x largest group), the rank match_als works at (mv_association.py:255, 269).  A graph the form cannot hold (more nodes than
+// NMAX or the row width ldw, rank above RMAX, a seed table too short) is REJECTED: labels -1, n_clusters 0, iters -1 -- or iters 0 for
+// the empty graph -- and x_bin / match_mat left unwritten; ok is false and the caller returns.  Every thread of the NT-thread workgroup
+// must call it; a caller whose LDS may still be in use places its own barrier first.
+template <int NMAX, int RMAX, int NT>
+__device__ __forceinline__ AlsHead als_head(int* sGid, int& s_n, int& s_r, int f, const int32_t* __restrict__ gcounts, int G, int ldw,
+                                            int seed_len, int32_t* __restrict__ lab, int32_t* __restrict__ n_clusters,
+                                            int32_t* __restrict__ iters_out) {
+    const int tid = threadIdx.x;
+    if (tid == 0) {
+        int n = 0, total = 0, gmax = 0;
+        for (int g = 0; g < G; ++g) {
+            int c = gcounts[f * G + g];
+            c = c < 0 ? 0 : c;
+            total += c;
+            for (int k = 0; k < c && n < NMAX; ++k) sGid[n++] = g;
+            if (c > gmax) gmax = c;
+        }
+        s_n = total;
+        const int r = 2 * gmax;
+        s_r = r < total ? r : total;
+    }
+    __syncthreads();
+    const int n = s_n, r = s_r;
+    const bool ok = !(n == 0 || n > NMAX || n > ldw || r > RMAX || n * r > seed_len);
+    if (!ok) {
+        for (int i = tid; i < ldw; i += NT) lab[i] = -1;
+        if (tid == 0) { n_clusters[f] = 0; iters_out[f] = (n == 0) ? 0 : -1; }
+    }
+    return {n, r, ok};
+}
+
+// Tail, first piece: X_bin = (X + X^T) / 2 > 0.5 (mv_association.py:311-312) from the final X (n x n, row stride ldx) into the byte matrix
+// sBin (row stride n).  Ends on a barrier.
+template <int NT>
+__device__ __forceinline__ void als_binarise(const double* sX, int ldx, int n, uint8_t* sBin) {
+    for (int e = threadIdx.x; e < n * n; e += NT) {
+        const int i = e / n, j = e - i * n;
+        sBin[e] = (0.5 * (sX[i * ldx + j] + sX[j * ldx + i])) > 0.5;
+    }
+    __syncthreads();
+}
+
+// Tail, second piece: closure and labels of graph f from its binary matrix bin (n x n, row stride ldb: sBin of als_binarise with ldb = n,
+// or -- ANY_NONZERO -- a caller's matrix in global memory in which every non-zero byte counts as 1).
+//   * transform_closure (mv_association.py:99-121): of its loop over k only k = n-1 survives (mv_association.py:105-110), so
+//     temp = x_bin | (x_bin[:, n-1] & x_bin[n-1, :]); then every row not yet visited marks its members visited and becomes a column
+//     of match_mat;
+//   * the cluster rule of parse_match_result (motion_capture.py:419-425): columns with >= 2 members are kept, a node's label is the
+//     ordinal of the first kept column that holds it, -1 if none does; n_clusters = number of kept columns.
+// Writes lab[0 .. ldw) (-1 beyond n), n_clusters[f] and, where the pointers are given, the graph's ldw x ldw x_bin / match_mat (zero
+// outside n x n).  sTmp and sOut are n x n byte matrices, sVis n bytes, sKeep n ints of LDS; bin is complete on entry (a barrier passed).
+template <int NT, bool ANY_NONZERO = false>
+__device__ __forceinline__ void closure_labels(const uint8_t* bin, int ldb, int n, uint8_t* sTmp, uint8_t* sOut, uint8_t* sVis, int* sKeep,
+                                               int f, int ldw, int32_t* __restrict__ lab, int32_t* __restrict__ n_clusters,
+                                               uint8_t* __restrict__ x_bin, uint8_t* __restrict__ match_mat) {
+    auto b = [&](int i, int j) -> uint8_t { const uint8_t v = bin[i * ldb + j]; return ANY_NONZERO ? (uint8_t)(v != 0) : v; };
+    const int tid = threadIdx.x;
+    for (int e = tid; e < n * n; e += NT) {
+        const int i = e / n, j = e - i * n;
+        sOut[e] = 0;
+        sTmp[e] = b(i, j) | (b(i, n - 1) & b(n - 1, j));
+    }
+    for (int i = tid; i < n; i += NT) sVis[i] = 0;
+    __syncthreads();
+    for (int i = 0; i < n; ++i) {
+        const bool skip = sVis[i] != 0;
+        __syncthreads();
+        if (!skip)
+            for (int j = tid; j < n; j += NT)
+                if (sTmp[i * n + j]) { sVis[j] = 1; sOut[j * n + i] = 1; }
+        __syncthreads();
+    }
+    for (int c = tid; c < n; c += NT) {
+        int s = 0;
+        for (int j = 0; j < n; ++j) s += sOut[j * n + c];
+        sKeep[c] = s >= 2;
+    }
+    __syncthreads();
+    for (int row = tid; row < ldw; row += NT) {
+        int label = -1;
+        if (row < n) {
+            int ord = 0;
+            for (int c = 0; c < n; ++c) {
+                if (!sKeep[c]) continue;
+                if (sOut[row * n + c]) { label = ord; break; }
+                ++ord;
+            }
+        }
+        lab[row] = label;
+    }
+    if (tid == 0) {
+        int k = 0;
+        for (int c = 0; c < n; ++c) k += sKeep[c];
+        n_clusters[f] = k;
+    }
+    if (x_bin || match_mat) {
+        for (int e = tid; e < ldw * ldw; e += NT) {
+            const int i = e / ldw, j = e - i * ldw;
+            const bool in = i < n && j < n;
+            if (x_bin) x_bin[(size_t)f * ldw * ldw + e] = in ? b(i, j) : 0;
+            if (match_mat) match_mat[(size_t)f * ldw * ldw + e] = in ? sOut[i * n + j] : 0;
+        }
+    }
+}
+
 // LDS of the generic ALS (any n <= NMAX, rank <= RMAX): X1 as a dense matrix, both factors, the augmented normal matrix
 template <int NMAX, int RMAX, int NT>
 struct AlsGenLds {
@@ -357,27 +468,10 @@ __device__ __forceinline__ void als_gen_graph(AlsGenLds<NMAX, RMAX, NT>& L, int 
     const int tid = threadIdx.x;
     __syncthreads();   // the LDS may still be in use by the caller's previous phase
 
-    if (tid == 0) {
-        int n = 0, total = 0, gmax = 0;
-        for (int g = 0; g < G; ++g) {
-            int c = gcounts[f * G + g];
-            c = c < 0 ? 0 : c;
-            total += c;
-            for (int k = 0; k < c && n < NMAX; ++k) sGid[n++] = g;
-            if (c > gmax) gmax = c;
-        }
-        s_n = total;
-        int r = 2 * gmax;
-        s_r = r < total ? r : total;
-    }
-    __syncthreads();
-    const int n = s_n, r = s_r;
     int32_t* lab = labels + (size_t)f * ldw;
-    if (n == 0 || n > NMAX || n > ldw || r > RMAX || n * r > seed_len) {
-        for (int i = tid; i < ldw; i += NT) lab[i] = -1;
-        if (tid == 0) { n_clusters[f] = 0; iters_out[f] = (n == 0) ? 0 : -1; }
-        return;
-    }
+    const AlsHead hd = als_head<NMAX, RMAX, NT>(sGid, s_n, s_r, f, gcounts, G, ldw, seed_len, lab, n_clusters, iters_out);
+    if (!hd.ok) return;
+    const int n = hd.n, r = hd.r;
 
     // ---- per-thread element state (registers): W, Z, Y, previous X ----
     int ei[T], ej[T];
@@ -487,71 +581,19 @@ __device__ __forceinline__ void als_gen_graph(AlsGenLds<NMAX, RMAX, NT>& L, int 
         else if (d_res > 10 * p_res) mu = mu / 2;
     }
 
-    // ---- X_bin = (X + X^T)/2 > 0.5 ----  (sA / sB are free now: reuse them for the byte matrices)
+    // ---- tail (als_binarise, closure_labels): the final X to sX; sA / sB / sX are free in turn and hold the byte matrices ----
     static_assert(NMAX * NMAX <= NMAX * RMAX * 8, "byte matrices must fit the factor buffers");
     uint8_t* sBin = reinterpret_cast<uint8_t*>(sA);
     uint8_t* sOut = reinterpret_cast<uint8_t*>(sB);
+    uint8_t* sTmp = reinterpret_cast<uint8_t*>(sX);    // (sX is dead once sBin has been made)
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < T; ++t)
         if (ei[t] >= 0) sX[t * NT + tid] = xp[t];
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-        if (ei[t] >= 0) sBin[t * NT + tid] = (0.5 * (sX[ei[t] * n + ej[t]] + sX[ej[t] * n + ei[t]])) > 0.5;
-    __syncthreads();
-    // ---- transform_closure: only k = n-1 survives (mv_association.py:105-110) ----
-    for (int e = tid; e < n * n; e += NT) {
-        int i = e / n, j = e - i * n;
-        sOut[e] = 0;
-        // reuse the upper bits of sBin for temp to save LDS: bit0 = x_bin, bit1 = temp
-        uint8_t xb = sBin[e] & 1;
-        uint8_t tmpv = xb | ((sBin[i * n + (n - 1)] & 1) & (sBin[(n - 1) * n + j] & 1));
-        sX[e] = (double)tmpv;  // temp kept in sX (free now)
-    }
-    for (int i = tid; i < n; i += NT) sVis[i] = 0;
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-        const bool skip = sVis[i] != 0;
-        __syncthreads();
-        if (!skip)
-            for (int j = tid; j < n; j += NT)
-                if (sX[i * n + j] != 0.0) { sVis[j] = 1; sOut[j * n + i] = 1; }
-        __syncthreads();
-    }
-    // ---- parse_match_result rule: keep columns with >= 2 members, first kept column wins ----
-    for (int c = tid; c < n; c += NT) {
-        int s = 0;
-        for (int j = 0; j < n; ++j) s += sOut[j * n + c];
-        sKeep[c] = s >= 2;
-    }
-    __syncthreads();
-    for (int row = tid; row < ldw; row += NT) {
-        int label = -1;
-        if (row < n) {
-            int ord = 0;
-            for (int c = 0; c < n; ++c) {
-                if (!sKeep[c]) continue;
-                if (sOut[row * n + c]) { label = ord; break; }
-                ++ord;
-            }
-        }
-        lab[row] = label;
-    }
-    if (tid == 0) {
-        int k = 0;
-        for (int c = 0; c < n; ++c) k += sKeep[c];
-        n_clusters[f] = k;
-        iters_out[f] = iters;
-    }
-    if (x_bin || match_mat) {
-        for (int e = tid; e < ldw * ldw; e += NT) {
-            int i = e / ldw, j = e - i * ldw;
-            bool in = i < n && j < n;
-            if (x_bin) x_bin[(size_t)f * ldw * ldw + e] = in ? (sBin[i * n + j] & 1) : 0;
-            if (match_mat) match_mat[(size_t)f * ldw * ldw + e] = in ? sOut[i * n + j] : 0;
-        }
-    }
+    als_binarise<NT>(sX, n, n, sBin);
+    closure_labels<NT>(sBin, n, n, sTmp, sOut, sVis, sKeep, f, ldw, lab, n_clusters, x_bin, match_mat);
+    if (tid == 0) iters_out[f] = iters;
 }
 
 template <typename TW, int NMAX, int RMAX, int NT>
@@ -820,89 +862,25 @@ als2_kernel(const TW* __restrict__ W, const int32_t* __restrict__ gcounts, int G
     __shared__ int sKeep[NMAX];
     __shared__ int s_n, s_r;
     const int f = blockIdx.x, tid = threadIdx.x;
-    if (tid == 0) {
-        int n = 0, total = 0, gmax = 0;
-        for (int g = 0; g < G; ++g) {
-            int c = gcounts[f * G + g];
-            c = c < 0 ? 0 : c;
-            total += c;
-            for (int k = 0; k < c && n < NMAX; ++k) sGid[n++] = g;
-            if (c > gmax) gmax = c;
-        }
-        s_n = total;
-        const int r = 2 * gmax;
-        s_r = r < total ? r : total;
-    }
-    __syncthreads();
-    const int n = s_n, r = s_r;
     int32_t* lab = labels + (size_t)f * ldw;
-    if (n == 0 || n > NMAX || n > ldw || r > RMAX || n * r > seed_len) {
-        for (int i = tid; i < ldw; i += 64) lab[i] = -1;
-        if (tid == 0) { n_clusters[f] = 0; iters_out[f] = (n == 0) ? 0 : -1; }
-        return;
-    }
+    const AlsHead hd = als_head<NMAX, RMAX, 64>(sGid, s_n, s_r, f, gcounts, G, ldw, seed_len, lab, n_clusters, iters_out);
+    if (!hd.ok) return;
+    const int n = hd.n, r = hd.r;
     const TW* Wf = W + (size_t)f * ldw * ldw;
     const int iters = (r <= 8) ? als2_iterate<TW, NMAX, 8>(Wf, ldw, n, r, sGid, seed, sX, sA, sB, sG, sMul, sDinv)
                                : als2_iterate<TW, NMAX, 16>(Wf, ldw, n, r, sGid, seed, sX, sA, sB, sG, sMul, sDinv);
-    // ---- tail: X_bin, closure (k = n-1 only), labels -- same rules as als_kernel ----
+    // ---- tail (als_binarise, closure_labels): the factor buffers and sG are free now and hold the byte matrices ----
     uint8_t* sBin = reinterpret_cast<uint8_t*>(sA);
     uint8_t* sOut = reinterpret_cast<uint8_t*>(sB);
     uint8_t* sTmp = reinterpret_cast<uint8_t*>(sG);
     static_assert(NMAX * NMAX <= NMAX * RMAX * 8 && NMAX * NMAX <= RMAX * RMAX * 8, "byte matrices must fit");
-    for (int e = tid; e < n * n; e += 64) {
-        const int i = e / n, j = e - i * n;
-        sBin[e] = (0.5 * (sX[i * n + j] + sX[j * n + i])) > 0.5;
-    }
-    __syncthreads();
-    for (int e = tid; e < n * n; e += 64) {
-        const int i = e / n, j = e - i * n;
-        sOut[e] = 0;
-        sTmp[e] = sBin[e] | (sBin[i * n + (n - 1)] & sBin[(n - 1) * n + j]);
-    }
-    for (int i = tid; i < n; i += 64) sVis[i] = 0;
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-        const bool skip = sVis[i] != 0;
-        __syncthreads();
-        if (!skip)
-            for (int j = tid; j < n; j += 64)
-                if (sTmp[i * n + j]) { sVis[j] = 1; sOut[j * n + i] = 1; }
-        __syncthreads();
-    }
-    for (int c = tid; c < n; c += 64) {
-        int s = 0;
-        for (int j = 0; j < n; ++j) s += sOut[j * n + c];
-        sKeep[c] = s >= 2;
-    }
-    __syncthreads();
-    for (int row = tid; row < ldw; row += 64) {
-        int label = -1;
-        if (row < n) {
-            int ord = 0;
-            for (int c = 0; c < n; ++c) {
-                if (!sKeep[c]) continue;
-                if (sOut[row * n + c]) { label = ord; break; }
-                ++ord;
-            }
-        }
-        lab[row] = label;
-    }
+    als_binarise<64>(sX, n, n, sBin);
+    closure_labels<64>(sBin, n, n, sTmp, sOut, sVis, sKeep, f, ldw, lab, n_clusters, x_bin, match_mat);
     if (tid == 0) {
-        int k = 0;
-        for (int c = 0; c < n; ++c) k += sKeep[c];
-        n_clusters[f] = k;
         iters_out[f] = iters;
 #ifdef MVMC_ALS_PROFILE
         for (int q = 0; q < 7; ++q) lab[ldw - 7 + q] = (int)(g_alsprof[q] / iters);
 #endif
-    }
-    if (x_bin || match_mat) {
-        for (int e = tid; e < ldw * ldw; e += 64) {
-            const int i = e / ldw, j = e - i * ldw;
-            const bool in = i < n && j < n;
-            if (x_bin) x_bin[(size_t)f * ldw * ldw + e] = in ? sBin[i * n + j] : 0;
-            if (match_mat) match_mat[(size_t)f * ldw * ldw + e] = in ? sOut[i * n + j] : 0;
-        }
     }
 }
 
@@ -1581,91 +1559,28 @@ __device__ __forceinline__ void als4_graph(Als4Lds<NMAX>& L, int f, const TW* __
     int &s_n = L.s_n, &s_r = L.s_r;
     const int tid = threadIdx.x;
     __syncthreads();   // the arena may still be in use by the caller's previous phase
-    if (tid == 0) {
-        int n = 0, total = 0, gmax = 0;
-        for (int g = 0; g < G; ++g) {
-            int c = gcounts[f * G + g];
-            c = c < 0 ? 0 : c;
-            total += c;
-            for (int k = 0; k < c && n < NMAX; ++k) sGid[n++] = g;
-            if (c > gmax) gmax = c;
-        }
-        s_n = total;
-        const int r = 2 * gmax;
-        s_r = r < total ? r : total;
-    }
-    __syncthreads();
-    const int n = s_n, r = s_r;
     int32_t* lab = labels + (size_t)f * ldw;
-    if (n == 0 || n > NMAX || n > ldw || r > RMAX || n * r > seed_len) {
-        for (int i = tid; i < ldw; i += NT4) lab[i] = -1;
-        if (tid == 0) { n_clusters[f] = 0; iters_out[f] = (n == 0) ? 0 : -1; }
-        return;
-    }
+    const AlsHead hd = als_head<NMAX, RMAX, NT4>(sGid, s_n, s_r, f, gcounts, G, ldw, seed_len, lab, n_clusters, iters_out);
+    if (!hd.ok) return;
+    const int n = hd.n, r = hd.r;
     const TW* Wf = W + (size_t)f * ldw * ldw;
     const int iters = (r <= 8 && n <= 24) ? als7_iterate<TW, NMAX>(Wf, ldw, n, r, sGid, seed, sX, sA, sB, sG, sHp, sHp + 80, sRed)
                       : (r <= 8)          ? als4_iterate<TW, NMAX, 8>(Wf, ldw, n, r, sGid, seed, sX, sA, sB, sG, sMul, sDinv, sHp, sRed)
                                           : als4_iterate<TW, NMAX, 16>(Wf, ldw, n, r, sGid, seed, sX, sA, sB, sG, sMul, sDinv, sHp, sRed);
-    // ---- tail: X_bin, closure (k = n-1 only), labels -- same rules as als_kernel ----
+    // ---- tail (als_binarise, closure_labels): the factor buffers and sHp are free now and hold the byte matrices ----
     uint8_t* sBin = reinterpret_cast<uint8_t*>(sA);
     uint8_t* sOut = reinterpret_cast<uint8_t*>(sB);
     uint8_t* sTmp = reinterpret_cast<uint8_t*>(sHp);
-    for (int e = tid; e < n * n; e += NT4) {
-        const int i = e / n, j = e - i * n;
-        sBin[e] = (0.5 * (sX[i * n + j] + sX[j * n + i])) > 0.5;
-    }
-    __syncthreads();
-    for (int e = tid; e < n * n; e += NT4) {
-        const int i = e / n, j = e - i * n;
-        sOut[e] = 0;
-        sTmp[e] = sBin[e] | (sBin[i * n + (n - 1)] & sBin[(n - 1) * n + j]);
-    }
-    for (int i = tid; i < n; i += NT4) sVis[i] = 0;
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-        const bool skip = sVis[i] != 0;
-        __syncthreads();
-        if (!skip)
-            for (int j = tid; j < n; j += NT4)
-                if (sTmp[i * n + j]) { sVis[j] = 1; sOut[j * n + i] = 1; }
-        __syncthreads();
-    }
-    for (int c = tid; c < n; c += NT4) {
-        int s = 0;
-        for (int j = 0; j < n; ++j) s += sOut[j * n + c];
-        sKeep[c] = s >= 2;
-    }
-    __syncthreads();
-    for (int row = tid; row < ldw; row += NT4) {
-        int label = -1;
-        if (row < n) {
-            int ord = 0;
-            for (int c = 0; c < n; ++c) {
-                if (!sKeep[c]) continue;
-                if (sOut[row * n + c]) { label = ord; break; }
-                ++ord;
-            }
-        }
-        lab[row] = label;
-    }
+    static_assert(NMAX * NMAX <= NMAX * RMAX * 8, "byte matrices must fit");
+    als_binarise<NT4>(sX, n, n, sBin);
+    closure_labels<NT4>(sBin, n, n, sTmp, sOut, sVis, sKeep, f, ldw, lab, n_clusters, x_bin, match_mat);
     if (tid == 0) {
-        int k = 0;
-        for (int c = 0; c < n; ++c) k += sKeep[c];
-        n_clusters[f] = k;
         iters_out[f] = iters;
 #ifdef MVMC_ALS_PROFILE
         // diagnostic build: cycles per iteration by phase {X1, accumulate G+H, eliminate, apply, X/Z/Y, reduce, residuals}
         if (r <= 8 && n <= 24 && ldw >= 28) { for (int q = 0; q < 28; ++q) lab[q] = (int)(g_alsprof2[q] / iters); }
         else for (int q = 0; q < 7; ++q) lab[ldw - 7 + q] = (int)(g_alsprof[q] / iters);
 #endif
-    }
-    if (x_bin || match_mat) {
-        for (int e = tid; e < ldw * ldw; e += NT4) {
-            const int i = e / ldw, j = e - i * ldw;
-            const bool in = i < n && j < n;
-            if (x_bin) x_bin[(size_t)f * ldw * ldw + e] = in ? sBin[i * n + j] : 0;
-            if (match_mat) match_mat[(size_t)f * ldw * ldw + e] = in ? sOut[i * n + j] : 0;
-        }
     }
 }
 
@@ -1890,27 +1805,10 @@ __device__ __forceinline__ void als5_graph(Als5Lds<NMAX, WLDS>& L, int f, const 
     int &s_n = L.s_n, &s_r = L.s_r;
     const int tid = threadIdx.x, wave = tid >> 6;
     __syncthreads();   // the LDS may still be in use by the caller's previous phase
-    if (tid == 0) {
-        int n = 0, total = 0, gmax = 0;
-        for (int g = 0; g < G; ++g) {
-            int c = gcounts[f * G + g];
-            c = c < 0 ? 0 : c;
-            total += c;
-            for (int k = 0; k < c && n < NMAX; ++k) sGid[n++] = g;
-            if (c > gmax) gmax = c;
-        }
-        s_n = total;
-        const int r = 2 * gmax;
-        s_r = r < total ? r : total;
-    }
-    __syncthreads();
-    const int n = s_n, r = s_r;
     int32_t* lab = labels + (size_t)f * ldw;
-    if (n == 0 || n > NMAX || n > ldw || r > 16 || n * r > seed_len) {
-        for (int i = tid; i < ldw; i += NT5) lab[i] = -1;
-        if (tid == 0) { n_clusters[f] = 0; iters_out[f] = (n == 0) ? 0 : -1; }
-        return;
-    }
+    const AlsHead hd = als_head<NMAX, 16, NT5>(sGid, s_n, s_r, f, gcounts, G, ldw, seed_len, lab, n_clusters, iters_out);
+    if (!hd.ok) return;
+    const int n = hd.n, r = hd.r;
     const TW* Wf = W + (size_t)f * ldw * ldw;
     // ---- element tiles ----
     const bool own = tid < 24 * 18;
@@ -2214,7 +2112,7 @@ __device__ __forceinline__ void als5_graph(Als5Lds<NMAX, WLDS>& L, int f, const 
             A5PROF(1)
         }
     }
-    // ---- tail: X_bin = (X + X^T) / 2 > 0.5, closure (k = n-1 only), labels -- same rules as als_kernel ----
+    // ---- tail (als_binarise, closure_labels): the final X to sX; the factor buffers and sH are free now and hold the byte matrices ----
     if (wave == SOLVER) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     if (own) {
@@ -2227,62 +2125,16 @@ __device__ __forceinline__ void als5_graph(Als5Lds<NMAX, WLDS>& L, int f, const 
     uint8_t* sBin = reinterpret_cast<uint8_t*>(sA);
     uint8_t* sOut = reinterpret_cast<uint8_t*>(sB);
     uint8_t* sTmp = reinterpret_cast<uint8_t*>(sH);
+    static_assert(NMAX * NMAX <= NMAX * FS * 8 && NMAX * NMAX <= 16 * LD * 8, "byte matrices must fit");
     __syncthreads();
-    for (int e = tid; e < n * n; e += NT5) {
-        const int i = e / n, j = e - i * n;
-        sBin[e] = (0.5 * (sX[i * LD + j] + sX[j * LD + i])) > 0.5;
-    }
-    __syncthreads();
-    for (int e = tid; e < n * n; e += NT5) {
-        const int i = e / n, j = e - i * n;
-        sOut[e] = 0;
-        sTmp[e] = sBin[e] | (sBin[i * n + (n - 1)] & sBin[(n - 1) * n + j]);
-    }
-    for (int i = tid; i < n; i += NT5) sVis[i] = 0;
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-        const bool skip = sVis[i] != 0;
-        __syncthreads();
-        if (!skip)
-            for (int j = tid; j < n; j += NT5)
-                if (sTmp[i * n + j]) { sVis[j] = 1; sOut[j * n + i] = 1; }
-        __syncthreads();
-    }
-    for (int c = tid; c < n; c += NT5) {
-        int sc = 0;
-        for (int j = 0; j < n; ++j) sc += sOut[j * n + c];
-        sKeep[c] = sc >= 2;
-    }
-    __syncthreads();
-    for (int row = tid; row < ldw; row += NT5) {
-        int label = -1;
-        if (row < n) {
-            int ord = 0;
-            for (int c = 0; c < n; ++c) {
-                if (!sKeep[c]) continue;
-                if (sOut[row * n + c]) { label = ord; break; }
-                ++ord;
-            }
-        }
-        lab[row] = label;
-    }
+    als_binarise<NT5>(sX, LD, n, sBin);
+    closure_labels<NT5>(sBin, n, n, sTmp, sOut, sVis, sKeep, f, ldw, lab, n_clusters, x_bin, match_mat);
     if (tid == 0) {
-        int k = 0;
-        for (int c = 0; c < n; ++c) k += sKeep[c];
-        n_clusters[f] = k;
         iters_out[f] = iters;
 #ifdef MVMC_ALS_PROFILE
         // diagnostic build: cycles per iteration {X1, barrier, H (wave 0) | G + inverse (wave 3), barrier wait, apply + barrier, X/Z/Y, reduce}
         for (int q = 0; q < 16; ++q) lab[q] = (int)(prof5[q] / iters);
 #endif
-    }
-    if (x_bin || match_mat) {
-        for (int e = tid; e < ldw * ldw; e += NT5) {
-            const int i = e / ldw, j = e - i * ldw;
-            const bool in = i < n && j < n;
-            if (x_bin) x_bin[(size_t)f * ldw * ldw + e] = in ? sBin[i * n + j] : 0;
-            if (match_mat) match_mat[(size_t)f * ldw * ldw + e] = in ? sOut[i * n + j] : 0;
-        }
     }
 }
 
@@ -2308,53 +2160,12 @@ closure_kernel(const uint8_t* __restrict__ x_bin, const int32_t* __restrict__ n_
     __shared__ uint8_t sO[MVMC_MAX_NODES * MVMC_MAX_NODES];
     __shared__ uint8_t sVis[MVMC_MAX_NODES];
     __shared__ int sKeep[MVMC_MAX_NODES];
-    const int f = blockIdx.x, tid = threadIdx.x;
+    const int f = blockIdx.x;
     int n = n_nodes[f];
     n = n < 0 ? 0 : (n > ld ? ld : n);
-    const uint8_t* xb = x_bin + (size_t)f * ld * ld;
-    for (int e = tid; e < n * n; e += 64) {
-        const int i = e / n, j = e - i * n;
-        sT[e] = (xb[i * ld + j] != 0) | ((xb[i * ld + (n - 1)] != 0) & (xb[(n - 1) * ld + j] != 0));
-        sO[e] = 0;
-    }
-    for (int i = tid; i < n; i += 64) sVis[i] = 0;
-    __syncthreads();
-    for (int i = 0; i < n; ++i) {
-        const bool skip = sVis[i] != 0;
-        __syncthreads();
-        if (!skip)
-            for (int j = tid; j < n; j += 64)
-                if (sT[i * n + j]) { sVis[j] = 1; sO[j * n + i] = 1; }
-        __syncthreads();
-    }
-    for (int c = tid; c < n; c += 64) {
-        int s = 0;
-        for (int j = 0; j < n; ++j) s += sO[j * n + c];
-        sKeep[c] = s >= 2;
-    }
-    __syncthreads();
-    for (int row = tid; row < ld; row += 64) {
-        int label = -1;
-        if (row < n) {
-            int ord = 0;
-            for (int c = 0; c < n; ++c) {
-                if (!sKeep[c]) continue;
-                if (sO[row * n + c]) { label = ord; break; }
-                ++ord;
-            }
-        }
-        labels[(size_t)f * ld + row] = label;
-    }
-    if (tid == 0) {
-        int k = 0;
-        for (int c = 0; c < n; ++c) k += sKeep[c];
-        n_clusters[f] = k;
-    }
-    if (match_mat)
-        for (int e = tid; e < ld * ld; e += 64) {
-            const int i = e / ld, j = e - i * ld;
-            match_mat[(size_t)f * ld * ld + e] = (i < n && j < n) ? sO[i * n + j] : 0;
-        }
+    // (the caller's matrix: closure_labels<., true> takes any non-zero byte as a 1)
+    closure_labels<64, true>(x_bin + (size_t)f * ld * ld, ld, n, sT, sO, sVis, sKeep, f, ld, labels + (size_t)f * ld, n_clusters, nullptr,
+                             match_mat);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2433,21 +2244,14 @@ extern "C" int mvmc_affinity(const double* kps17, const int32_t* counts, const f
 template <typename TW>
 static int launch_als(const TW* W, const int32_t* gc, int F, int G, int n_max, int r_max, const double* seed,
                       int seed_len, uint8_t* xb, uint8_t* mm, int32_t* lab, int32_t* nc, int32_t* it, hipStream_t s) {
-#define MVMC_ALS(NM, RM, NT)                                                                              \
-    do {                                                                                                  \
-        const size_t lds = sizeof(AlsGenLds<NM, RM, NT>);                                                 \
-        if (lds > 65536 && hipFuncSetAttribute((const void*)als_kernel<TW, NM, RM, NT>,                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return MVMC_ERR_LAUNCH;                                                                       \
-        hipLaunchKernelGGL((als_kernel<TW, NM, RM, NT>), dim3(F), dim3(NT), lds, s, W, gc, G, n_max, seed, \
-                           seed_len, xb, mm, lab, nc, it);                                                \
-    } while (0)
-#define MVMC_ALS2(NM)                                                                                     \
-    hipLaunchKernelGGL((als2_kernel<TW, NM>), dim3(F), dim3(64), 0, s, W, gc, G, n_max, seed, seed_len, xb, mm, \
-                       lab, nc, it)
-#define MVMC_ALS4(NM)                                                                                     \
-    hipLaunchKernelGGL((als4_kernel<TW, NM>), dim3(F), dim3(256), 0, s, W, gc, G, n_max, seed, seed_len, xb, mm, \
-                       lab, nc, it)
+    // one launch of F workgroups of nt threads with lds bytes of dynamic LDS; above 64 KB the kernel has to be told first
+    auto launch = [&](void (*kernel)(const TW*, const int32_t*, int, int, const double*, int, uint8_t*, uint8_t*, int32_t*, int32_t*, int32_t*),
+                      int nt, size_t lds) -> int {
+        if (lds > 65536 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return MVMC_ERR_LAUNCH;
+        hipLaunchKernelGGL(kernel, dim3(F), dim3(nt), lds, s, W, gc, G, n_max, seed, seed_len, xb, mm, lab, nc, it);
+        return MVMC_OK;
+    };
     // WHICH VARIANT A CALL REACHES (n = n_max nodes, r = r_max = min(n, 2 g_max), F graphs in the launch) -- every one is reached:
     //   n <= 32, r <= 16, F <= 4096   als4_kernel<., 24 | 32>   one 256-thread workgroup per graph; inside it rank <= 8 and n <= 24 (every
     //     or n <= 24, r <= 8, any F    graph of configs 1-4) run als7_iterate (solver wave + three worker waves), the rest als4_iterate.
@@ -2468,24 +2272,17 @@ static int launch_als(const TW* W, const int32_t* gc, int F, int G, int n_max, i
     // (round 4: graphs the solver-wave form als7_iterate holds -- n <= 24, rank <= 8 -- take the workgroup kernel at ANY batch size: 512
     // graphs resident at 7.4 k cycles per iteration beat als2's 1,024 at ~20 k; config 3, 10 k graphs: 484 k -> 642 k frames/s)
     const bool few = F <= 4096 || (n_max <= 24 && r_max <= 8);
-    if (n_max <= 24 && r_max <= 16) { if (few) MVMC_ALS4(24); else MVMC_ALS2(24); }
-    else if (n_max <= 32 && r_max <= 16) { if (few) MVMC_ALS4(32); else MVMC_ALS2(32); }
-    else if (n_max <= 24) MVMC_ALS(24, 24, 64);
-    else if (n_max <= 32) MVMC_ALS(32, 32, 128);
-    else if (n_max <= 72 && r_max <= 16 && few) {   // config 5 (C8 P8, + 8 tracklets): the workgroup form the chain kernel's BIG layout runs
-        const size_t lds = sizeof(Als5Lds<72>);
-        if (hipFuncSetAttribute((const void*)als5_kernel<TW, 72>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MVMC_ERR_LAUNCH;
-        hipLaunchKernelGGL((als5_kernel<TW, 72>), dim3(F), dim3(512), lds, s, W, gc, G, n_max, seed, seed_len, xb, mm, lab, nc, it);
-    }
-    else if (n_max <= 64 && r_max <= 16) MVMC_ALS(64, 16, 256);
-    else if (n_max <= 80 && r_max <= 16) MVMC_ALS(80, 16, 512);
-    else if (n_max <= 80) MVMC_ALS(80, 32, 512);   // up to 16 groups members (the repair tier's 16 tracklet slots): 121 KB of LDS
-    else return MVMC_ERR_UNSUPPORTED;
-#undef MVMC_ALS
-#undef MVMC_ALS2
-#undef MVMC_ALS4
-    return MVMC_OK;
+    if (n_max <= 24 && r_max <= 16) return few ? launch(als4_kernel<TW, 24>, 256, 0) : launch(als2_kernel<TW, 24>, 64, 0);
+    if (n_max <= 32 && r_max <= 16) return few ? launch(als4_kernel<TW, 32>, 256, 0) : launch(als2_kernel<TW, 32>, 64, 0);
+    if (n_max <= 24) return launch(als_kernel<TW, 24, 24, 64>, 64, sizeof(AlsGenLds<24, 24, 64>));
+    if (n_max <= 32) return launch(als_kernel<TW, 32, 32, 128>, 128, sizeof(AlsGenLds<32, 32, 128>));
+    // config 5 (C8 P8, + 8 tracklets): the workgroup form the chain kernel's BIG layout runs
+    if (n_max <= 72 && r_max <= 16 && few) return launch(als5_kernel<TW, 72>, 512, sizeof(Als5Lds<72>));
+    if (n_max <= 64 && r_max <= 16) return launch(als_kernel<TW, 64, 16, 256>, 256, sizeof(AlsGenLds<64, 16, 256>));
+    if (n_max <= 80 && r_max <= 16) return launch(als_kernel<TW, 80, 16, 512>, 512, sizeof(AlsGenLds<80, 16, 512>));
+    // up to 16 group members (the repair tier's 16 tracklet slots): 121 KB of LDS
+    if (n_max <= 80) return launch(als_kernel<TW, 80, 32, 512>, 512, sizeof(AlsGenLds<80, 32, 512>));
+    return MVMC_ERR_UNSUPPORTED;
 }
 
 extern "C" int mvmc_als_associate(const void* W, int w_dtype, const int32_t* group_counts, int n_frames,

@@ -226,9 +226,10 @@ def transform_closure(x_bin):
     return out
 
 
-def match_als(W, dim_group, return_iters=False):
+def match_als(W, dim_group, return_iters=False, return_x=False):
     """mv_association.py:222-318.  Dtype propagation follows NumPy exactly:
-    a float32 W (from geometry_affinity) keeps iteration 1's X update in f32."""
+    a float32 W (from geometry_affinity) keeps iteration 1's X update in f32.
+    return_x appends the symmetrised X that x_bin thresholds (how far a graph's entries are from the 0.5 decision)."""
     dim_group = list(dim_group)
     n = W.shape[0]
     rank = min(n, int(max(np.diff(dim_group))) * 2)
@@ -265,9 +266,8 @@ def match_als(W, dim_group, return_iters=False):
     X = 0.5 * (X + X.T)
     x_bin = X > 0.5
     match_mat = transform_closure(x_bin)
-    if return_iters:
-        return match_mat, x_bin, iters
-    return match_mat, x_bin
+    out = (match_mat, x_bin, iters) if return_iters else (match_mat, x_bin)
+    return out + (X,) if return_x else out
 
 
 # ---- match_svt (mv_association.py:321-411) with its doubly-stochastic projection (:15-60) ----
