@@ -17,6 +17,8 @@ re-solves every frame's pose against it:
 
 Device code: csrc/mvmc_bodyfit.hip (include/mvmc.h: mvmc_body_observe, mvmc_body_lengths, mvmc_ik_solve_stages_rigs); NumPy
 restatement: tests/body_fit_np.py.  Sequences with the same number of cameras share every launch (one per step), each with its own rig.
+The input checks, the group stacking, step a and the record shells are sequences.py's (check_records, stack_group, select_views,
+pose_tuples / new_record), shared with smoothing and rig_refine.
 """
 from __future__ import annotations
 
@@ -26,7 +28,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .sequences import SequenceInput, check_sequences
+from .sequences import (SequenceInput, check_records, new_record, no_sequences, plan_groups, pose_slot, pose_tuples, select_views,
+                        stack_group, stopwatch)
 
 MIN_SCORE = 0.1
 MAX_DIST = 15.0 + 30.0 * math.log(999.0) / 5.0   # S = 1 / (1 + exp(5 (D - 15) / 30)) < 1e-3 is cut to 0 (mvmc_st_affinity)
@@ -36,37 +39,11 @@ LM_XTOL = 1e-10     # stop: |d|_inf below LM_XTOL m
 MAX_ITER_CAP = 12   # include/mvmc.h: MVMC_BODY_INFO_DOUBLES - 4
 
 
-def _record_arrays(rec, F: int, where: str):
-    """(frames (n,), params (n,68), joints (n,18,3)) of one MvTracklet record; ValueError where it does not fit."""
-    frames = np.asarray(rec.frame_idxs, dtype=np.int64)
-    poses = rec.poses
-    n = frames.shape[0]
-    if n == 0 or len(poses) != n:
-        raise ValueError(f"{where}: {n} frame indices and {len(poses)} poses")
-    if frames.min() < 0 or frames.max() >= F:
-        raise ValueError(f"{where}: frame {int(frames.max() if frames.max() >= F else frames.min())} outside the {F} frames of kps")
-    if np.unique(frames).shape[0] != n:
-        raise ValueError(f"{where}: a frame appears twice")
-    try:
-        root = np.array([np.asarray(p[1].root, np.float64).reshape(3) for p in poses])
-        ang = np.array([np.asarray(p[1].euler_angles, np.float64).reshape(54) for p in poses])
-        lens = np.array([np.asarray(p[1].bone_lens, np.float64).reshape(11) for p in poses])
-        joints = np.array([np.asarray(p[2].keypoints, np.float64).reshape(18, 3) for p in poses])
-    except (ValueError, AttributeError, TypeError) as e:
-        raise ValueError(f"{where}: poses must be (frame, PoseShapeParam (3 + 18x3 + 11), BASIC_18 Pose): {e}") from None
-    return frames, np.concatenate([root, ang, lens], axis=1), joints
-
-
 def _check(sequences, tracklets_per_sequence, rounds, max_iter, max_nfev):
-    if len(tracklets_per_sequence) != len(sequences):
-        raise ValueError(f"fit_sequences: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
-    if int(rounds) < 0 or not 0 <= int(max_iter) <= MAX_ITER_CAP or int(max_nfev) < 1:
-        raise ValueError(f"fit_sequences: rounds >= 0, 0 <= max_iter <= {MAX_ITER_CAP} and max_nfev >= 1 required")
-    shapes = check_sequences(sequences, "fit_sequences")
-    recs = []
-    for s, (tl, (F, _, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
-        recs.append([_record_arrays(t, F, f"sequence {s}, record {j}") for j, t in enumerate(tl)])
-    return shapes, recs
+    def own():
+        if int(rounds) < 0 or not 0 <= int(max_iter) <= MAX_ITER_CAP or int(max_nfev) < 1:
+            raise ValueError(f"fit_sequences: rounds >= 0, 0 <= max_iter <= {MAX_ITER_CAP} and max_nfev >= 1 required")
+    return check_records(sequences, tracklets_per_sequence, "fit_sequences", own)
 
 
 def fit_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], rounds: int = 3, max_iter: int = 10,
@@ -80,64 +57,24 @@ def fit_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Se
     ``fit_trials`` per round the length step's trials (1 accepted, 0 rejected).
     Sequences with the same camera count share one launch per step: selection, then per round the length step and the pose step.
     timings: a dict that receives the seconds spent in {"select", "length", "pose", "records"} (synchronising between the parts)."""
-    if len(sequences) == 0:
-        if len(tracklets_per_sequence):
-            raise ValueError("fit_sequences: records without sequences")
+    if no_sequences(sequences, tracklets_per_sequence, "fit_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence, rounds, max_iter, max_nfev)
     import torch
 
     from . import device as dev
     d = torch.device(device)
-    tm = {"select": 0.0, "length": 0.0, "pose": 0.0, "records": 0.0}
-
-    def lap(k, t0):
-        if timings is not None:
-            torch.cuda.synchronize(d)
-        t1 = time.perf_counter()
-        tm[k] += t1 - t0
-        return t1
-
+    T = dev.uploader(d)
+    lap, tm = stopwatch(timings, d, ("select", "length", "pose", "records"))
     out: List[list] = [[None] * len(r) for r in recs]
-    by_c = {}
-    for i, (_, C, _) in enumerate(shapes):
-        by_c.setdefault(C, []).append(i)
-    for C, ids in by_c.items():
-        items = [(i, j) for i in ids for j in range(len(recs[i]))]
-        if not items:
+    for lay in plan_groups(shapes, 1):
+        if not any(recs[i] for i in lay.seq_ids):
             continue
         t0 = time.perf_counter()
-        Pg = max(shapes[i][2] for i in ids)
-        f_off = np.concatenate([[0], np.cumsum([shapes[i][0] for i in ids])]).astype(np.int64)
-        ks = [np.asarray(sequences[i][0]) for i in ids]
-        dt = np.float32 if all(k.dtype == np.float32 for k in ks) else np.float64
-        kps = np.zeros((int(f_off[-1]), C, Pg, ks[0].shape[3], 3), dtype=dt)
-        cnt = np.zeros((int(f_off[-1]), C), dtype=np.int32)
-        for r, i in enumerate(ids):
-            kps[f_off[r]:f_off[r + 1], :, :ks[r].shape[2]] = ks[r]
-            cnt[f_off[r]:f_off[r + 1]] = np.asarray(sequences[i][1])
-        Pm = np.array([[np.asarray(c.P, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
-        rig_of_seq = {i: r for r, i in enumerate(ids)}
-        # problems in (sequence, record, frame) order
-        fr = [recs[i][j][0] for i, j in items]
-        n_of = np.array([f.shape[0] for f in fr], dtype=np.int64)
-        rec_lo = np.concatenate([[0], np.cumsum(n_of)]).astype(np.int64)
-        frame_of = np.concatenate([f + f_off[rig_of_seq[i]] for f, (i, _) in zip(fr, items)]).astype(np.int32)
-        rig_of = np.repeat(np.array([rig_of_seq[i] for i, _ in items], dtype=np.int32), n_of)
-        rank = np.repeat(np.array([j for _, j in items], dtype=np.int32), n_of)
-        params = np.concatenate([recs[i][j][1] for i, j in items])
-        joints = np.concatenate([recs[i][j][2] for i, j in items])
-        order = np.argsort(frame_of, kind="stable").astype(np.int32)
-        fs = frame_of[order]
-        lo = np.searchsorted(fs, frame_of, side="left").astype(np.int32)
-        hi = np.searchsorted(fs, frame_of, side="right").astype(np.int32)
-        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
-        k17, c17 = dev.ingest(T(kps), T(cnt))
-        Pm_d = T(Pm)
-        rig_d = T(rig_of)
-        members, n_views, _, _ = dev.body_observe(k17, c17, Pm_d, T(frame_of), rig_d, T(joints), T(order), T(lo), T(hi), T(rank),
-                                                  MAX_DIST, MIN_SCORE)
-        nv = n_views.cpu().numpy()
+        sel = select_views(stack_group(lay, sequences), recs, d, MAX_DIST, MIN_SCORE, want_params=True)
+        items, rec_lo, n_of, params, joints = sel.items, sel.rec_lo, sel.n_of, sel.params, sel.joints
+        k17, Pm_d, rig_d, members = sel.k17, sel.Pm_d, sel.rig_d, sel.members
+        nv = sel.n_views.cpu().numpy()
         t0 = lap("select", t0)
         live = nv >= 2
         # initial skeleton per identity, and the live problems of the identities that have any, identity by identity
@@ -205,11 +142,9 @@ def fit_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Se
         fk_rows = np.flatnonzero(need_fk)
         if fk_rows.size:
             joints_out[fk_rows] = dev.fk(T(params_out[fk_rows])).cpu().numpy()
-        # selected pose slot per camera (ingest order) or -1
-        mem_h = members.cpu().numpy().astype(np.int64)
-        sel = np.where(mem_h >= 0, mem_h % Pg, -1)
         views_used = np.where(live, nv, 0)
-        _records(out, items, recs, tracklets_per_sequence, rec_lo, params_out, joints_out, lens_fit, views_used, sel, costs, trials)
+        _records(out, items, recs, tracklets_per_sequence, rec_lo, params_out, joints_out, lens_fit, views_used,
+                 pose_slot(members.cpu().numpy(), sel.Pg), costs, trials)
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
@@ -218,25 +153,13 @@ def fit_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Se
 
 def _records(out, items, recs, tracklets_per_sequence, rec_lo, params, joints, lens, views, sel, costs, trials):
     """New MvTracklet records from the fitted tables (one slice per record; the per-frame objects built from whole arrays)."""
-    from .inverse_kinematics import PoseShapeParam
-    from .motion_capture import MvTracklet
-    from .pose_def import KpsFormat, Pose
-    trans, ang = params[:, :3].copy(), params[:, 3:57].reshape(-1, 18, 3).copy()
-    ones = np.ones((18, 1))
+    frames = np.concatenate([recs[i][j][0] for i, j in items])
+    poses = pose_tuples(frames, params, joints)
     for a, (i, j) in enumerate(items):
-        src = tracklets_per_sequence[i][j]
         lo, hi = int(rec_lo[a]), int(rec_lo[a + 1])
-        frm = recs[i][j][0].tolist()
-        L = lens[a].copy()
-        poses = [(frm[k], PoseShapeParam(trans[lo + k], ang[lo + k], L.copy()), Pose(KpsFormat.BASIC_18, joints[lo + k], ones.copy(), None))
-                 for k in range(hi - lo)]
-        t = MvTracklet(src.track_id, frm[0], poses[0][1], poses[0][2])
-        t.frame_idxs = list(frm)
-        t.poses = poses
-        t.state = src.state
-        t.hits = src.hits
-        t.time_since_update = getattr(src, "time_since_update", 0)
-        t.bone_lens = L
+        src = tracklets_per_sequence[i][j]
+        t = new_record(src.track_id, poses[lo:hi], src)
+        t.bone_lens = lens[a].copy()
         t.fit_views = views[lo:hi].astype(np.int32)
         t.fit_cost = costs[a].copy()
         t.fit_select = sel[lo:hi].astype(np.int32)

@@ -29,6 +29,11 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def uploader(device):
+    """-> T(a): the host array ``a`` (made contiguous) as a tensor on ``device``; the one upload helper of the record stages."""
+    return lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+
+
 def _req(t: torch.Tensor, dtype, name: str, shape=None):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise ValueError(f"{name}: expected a CUDA tensor")

@@ -5,7 +5,7 @@ Per identity (one tracklet of one session) the rows are the consecutive frames f
 is a DATA row when the tracker appended a pose for that frame (commit_tables' rule: the tracklet is new or its hits grew), else a
 MISSING row.  A data row starts from the tracker's 68 parameters, its Euler triples unwrapped (smoothing.unwrap_euler's rule) towards
 the unwrapped INPUT angles of the identity's previous data row, so that the stream of unwrapped inputs equals unwrap_euler of the
-complete record; its views are the body fit's selection (mvmc_body_observe on the tracker's joints, MAX_DIST, MIN_SCORE).  A missing row
+complete record; its views are sequences.select_views' selection (mvmc_body_observe on the tracker's joints, MAX_DIST, MIN_SCORE).  A missing row
 starts as a copy of the previous row's current values and has no data term.  A session whose frame index jumps by d gets d - 1 missing
 rows in every live identity.
 
@@ -28,6 +28,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 
 from .body_fit import MAX_DIST, MIN_SCORE
+from .sequences import frame_buckets, new_record, pose_slot, pose_tuples
 from .smoothing import ANG_ACC, ANG_VEL, LM_FTOL, LM_MU0, LM_XTOL, ROOT_ACC, ROOT_VEL, unwrap_euler_many
 from .tracker import T_WIDE
 
@@ -249,7 +250,7 @@ class LiveSmoother:
         from . import device as dev
         st = self._state()
         d, C, W = st["d"], self.C, self.W
-        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+        T = dev.uploader(d)
         # ---- host: the tick's rows, items and selection problems ----
         J = work[0][2].shape[2]
         kst = np.zeros((len(work), C, self.P, J, 3))
@@ -314,12 +315,9 @@ class LiveSmoother:
         B = len(newp)
         if B:
             frame_of = np.array([p[0] for p in prob], np.int32)
-            order = np.argsort(frame_of, kind="stable").astype(np.int32)
-            fs = frame_of[order]
+            order, lo, hi = frame_buckets(frame_of)
             mem_d, nv_d, _, _ = dev.body_observe(st["kps"], st["cnt"], st["Pm"], T(frame_of), T(np.array([p[1] for p in prob], np.int32)),
-                                                 T(np.array([p[2] for p in prob])), T(order),
-                                                 T(np.searchsorted(fs, frame_of, side="left").astype(np.int32)),
-                                                 T(np.searchsorted(fs, frame_of, side="right").astype(np.int32)),
+                                                 T(np.array([p[2] for p in prob])), T(order), T(lo), T(hi),
                                                  T(np.array([p[3] for p in prob], np.int32)), MAX_DIST, MIN_SCORE)
             newp_d = T(np.array([p for _, p in newp]))
         else:
@@ -352,9 +350,9 @@ class LiveSmoother:
         J_h = take(n_rows * 54, (n_rows, 18, 3))
         mem_h = take(B * C, (B, C)).astype(np.int64)
         nv_h = take(B, (B,)).astype(np.int64)
+        sel_h = pose_slot(mem_h, self.P)
         for b, (idn, _) in enumerate(newp):
-            idn.views[-1] = int(nv_h[b])
-            idn.sel[-1] = np.where(mem_h[b] >= 0, mem_h[b] % self.P, -1).astype(np.int32)
+            idn.views[-1], idn.sel[-1] = int(nv_h[b]), sel_h[b]
         got = {}
         for k, (idn, r) in enumerate(want_fin + want):
             got[(id(idn), r)] = k
@@ -365,6 +363,7 @@ class LiveSmoother:
                 idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
             idn.n_final = keep
             out[key].finished.append(self._record(idn, keep, 3))
+        emit = []
         for a, (key, idn, f) in enumerate(solved_of):
             for r in range(was_final[a], idn.n_final):
                 k = got[(id(idn), r)]
@@ -376,8 +375,11 @@ class LiveSmoother:
                 out[key].solved[idn.tid] = dict(cost=inf_h[a, :4].copy(), trials=[int(v) for v in inf_h[a, 8:8 + n_t]], stop=int(inf_h[a, 7]))
             r = f - self.lag - idn.f0
             if r >= 0:
-                k = got[(id(idn), r)]
-                out[key].emitted.append((idn.tid, f - self.lag) + self._pose(P_h[k], J_h[k]) + (bool(idn.filled[r]), int(idn.views[r])))
+                emit.append((key, idn.tid, f - self.lag, got[(id(idn), r)], bool(idn.filled[r]), int(idn.views[r])))
+        if emit:      # the tick's emitted poses in one pass
+            ks = [e[3] for e in emit]
+            for (key, tid, _, _, filled, views), pose in zip(emit, pose_tuples([e[2] for e in emit], P_h[ks], J_h[ks])):
+                out[key].emitted.append((tid,) + pose + (filled, views))
         t_end = time.perf_counter()
         self.timings["pack"] += t_pack - t_start
         self.timings["launch"] += t_launch - t_pack
@@ -437,26 +439,13 @@ class LiveSmoother:
         return self.update_tables(tables)
 
     # -- records -----------------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _pose(p, j):
-        from .inverse_kinematics import PoseShapeParam
-        from .pose_def import KpsFormat, Pose
-        return (PoseShapeParam(p[:3].copy(), p[3:57].reshape(18, 3).copy(), p[57:].copy()),
-                Pose(KpsFormat.BASIC_18, np.array(j, np.float64).reshape(18, 3).copy(), np.ones((18, 1)), None))
-
     def _record(self, idn: _Ident, n: int, state: Optional[int] = None, live=None):
         """The identity's rows 0..n-1 as an MvTracklet-like record (save_bvh takes it); ``live``: values of the rows not final yet."""
-        from .motion_capture import MvTracklet, TrackState
-        poses = []
-        for r in range(n):
-            p, j = (idn.params[r], idn.joints[r]) if idn.params[r] is not None else live[r]
-            poses.append((idn.f0 + r,) + self._pose(p, j))
-        t = MvTracklet(idn.tid, poses[0][0], poses[0][1], poses[0][2])
-        t.frame_idxs = [q[0] for q in poses]
-        t.poses = poses
-        t.state = TrackState(idn.state if state is None else state)
-        t.hits = idn.hits
-        t.time_since_update = idn.n - idn.last_data()
+        from .motion_capture import TrackState
+        rows = [(idn.params[r], idn.joints[r]) if idn.params[r] is not None else live[r] for r in range(n)]
+        poses = pose_tuples(idn.f0 + np.arange(n), np.array([p for p, _ in rows]), np.array([j for _, j in rows], np.float64))
+        t = new_record(idn.tid, poses, state=TrackState(idn.state if state is None else state), hits=idn.hits,
+                       time_since_update=idn.n - idn.last_data())
         t.smooth_filled = np.array(idn.filled[:n], bool)
         t.smooth_views = np.array(idn.views[:n], np.int32)
         t.smooth_select = np.array(idn.sel[:n], np.int32).reshape(n, self.C)

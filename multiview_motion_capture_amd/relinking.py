@@ -163,7 +163,7 @@ def merge_records(tracklets: list, order: np.ndarray, head: np.ndarray, pos: np.
     track_id of the earliest fragment; frame_idxs / poses of the fragments in time order (the pose tuples themselves, unchanged);
     hits = the number of poses; state and time_since_update of the last fragment; ``relink_parts`` [(track_id, first frame, last
     frame) per fragment]; ``relink_costs`` [the cost of each link taken]."""
-    from .motion_capture import MvTracklet
+    from .sequences import new_record
     n = len(tracklets)
     if n == 0:
         return []
@@ -177,11 +177,7 @@ def merge_records(tracklets: list, order: np.ndarray, head: np.ndarray, pos: np.
         for t in parts:
             frames += list(t.frame_idxs)
             poses += list(t.poses)
-        t = MvTracklet(parts[0].track_id, frames[0], poses[0][1], poses[0][2])
-        t.frame_idxs, t.poses = frames, poses
-        t.hits = len(poses)
-        t.state = parts[-1].state
-        t.time_since_update = getattr(parts[-1], "time_since_update", 0)
+        t = new_record(parts[0].track_id, poses, parts[-1], frame_idxs=frames, hits=len(poses))
         t.relink_parts = [(p.track_id, int(p.frame_idxs[0]), int(p.frame_idxs[-1])) for p in parts]
         t.relink_costs = [float(cost[k]) for k in by[a:b - 1]]
         out.append(t)

@@ -38,7 +38,8 @@ import numpy as np
 
 from . import body_fit
 from .common import Calib
-from .rig_refine import LOSS_PX, MAX_CAMS, MAX_ITER_CAP, STOP, RigRefinement, _moved, check_loss, robust_fields, solve_group
+from .rig_refine import LOSS_PX, MAX_CAMS, MAX_ITER_CAP, RigRefinement, check_loss, decode, solve_group
+from .sequences import stopwatch
 
 MAX_SAMPLE, MAX_ROUNDS = 32, 8            # include/mvmc.h: MVMC_RIGINIT_MAX_SAMPLE, MVMC_RIGINIT_MAX_ROUNDS
 MIN_COMMON = 10                           # points two edges must share for a scale
@@ -260,16 +261,8 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
 
     from . import device as dev
     d = torch.device(device)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
-    tm = {"observe": 0.0, "pairs": 0.0, "graph": 0.0, "polish": 0.0, "start": 0.0, "trials": 0.0}
-
-    def lap(k, t0):
-        if timings is not None:
-            torch.cuda.synchronize(d)
-        t1 = time.perf_counter()
-        tm[k] += t1 - t0
-        return t1
-
+    T = dev.uploader(d)
+    lap, tm = stopwatch(timings, d, ("observe", "pairs", "graph", "polish", "start", "trials"))
     t0 = time.perf_counter()
     S = len(sequences)
     Ks = [np.array([k for k, _ in cm]) for cm in cams]
@@ -352,42 +345,18 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
         Rtin = np.array([Rt_tree[s] for s in ids])
         any_c = obs.shape[0] > 0
         g = solve_group(T(obs) if any_c else None, T(rig_c) if any_c else None, T(np.einsum("scij,scjk->scik", Kin, Rtin)) if any_c else None,
-                        Kin, Rtin, n, C, d, int(polish_iter), float(polish_px), float(min_score), 2, int(min_pair_inliers), 1, lap, t0,
+                        Kin, Rtin, n, C, d, int(polish_iter), float(polish_px), float(min_score), 2, int(min_pair_inliers), 1, lap,
                         polish_loss, polish_loss_px, polish_ftol, None)
-        t0 = g["t0"]
-        X_run = g["X_d"].cpu().numpy()
-        X0 = g["X0_d"].cpu().numpy()[:, :3] if any_c else np.zeros((0, 3))
-        x_lo = np.concatenate([[0], np.cumsum(np.bincount(g["seq_of"][g["dev_pt"]], minlength=n))])
-        w_lo = np.concatenate([[0], np.cumsum(np.where(g["run"], g["n_pts"], 0))])
         for r, s in enumerate(ids):
-            m = g["seq_of"] == r
-            Rt_new = np.concatenate([g["cams_h"][r, :, 9:18].reshape(C, 3, 3), g["cams_h"][r, :, 18:21, None]], axis=2)
-            n_o = int(g["n_obs"][r].sum())
-            if g["run"][r]:
-                n_t = int(g["ctl_h"][r, 1])
-                cost = g["info_h"][r, 8 + MAX_ITER_CAP:8 + MAX_ITER_CAP + n_t + 1].copy()
-                trials = [int(v) for v in g["info_h"][r, 8:8 + n_t]]
-                rb, ra = float(np.sqrt(2.0 * g["info_h"][r, 0] / n_o)), float(np.sqrt(2.0 * g["info_h"][r, 1] / n_o))
-                Xp = X_run[x_lo[r]:x_lo[r + 1]]
-            else:
-                dd = g["dist"][m[:, None] & g["obs"]]
-                e0 = 0.5 * float(np.sum(dd * dd))
-                cost, trials = (np.array([e0]) if n_o else np.zeros(0)), []
-                rb = ra = float(np.sqrt(2.0 * e0 / n_o)) if n_o else float("nan")
-                Xp = X0[m & g["is_pt"]]
-            rob = robust_fields(g, r, w_lo, n_o, polish_loss, polish_loss_px, False) if polish_loss is not None else {}
-            rb, ra = rob.pop("rms", (rb, ra))
+            pol = decode(g, r, cams[s], Rtin[r], polish_loss, polish_loss_px)
+            Rt_new = np.array([c.Rt for c in pol.calibs])
             wh = [w for _, w in cams[s]]
-            pol = RigRefinement(calibs=[Calib.from_k_rt(Ks[s][c].copy(), Rt_new[c].copy(), wh[c]) for c in range(C)], rms_before=rb,
-                                rms_after=ra, n_points=int(g["n_pts"][r]), n_obs=n_o, obs_per_camera=g["n_obs"][r].copy(),
-                                held=g["held"][r].copy(), cost=cost, trials=trials, stop=STOP[int(g["ctl_h"][r, 0])],
-                                moved=_moved(Rtin[r], Rt_new), **rob)
             X = np.full((cand[r].shape[0], 3), np.nan)
-            X[np.flatnonzero(is_c[r])[g["is_pt"][m]]] = Xp
+            X[np.flatnonzero(is_c[r])[g.is_pt[g.seq_of == r]]] = g.points(r)
             Rt_fin, X_fin, src = finish(Rt_new, X.reshape(-1, 17, 3), bases[s], world)
             out[s].calibs = [Calib.from_k_rt(Ks[s][c].copy(), Rt_fin[c], wh[c]) for c in range(C)]
-            out[s].rms_px, out[s].scale_source, out[s].polish, out[s].points = ra, src, pol, X_fin
-        t0 = lap("polish", t0)
+            out[s].rms_px, out[s].scale_source, out[s].polish, out[s].points = pol.rms_after, src, pol, X_fin
+        lap("polish")
     if timings is not None:
         tm["polish"] += tm.pop("start") + tm.pop("trials")
         timings.update(tm)

@@ -3,7 +3,7 @@
 Every stage of the offline pipeline takes the rig as given.  refine_rigs() repairs a rig that is a little stale (a bumped tripod, a
 calibration a day old) by a bundle adjustment over the keypoints of the people the tracker already follows:
 
-  a. selection: the body fit's (mvmc_body_observe on the records' joints: per record frame and camera a pose slot or -1), every
+  a. selection: sequences.select_views (mvmc_body_observe on the records' joints: per record frame and camera a pose slot or -1), every
      ``frame_step``-th frame of each record;
   b. points: one per (record, frame, keypoint of the 17 ingested) that at least ``min_views`` selected views see with score >
      ``min_score``; start = mvmc_dlt's arithmetic on the input rig (a NaN point is dropped); an observation farther than ``max_px``
@@ -41,9 +41,9 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import body_fit
-from .body_fit import LM_FTOL, LM_MU0, LM_XTOL, _record_arrays
+from .body_fit import LM_FTOL, LM_MU0, LM_XTOL
 from .common import Calib
-from .sequences import SequenceInput, check_sequences
+from .sequences import SequenceInput, check_records, no_sequences, plan_groups, select_views, stack_group, stopwatch
 
 TILE = 64            # include/mvmc.h: MVMC_RIG_TILE
 MAX_CAMS = 8         # MVMC_RIG_MAX_CAMS
@@ -90,23 +90,18 @@ def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score,
     """The input checks of refine_rigs, before any device work: ValueError, or (shapes, per sequence the records' (frames, params,
     joints) arrays)."""
     check_loss("refine_rigs", loss, loss_px, ftol, xtol)
-    if len(tracklets_per_sequence) != len(sequences):
-        raise ValueError(f"refine_rigs: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
-    if int(min_views) < 2:
-        raise ValueError("refine_rigs: min_views >= 2 required (a point needs two views)")
-    if int(frame_step) < 1:
-        raise ValueError("refine_rigs: frame_step >= 1 required")
-    if not 0 <= int(max_iter) <= MAX_ITER_CAP:
-        raise ValueError(f"refine_rigs: 0 <= max_iter <= {MAX_ITER_CAP} required")
-    if not (float(max_px) > 0.0 and float(min_score) >= 0.0 and int(min_cam_obs) >= 0):
-        raise ValueError("refine_rigs: max_px > 0, min_score >= 0 and min_cam_obs >= 0 required")
-    shapes = check_sequences(sequences, "refine_rigs")
-    recs = []
-    for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
-        if not 2 <= C <= MAX_CAMS:
-            raise ValueError(f"refine_rigs: sequence {s} has {C} cameras, 2 .. {MAX_CAMS} required")
-        recs.append([_record_arrays(t, F, f"sequence {s}, record {j}") for j, t in enumerate(tl)])
-    return shapes, recs
+
+    def own():
+        if int(min_views) < 2:
+            raise ValueError("refine_rigs: min_views >= 2 required (a point needs two views)")
+        if int(frame_step) < 1:
+            raise ValueError("refine_rigs: frame_step >= 1 required")
+        if not 0 <= int(max_iter) <= MAX_ITER_CAP:
+            raise ValueError(f"refine_rigs: 0 <= max_iter <= {MAX_ITER_CAP} required")
+        if not (float(max_px) > 0.0 and float(min_score) >= 0.0 and int(min_cam_obs) >= 0):
+            raise ValueError("refine_rigs: max_px > 0, min_score >= 0 and min_cam_obs >= 0 required")
+    return check_records(sequences, tracklets_per_sequence, "refine_rigs", own,
+                         cameras=(2, MAX_CAMS, f"refine_rigs: sequence {{s}} has {{C}} cameras, 2 .. {MAX_CAMS} required"))
 
 
 def _per_camera(seq_of, obs, n_seqs):
@@ -162,19 +157,50 @@ def _moved(Rt_in, Rt_out):
     return out
 
 
-def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, t0, loss=None,
-                loss_px=LOSS_PX, ftol=None, xtol=None):
+@dataclass
+class GroupSolve:
+    """solve_group's result for a group of S sequences: the host gates' arrays over the n candidates, the one read-back, and the
+    device's start values and final points."""
+    dist: np.ndarray             # (n, C) px at the start values, NaN where the camera does not see the candidate
+    seq_of: np.ndarray           # (n,) the candidate's sequence
+    obs: np.ndarray              # (n, C) bool: the observations of the problem
+    held: np.ndarray             # (S, C) bool
+    is_pt: np.ndarray            # (n,) bool: the candidate became a point
+    n_pts: np.ndarray            # (S,)
+    n_obs: np.ndarray            # (S, C)
+    run: np.ndarray              # (S,) bool: the sequence was solved (the others stopped with few_cameras / few_points)
+    cams_h: np.ndarray           # (S, C, 21): K, R, t after the trials
+    info_h: np.ndarray           # (S, MVMC_RIG_INFO_DOUBLES)
+    ctl_h: np.ndarray            # (S, 4)
+    X0_d: object                 # (n, 4) device: the start values (None without candidates)
+    X_d: object                  # device: the final points of dev_pt's candidates
+    dev_pt: np.ndarray           # (n,) bool: is_pt of the solved sequences
+    e_plain: Optional[np.ndarray] = None    # with a loss (S, 2): the plain 1/2 sum r^2 before and after
+    w_h: Optional[np.ndarray] = None        # with a loss (points of dev_pt, C): the final weights
+
+    _host: Optional[tuple] = None           # points(): X_d and X0_d read back once, and each sequence's first row of X_d
+
+    def points(self, r):
+        """Sequence r's points (its candidates that are is_pt, in order; candidates are stored sequence by sequence): the final ones
+        where it was solved, else the start values."""
+        if self._host is None:
+            x_lo = np.concatenate([[0], np.cumsum(np.bincount(self.seq_of[self.dev_pt], minlength=self.run.shape[0]))])
+            self._host = (self.X_d.cpu().numpy(), self.X0_d.cpu().numpy()[:, :3] if self.X0_d is not None else np.zeros((0, 3)), x_lo)
+        X, X0, x_lo = self._host
+        return X[x_lo[r]:x_lo[r + 1]] if self.run[r] else X0[(self.seq_of == r) & self.is_pt]
+
+
+def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, loss=None,
+                loss_px=LOSS_PX, ftol=None, xtol=None) -> GroupSolve:
     """Steps b - e on the candidates of a group of S sequences of C cameras: what refine_rigs does after its selection, and what
     rig_init.calibrate_rigs polishes with.  obs_d (n,C,3) f64 device: u, v, score per candidate and camera (None: no candidate);
-    rig_c (n,) i32 device: the candidate's sequence; Pm_d (S,C,3,4) device; Kin (S,C,3,3), Rtin (S,C,3,4) host; lap(key, t0) -> t1 the
-    caller's stopwatch ("start", "trials").  -> dict: the host gates' arrays (dist, seq_of, obs, held, is_pt, n_pts, n_obs, run), the
-    one read-back (cams_h (S,C,21), info_h, ctl_h), the device's start values X0_d and final points X_d with dev_pt (their candidates),
-    and t0.  With a loss also e_plain (S,2): the plain 1/2 sum r^2 before and after, and w_h (points of dev_pt, C): the final weights."""
+    rig_c (n,) i32 device: the candidate's sequence; Pm_d (S,C,3,4) device; Kin (S,C,3,3), Rtin (S,C,3,4) host; lap: the caller's
+    stopwatch (sequences.stopwatch), which gets "start" and "trials"."""
     import torch
 
     from . import _cabi
     from . import device as dev
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+    T = dev.uploader(d)
     n_cand = 0 if obs_d is None else int(obs_d.shape[0])
     X0_d = None
     if n_cand:
@@ -204,12 +230,13 @@ def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_sc
         uv_d = uv_d.contiguous()
     else:
         X_d, uv_d = torch.zeros((0, 3), dtype=torch.float64, device=d), torch.zeros((0, C, 2), dtype=torch.float64, device=d)
-    t0 = lap("start", t0)
+    lap("start")
     Xt_d = X_d.clone()
     tile_d, seq_d, slot_d, cams_d, info_d, ctl_d = T(tile), T(seq), T(slot), T(cams), T(info), T(ctl)
     camt_d = cams_d.clone()
     part, part2, red = dev.rig_work(tile.shape[0], S, C, d)
     ftol, xtol = LM_FTOL if ftol is None else float(ftol), LM_XTOL if xtol is None else float(xtol)
+    code, px = LOSS[loss], 0.0 if loss is None else float(loss_px)      # MVMC_RIG_LOSS_NONE: the kernels of the entries without a loss
     extra = []
 
     def plain_cost():
@@ -219,48 +246,58 @@ def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_sc
                            variant)
         return info2[:, 0]
 
-    if run.any() and loss is None:
-        for _ in range(max(int(max_iter), 1)):
-            dev.rig_accumulate(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant)
-            if int(max_iter):
-                dev.rig_step(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, ftol, xtol, part2)
-    elif run.any():
-        code, px = LOSS[loss], float(loss_px)
-        extra.append(plain_cost())
+    if run.any():
+        if code:
+            extra.append(plain_cost())
         for _ in range(max(int(max_iter), 1)):
             dev.rig_accumulate_robust(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant,
                                       code, px)
             if int(max_iter):
                 dev.rig_step_robust(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, ftol, xtol,
                                     part2, code, px)
-        extra.append(plain_cost())
-        extra.append(dev.rig_weights(X_d, uv_d, tile_d, cams_d, code, px).reshape(-1))
-    t0 = lap("trials", t0)
+        if code:
+            extra += [plain_cost(), dev.rig_weights(X_d, uv_d, tile_d, cams_d, code, px).reshape(-1)]
+    lap("trials")
     back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()] + extra).cpu().numpy()   # the one read-back
     cams_h = back[:S * C * 21].reshape(S, C, 21)
     info_h = back[S * C * 21:S * C * 21 + info.size].reshape(S, -1)
     n_fix = S * C * 21 + info.size + 4 * S
     ctl_h = back[S * C * 21 + info.size:n_fix].reshape(S, 4).astype(np.int64)
-    robust = {}
+    g = GroupSolve(dist, seq_of, obs, held, is_pt, n_pts, n_obs, run, cams_h, info_h, ctl_h, X0_d, X_d, dev_pt)
     if extra:
-        robust = dict(e_plain=back[n_fix:n_fix + 2 * S].reshape(2, S).T, w_h=back[n_fix + 2 * S:].reshape(-1, C))
-    return dict(**robust, t0=t0, dist=dist, seq_of=seq_of, obs=obs, held=held, is_pt=is_pt, n_pts=n_pts, n_obs=n_obs, run=run, cams_h=cams_h,
-                info_h=info_h, ctl_h=ctl_h, X0_d=X0_d, X_d=X_d, dev_pt=dev_pt)
+        g.e_plain, g.w_h = back[n_fix:n_fix + 2 * S].reshape(2, S).T, back[n_fix + 2 * S:].reshape(-1, C)
+    return g
 
 
-def robust_fields(g, r, w_lo, n_o, loss, loss_px, return_weights):
-    """The RigRefinement fields a loss adds for sequence r of solve_group's result g (w_lo (S + 1,): its rows of g["w_h"]): loss,
-    loss_px, downweighted, weights, and for a solved sequence rms = the plain (rms_before, rms_after)."""
-    C = g["held"].shape[1]
-    out = dict(loss=loss, loss_px=float(loss_px), downweighted=np.full(C, np.nan), weights=None)
-    if g["run"][r] and "w_h" in g:
-        w = g["w_h"][w_lo[r]:w_lo[r + 1]]
-        with np.errstate(invalid="ignore", divide="ignore"):
-            out["downweighted"] = (w < 0.5).sum(axis=0) / (~np.isnan(w)).sum(axis=0)
-        if return_weights:
-            out["weights"] = w.copy()
-        out["rms"] = tuple(float(np.sqrt(2.0 * e / n_o)) for e in g["e_plain"][r])
-    return out
+def decode(g: GroupSolve, r: int, cameras, Rtin, loss=None, loss_px=LOSS_PX, return_weights=False) -> RigRefinement:
+    """Sequence r of a solved group as its RigRefinement.  cameras: per view (K, (w, h)); Rtin (C,3,4): the rig it started from."""
+    C = g.held.shape[1]
+    Rt_new = np.concatenate([g.cams_h[r, :, 9:18].reshape(C, 3, 3), g.cams_h[r, :, 18:21, None]], axis=2)
+    n_o = int(g.n_obs[r].sum())
+    if g.run[r]:
+        n_t = int(g.ctl_h[r, 1])
+        cost = g.info_h[r, 8 + MAX_ITER_CAP:8 + MAX_ITER_CAP + n_t + 1].copy()
+        trials = [int(v) for v in g.info_h[r, 8:8 + n_t]]
+        rb, ra = float(np.sqrt(2.0 * g.info_h[r, 0] / n_o)), float(np.sqrt(2.0 * g.info_h[r, 1] / n_o))
+    else:
+        dd = g.dist[(g.seq_of == r)[:, None] & g.obs]
+        e0 = 0.5 * float(np.sum(dd * dd))
+        cost, trials = (np.array([e0]) if n_o else np.zeros(0)), []
+        rb = ra = float(np.sqrt(2.0 * e0 / n_o)) if n_o else float("nan")
+    rob = {}
+    if loss is not None:      # downweighted, weights, and for a solved sequence the PLAIN rms in place of the robust cost's
+        rob = dict(loss=loss, loss_px=float(loss_px), downweighted=np.full(C, np.nan), weights=None)
+        if g.run[r] and g.w_h is not None:
+            lo = int(np.where(g.run, g.n_pts, 0)[:r].sum())
+            w = g.w_h[lo:lo + int(g.n_pts[r])]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                rob["downweighted"] = (w < 0.5).sum(axis=0) / (~np.isnan(w)).sum(axis=0)
+            if return_weights:
+                rob["weights"] = w.copy()
+            rb, ra = (float(np.sqrt(2.0 * e / n_o)) for e in g.e_plain[r])
+    calibs = [Calib.from_k_rt(np.array(K, np.float64), Rt_new[k].copy(), wh) for k, (K, wh) in enumerate(cameras)]
+    return RigRefinement(calibs=calibs, rms_before=rb, rms_after=ra, n_points=int(g.n_pts[r]), n_obs=n_o, obs_per_camera=g.n_obs[r].copy(),
+                         held=g.held[r].copy(), cost=cost, trials=trials, stop=STOP[int(g.ctl_h[r, 0])], moved=_moved(Rtin, Rt_new), **rob)
 
 
 def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], max_iter: int = 10,
@@ -276,109 +313,52 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
     loss: None (the plain least squares, the code path without these arguments), "huber" or "cauchy" at loss_px pixels, behind the
     two max_px gates; the records then carry loss, loss_px, downweighted and (return_weights=True) weights, their cost is the robust
     E, and rms_before / rms_after stay the plain rms.  ftol, xtol: the stop tolerances, None = the body fit's constants."""
-    if len(sequences) == 0:
-        if len(tracklets_per_sequence):
-            raise ValueError("refine_rigs: records without sequences")
+    if no_sequences(sequences, tracklets_per_sequence, "refine_rigs"):
         return []
     shapes, recs = check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step, loss,
                                 loss_px, ftol, xtol)
     import torch
 
-    from . import _cabi
     from . import device as dev
     d = torch.device(device)
-    tm = {"select": 0.0, "start": 0.0, "trials": 0.0, "records": 0.0}
-
-    def lap(k, t0):
-        if timings is not None:
-            torch.cuda.synchronize(d)
-        t1 = time.perf_counter()
-        tm[k] += t1 - t0
-        return t1
-
+    T = dev.uploader(d)
+    lap, tm = stopwatch(timings, d, ("select", "start", "trials", "records"))
     out: List[Optional[RigRefinement]] = [None] * len(sequences)
     if problems is not None:
         problems[:] = [None] * len(sequences)
-    by_c = {}
-    for i, (_, C, _) in enumerate(shapes):
-        by_c.setdefault(C, []).append(i)
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
-    for C, ids in by_c.items():
+    for lay in plan_groups(shapes, 1):
         t0 = time.perf_counter()
-        S = len(ids)
-        Pg = max(shapes[i][2] for i in ids)
-        f_off = np.concatenate([[0], np.cumsum([shapes[i][0] for i in ids])]).astype(np.int64)
-        ks = [np.asarray(sequences[i][0]) for i in ids]
-        dt = np.float32 if all(k.dtype == np.float32 for k in ks) else np.float64
-        kps = np.zeros((int(f_off[-1]), C, Pg, ks[0].shape[3], 3), dtype=dt)
-        cnt = np.zeros((int(f_off[-1]), C), dtype=np.int32)
-        for r, i in enumerate(ids):
-            kps[f_off[r]:f_off[r + 1], :, :ks[r].shape[2]] = ks[r]
-            cnt[f_off[r]:f_off[r + 1]] = np.asarray(sequences[i][1])
+        ids, S, C = lay.seq_ids, len(lay.seq_ids), lay.n_views
+        grp = stack_group(lay, sequences)
         Kin = np.array([[np.asarray(c.K, np.float64).reshape(3, 3) for c in sequences[i][2]] for i in ids])
         Rtin = np.array([[np.asarray(c.Rt, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
-        Pm = np.array([[np.asarray(c.P, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
-        items = [(r, j) for r, i in enumerate(ids) for j in range(len(recs[i]))]
-        n_cand = 0
-        if items:
-            # the body fit's selection, problems in (sequence, record, frame) order
-            fr = [recs[ids[r]][j][0] for r, j in items]
-            n_of = np.array([f.shape[0] for f in fr], dtype=np.int64)
-            frame_of = np.concatenate([f + f_off[r] for f, (r, _) in zip(fr, items)]).astype(np.int32)
-            rig_of = np.repeat(np.array([r for r, _ in items], dtype=np.int32), n_of)
-            rank = np.repeat(np.array([j for _, j in items], dtype=np.int32), n_of)
-            joints = np.concatenate([recs[ids[r]][j][2] for r, j in items])
-            order = np.argsort(frame_of, kind="stable").astype(np.int32)
-            fs = frame_of[order]
-            lo = np.searchsorted(fs, frame_of, side="left").astype(np.int32)
-            hi = np.searchsorted(fs, frame_of, side="right").astype(np.int32)
-            k17, c17 = dev.ingest(T(kps), T(cnt))
-            Pm_d = T(Pm)
-            members, _, _, _ = dev.body_observe(k17, c17, Pm_d, T(frame_of), T(rig_of), T(joints), T(order), T(lo), T(hi), T(rank),
-                                                float(max_px), float(min_score))
-            take = np.concatenate([np.arange(0, n, int(frame_step)) + o for n, o in zip(n_of, np.cumsum(n_of) - n_of)])
-            mem = members[T(take)].long()                                    # (B, C)
+        obs_d = rig_c = Pm_d = None
+        if any(recs[i] for i in ids):
+            sel = select_views(grp, recs, d, float(max_px), float(min_score))
+            n_of, k17, Pm_d = sel.n_of, sel.k17, sel.Pm_d
+            take = np.concatenate([np.arange(0, n, int(frame_step)) + o for n, o in zip(n_of, sel.rec_lo[:-1])])
+            mem = sel.members[T(take)].long()                                # (B, C)
             o17 = k17.reshape(-1, 17, 3)[mem.clamp(min=0)]                     # (B, C, 17, 3)
             o17[..., 2] = torch.where((mem >= 0)[:, :, None], o17[..., 2], torch.zeros((), dtype=o17.dtype, device=d))
             obs_all = o17.permute(0, 2, 1, 3).reshape(-1, C, 3)
             is_cand = ((obs_all[:, :, 2] > float(min_score)).sum(dim=1) >= int(min_views))
             obs_d = obs_all[is_cand].contiguous()
-            rig_c = T(np.repeat(rig_of[take], 17))[is_cand].contiguous()
-            n_cand = int(obs_d.shape[0])
-        t0 = lap("select", t0)
-        g = solve_group(obs_d if n_cand else None, rig_c if n_cand else None, Pm_d if n_cand else None, Kin, Rtin, S, C, d, max_iter,
-                        max_px, min_score, min_views, min_cam_obs, variant, lap, t0, loss, loss_px, ftol, xtol)
-        t0, dist, seq_of, obs, held, is_pt, n_pts, n_obs, run = (g[k] for k in ("t0", "dist", "seq_of", "obs", "held", "is_pt", "n_pts",
-                                                                                "n_obs", "run"))
-        cams_h, info_h, ctl_h, X0_d = g["cams_h"], g["info_h"], g["ctl_h"], g["X0_d"]
-        if problems is not None and n_cand:
-            cand, X0 = obs_d.cpu().numpy(), X0_d.cpu().numpy()
-        w_lo = np.concatenate([[0], np.cumsum(np.where(run, n_pts, 0))])
+            rig_c = T(np.repeat(sel.rig_of[take], 17))[is_cand].contiguous()
+            if not int(obs_d.shape[0]):
+                obs_d = rig_c = Pm_d = None
+        lap("select", t0)
+        g = solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, loss,
+                        loss_px, ftol, xtol)
+        if problems is not None and obs_d is not None:
+            cand, X0 = obs_d.cpu().numpy(), g.X0_d.cpu().numpy()
         for r, i in enumerate(ids):
-            Rt_new = np.concatenate([cams_h[r, :, 9:18].reshape(C, 3, 3), cams_h[r, :, 18:21, None]], axis=2)
-            n_o = int(n_obs[r].sum())
-            if run[r]:
-                n_t = int(ctl_h[r, 1])
-                cost = info_h[r, 8 + MAX_ITER_CAP:8 + MAX_ITER_CAP + n_t + 1].copy()
-                trials = [int(v) for v in info_h[r, 8:8 + n_t]]
-                rb, ra = float(np.sqrt(2.0 * info_h[r, 0] / n_o)), float(np.sqrt(2.0 * info_h[r, 1] / n_o))
-            else:
-                dd = dist[(seq_of == r)[:, None] & obs]
-                e0 = 0.5 * float(np.sum(dd * dd))
-                cost, trials = (np.array([e0]) if n_o else np.zeros(0)), []
-                rb = ra = float(np.sqrt(2.0 * e0 / n_o)) if n_o else float("nan")
-            rob = robust_fields(g, r, w_lo, n_o, loss, loss_px, return_weights) if loss is not None else {}
-            rb, ra = rob.pop("rms", (rb, ra))
-            calibs = [Calib.from_k_rt(np.array(c.K, np.float64), Rt_new[k].copy(), c.img_wh_size) for k, c in enumerate(sequences[i][2])]
-            out[i] = RigRefinement(calibs=calibs, rms_before=rb, rms_after=ra, n_points=int(n_pts[r]), n_obs=n_o,
-                                   obs_per_camera=n_obs[r].copy(), held=held[r].copy(), cost=cost, trials=trials,
-                                   stop=STOP[int(ctl_h[r, 0])], moved=_moved(Rtin[r], Rt_new), **rob)
-            if problems is not None and n_cand:
-                m = seq_of == r
-                pr = is_pt[m]
+            out[i] = decode(g, r, [(c.K, c.img_wh_size) for c in sequences[i][2]], Rtin[r], loss, loss_px, return_weights)
+            if problems is not None and obs_d is not None:
+                m = g.seq_of == r
+                pr = g.is_pt[m]
                 problems[i] = dict(cand=cand[m], rows=np.flatnonzero(pr), X0=X0[m][pr][:, :3],
-                                   uv=np.where(obs[m][pr][:, :, None], cand[m][pr][:, :, :2], np.nan))
-        lap("records", t0)
+                                   uv=np.where(g.obs[m][pr][:, :, None], cand[m][pr][:, :, :2], np.nan))
+        lap("records")
     if timings is not None:
         timings.update(tm)
     return out

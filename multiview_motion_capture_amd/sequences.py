@@ -8,6 +8,10 @@ become the reference's MvTracklet records.
 
 These are the BATCHED semantics the benchmark measures, not frame-by-frame MvTracker.update_4d: every chain starts from match_spatial
 and cold IK solves, and identities are carried across chain boundaries by the stitch.
+
+The stages that run on finished records (body_fit, smoothing, rig_refine; parts of it live_smoothing, rig_init, relinking) share their
+host front end and record writer here: check_records, stack_group, select_views (problem_tables, frame_buckets), stopwatch, and
+pose_tuples / new_record / pose_slot.
 """
 from __future__ import annotations
 
@@ -103,6 +107,194 @@ def pack_group(layout: GroupLayout, sequences: Sequence[SequenceInput], chain_le
     return kps, counts
 
 
+# -- the record stages' shared front end (body_fit, smoothing, rig_refine; live_smoothing and rig_init take parts of it) --------------------
+def no_sequences(sequences, tracklets_per_sequence, who: str) -> bool:
+    """True for an empty call (the stage returns []); records without sequences: ValueError."""
+    if len(sequences) == 0 and len(tracklets_per_sequence):
+        raise ValueError(f"{who}: records without sequences")
+    return len(sequences) == 0
+
+
+def record_arrays(rec, F: int, where: str):
+    """(frames (n,), params (n,68), joints (n,18,3)) of one MvTracklet record; ValueError where it does not fit."""
+    frames = np.asarray(rec.frame_idxs, dtype=np.int64)
+    poses = rec.poses
+    n = frames.shape[0]
+    if n == 0 or len(poses) != n:
+        raise ValueError(f"{where}: {n} frame indices and {len(poses)} poses")
+    if frames.min() < 0 or frames.max() >= F:
+        raise ValueError(f"{where}: frame {int(frames.max() if frames.max() >= F else frames.min())} outside the {F} frames of kps")
+    if np.unique(frames).shape[0] != n:
+        raise ValueError(f"{where}: a frame appears twice")
+    try:
+        root = np.array([np.asarray(p[1].root, np.float64).reshape(3) for p in poses])
+        ang = np.array([np.asarray(p[1].euler_angles, np.float64).reshape(54) for p in poses])
+        lens = np.array([np.asarray(p[1].bone_lens, np.float64).reshape(11) for p in poses])
+        joints = np.array([np.asarray(p[2].keypoints, np.float64).reshape(18, 3) for p in poses])
+    except (ValueError, AttributeError, TypeError) as e:
+        raise ValueError(f"{where}: poses must be (frame, PoseShapeParam (3 + 18x3 + 11), BASIC_18 Pose): {e}") from None
+    return frames, np.concatenate([root, ang, lens], axis=1), joints
+
+
+def check_records(sequences, tracklets_per_sequence, who: str, own_checks=None, cameras=None, increasing=False, finite=False):
+    """The input checks every record stage shares, host only: ValueError, or (shapes, per sequence its records' record_arrays).  In
+    this order: one record list per sequence; ``own_checks()`` (the stage's parameter checks); check_sequences; then sequence by
+    sequence ``cameras`` = (lo, hi, message with {s} and {C}) and per record its arrays, ``increasing`` frames, ``finite`` parameters."""
+    if len(tracklets_per_sequence) != len(sequences):
+        raise ValueError(f"{who}: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
+    if own_checks is not None:
+        own_checks()
+    shapes = check_sequences(sequences, who)
+    recs = []
+    for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
+        if cameras is not None and not cameras[0] <= C <= cameras[1]:
+            raise ValueError(cameras[2].format(s=s, C=C))
+        rr = []
+        for j, t in enumerate(tl):
+            where = f"sequence {s}, record {j}"
+            fr, par, jn = record_arrays(t, F, where)
+            if increasing and np.any(np.diff(fr) <= 0):
+                raise ValueError(f"{where}: frame indices must increase")
+            if finite and not np.all(np.isfinite(par)):
+                raise ValueError(f"{where}: parameters must be finite")
+            rr.append((fr, par, jn))
+        recs.append(rr)
+    return shapes, recs
+
+
+def stopwatch(timings: Optional[dict], device, keys):
+    """-> (lap, tm).  tm: seconds per key, from 0.  lap(key, t0=None) adds the time since t0 (None: since the previous lap ended) to
+    tm[key] and returns now; it synchronises ``device`` first only when the caller passed a ``timings`` dict."""
+    import time
+
+    import torch
+    tm = {k: 0.0 for k in keys}
+    last = [time.perf_counter()]
+
+    def lap(k, t0=None):
+        if timings is not None:
+            torch.cuda.synchronize(device)
+        t1 = time.perf_counter()
+        tm[k] += t1 - (last[0] if t0 is None else t0)
+        last[0] = t1
+        return t1
+    return lap, tm
+
+
+@dataclass
+class StackedGroup:
+    """The sequences of one camera count, frames end to end: sequence seq_ids[r] owns rows f_off[r]:f_off[r + 1] and is rig r."""
+    seq_ids: List[int]
+    n_views: int
+    Pg: int                     # person slots of every row (the group's largest P_s; the others zero)
+    f_off: np.ndarray           # (S + 1,) i64
+    kps: np.ndarray             # (f_off[-1], C, Pg, 25|17, 3): pack_group's dtype rule
+    cnt: np.ndarray             # (f_off[-1], C) i32
+    Pm: np.ndarray              # (S, C, 3, 4) f64
+
+
+def stack_group(layout: GroupLayout, sequences: Sequence[SequenceInput]) -> StackedGroup:
+    """One group of plan_groups(shapes, 1) -> its stacked host arrays (pack_group at a chain length of 1: a chain is a frame)."""
+    kps, cnt = pack_group(layout, sequences, 1)
+    Pm = np.array([[np.asarray(c.P, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in layout.seq_ids])
+    f_off = np.array(layout.chain_lo + [layout.total_chains], dtype=np.int64)
+    return StackedGroup(list(layout.seq_ids), layout.n_views, layout.p_max, f_off, kps, cnt, Pm)
+
+
+def frame_buckets(frame_of: np.ndarray):
+    """frame_of (B,) i32 -> order, lo, hi (B,) i32: order[lo[b]:hi[b]] = the problems of b's frame, in input order (body_observe's
+    tie rule looks through them)."""
+    order = np.argsort(frame_of, kind="stable").astype(np.int32)
+    fs = frame_of[order]
+    lo, hi = (np.searchsorted(fs, frame_of, side=side).astype(np.int32) for side in ("left", "right"))
+    return order, lo, hi
+
+
+@dataclass
+class Selection:
+    """The selection problems of one group, one per (record, record frame) in (sequence, record, frame) order, and what
+    mvmc_body_observe chose for them.  Record a = items[a] owns problems rec_lo[a]:rec_lo[a + 1]."""
+    items: List[Tuple[int, int]]    # (sequence: position in the caller's list, record)
+    n_of: np.ndarray                # (R,) i64 frames per record
+    rec_lo: np.ndarray              # (R + 1,) i64
+    frame_of: np.ndarray            # (B,) i32 stacked frame
+    rig_of: np.ndarray              # (B,) i32 the sequence's ordinal in the group
+    rank: np.ndarray                # (B,) i32 the record's position in its sequence's list: the earlier record wins a tie
+    order: np.ndarray               # frame_buckets(frame_of)
+    lo: np.ndarray
+    hi: np.ndarray
+    params: Optional[np.ndarray]    # (B,68) f64 host (None unless asked for)
+    joints: np.ndarray              # (B,18,3) f64 host
+    Pg: int
+    f_off: np.ndarray
+    # device side, filled by select_views
+    k17: object = None              # (f_off[-1], C, Pg, 17, 3) ingested keypoints
+    c17: object = None
+    Pm_d: object = None
+    rig_d: object = None            # rig_of
+    members: object = None          # (B, C) i32: pose row of k17.reshape(-1, 17, 3) or -1
+    n_views: object = None          # (B,) i32
+
+
+def problem_tables(grp: StackedGroup, recs: Sequence[list], want_params: bool = False) -> Selection:
+    """The host tables of a group's selection: recs[i] = check_records' arrays of sequence i's records (at least one in the group)."""
+    rig_of_seq = {i: r for r, i in enumerate(grp.seq_ids)}
+    items = [(i, j) for i in grp.seq_ids for j in range(len(recs[i]))]
+    fr = [recs[i][j][0] for i, j in items]
+    n_of = np.array([f.shape[0] for f in fr], dtype=np.int64)
+    rec_lo = np.concatenate([[0], np.cumsum(n_of)]).astype(np.int64)
+    frame_of = np.concatenate([f + grp.f_off[rig_of_seq[i]] for f, (i, _) in zip(fr, items)]).astype(np.int32)
+    rig_of = np.repeat(np.array([rig_of_seq[i] for i, _ in items], dtype=np.int32), n_of)
+    rank = np.repeat(np.array([j for _, j in items], dtype=np.int32), n_of)
+    params = np.concatenate([recs[i][j][1] for i, j in items]) if want_params else None
+    joints = np.concatenate([recs[i][j][2] for i, j in items])
+    return Selection(items, n_of, rec_lo, frame_of, rig_of, rank, *frame_buckets(frame_of), params, joints, grp.Pg, grp.f_off)
+
+
+def select_views(grp: StackedGroup, recs: Sequence[list], device, max_dist: float, min_score: float, want_params: bool = False) -> Selection:
+    """Ingest the group's keypoints and select, per problem and camera, the pose nearest to the record's joints (body_fit's step a;
+    include/mvmc.h: mvmc_body_observe).  No synchronisation: members and n_views stay on the device."""
+    from . import device as dev
+    T = dev.uploader(device)
+    sel = problem_tables(grp, recs, want_params)
+    sel.k17, sel.c17 = dev.ingest(T(grp.kps), T(grp.cnt))
+    sel.Pm_d, sel.rig_d = T(grp.Pm), T(sel.rig_of)
+    sel.members, sel.n_views, _, _ = dev.body_observe(sel.k17, sel.c17, sel.Pm_d, T(sel.frame_of), sel.rig_d, T(sel.joints), T(sel.order),
+                                                      T(sel.lo), T(sel.hi), T(sel.rank), max_dist, min_score)
+    return sel
+
+
+def pose_slot(members: np.ndarray, Pg: int) -> np.ndarray:
+    """members (.., C): rows of the ingested keypoints (frame, camera, slot) or -1 -> the pose slot in ingest order, or -1 (i32)."""
+    mem = np.asarray(members).astype(np.int64)
+    return np.where(mem >= 0, mem % Pg, -1).astype(np.int32)
+
+
+def pose_tuples(frames, params: np.ndarray, joints: np.ndarray) -> list:
+    """frames (n,), params (n,68), joints (n,18,3) -> an MvTracklet's poses [(frame, PoseShapeParam, BASIC_18 Pose)].  The poses' arrays
+    are rows of copies made here: none aliases an input."""
+    from .inverse_kinematics import PoseShapeParam
+    from .pose_def import KpsFormat, Pose
+    frm = np.asarray(frames).tolist()
+    x = np.asarray(params)
+    trans, ang, shape = x[:, :3].copy(), x[:, 3:57].reshape(-1, 18, 3).copy(), x[:, 57:].copy()
+    jo = np.array(joints, copy=True).reshape(-1, 18, 3)
+    ones = np.ones((18, 1))
+    return [(frm[k], PoseShapeParam(trans[k], ang[k], shape[k]), Pose(KpsFormat.BASIC_18, jo[k], ones.copy(), None)) for k in range(len(frm))]
+
+
+def new_record(track_id, poses: list, src=None, frame_idxs=None, state=None, hits=None, time_since_update=None):
+    """An MvTracklet of ``poses``; state, hits and time_since_update (0 where it has none) from the record ``src`` unless given."""
+    from .motion_capture import MvTracklet
+    frame_idxs = [p[0] for p in poses] if frame_idxs is None else frame_idxs
+    t = MvTracklet(track_id, frame_idxs[0], poses[0][1], poses[0][2])
+    t.frame_idxs, t.poses = frame_idxs, poses
+    t.state = src.state if state is None else state
+    t.hits = src.hits if hits is None else hits
+    t.time_since_update = getattr(src, "time_since_update", 0) if time_since_update is None else time_since_update
+    return t
+
+
 def tables_to_tracklets(meta: np.ndarray, n_tracks: np.ndarray, params: np.ndarray, joints: np.ndarray, gid: np.ndarray, chain_len: int,
                         n_real: int, frame_idx0: int = 0):
     """One sequence's stitched per-frame tables -> MvTracklet records, one per global identity, longest first.
@@ -116,9 +308,7 @@ def tables_to_tracklets(meta: np.ndarray, n_tracks: np.ndarray, params: np.ndarr
     grew since its previous row; ``hits`` is then the number of frames appended (as in update_4d, where it counts them); ``state`` is
     the identity's state in its last row, Dead when that row lies before the sequence's last real frame; ``time_since_update`` counts
     the frames from its last appended frame to its last row (to the frame after it, for a dead one)."""
-    from .inverse_kinematics import PoseShapeParam
-    from .motion_capture import MvTracklet, TrackState
-    from .pose_def import KpsFormat, Pose
+    from .motion_capture import TrackState
     L = int(chain_len)
     n_real = int(n_real)
     if n_real <= 0:
@@ -155,13 +345,7 @@ def tables_to_tracklets(meta: np.ndarray, n_tracks: np.ndarray, params: np.ndarr
     last_row = last_any[::-1][last_pos]                                   # (the last row of each identity, ids_all ascending)
     assert np.array_equal(ids, ids_all)
     fs, ss = f_idx[sel], s_idx[sel]
-    x = params[fs, ss]
-    trans, ang, shape = x[:, :3].copy(), x[:, 3:57].reshape(-1, 18, 3).copy(), x[:, 57:].copy()
-    jo = joints[fs, ss].copy()
-    frm = (frame_idx0 + fs).tolist()
-    ones = np.ones((18, 1))
-    poses = [(frm[k], PoseShapeParam(trans[k], ang[k], shape[k]), Pose(KpsFormat.BASIC_18, jo[k], ones.copy(), None))
-             for k in range(sel.size)]
+    poses = pose_tuples(frame_idx0 + fs, params[fs, ss], joints[fs, ss])
     last_f = f_idx[last_row]
     dead = last_f < n_real - 1
     state = np.where(dead, TrackState.Dead.value, meta[last_f, s_idx[last_row], 1])
@@ -170,13 +354,7 @@ def tables_to_tracklets(meta: np.ndarray, n_tracks: np.ndarray, params: np.ndarr
     out = []
     for j, tid in enumerate(ids.tolist()):
         a, n = int(start[j]), int(cnt[j])
-        t = MvTracklet(tid, frm[a], poses[a][1], poses[a][2])
-        t.frame_idxs = frm[a:a + n]
-        t.poses = poses[a:a + n]
-        t.hits = n
-        t.state = TrackState(int(state[j]))
-        t.time_since_update = int(since[j])
-        out.append(t)
+        out.append(new_record(tid, poses[a:a + n], state=TrackState(int(state[j])), hits=n, time_since_update=int(since[j])))
     return sorted(out, key=lambda t: -len(t))
 
 
@@ -199,6 +377,7 @@ def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_m
 
     import torch
 
+    from .device import uploader
     from .pipeline import HotPath
     from .tracker import check_chain_flags, repair_chains, run_chains_fused
     shapes = check_sequences(sequences)
@@ -206,23 +385,14 @@ def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_m
     d = torch.device(device)
     result: List[list] = [[] for _ in sequences]
     per_seq: List[Optional[dict]] = [None for _ in sequences]
-    tm = {"kernel": 0.0, "repair_stitch": 0.0, "convert": 0.0}
-
-    def lap(k, t0):
-        if timings is not None:
-            torch.cuda.synchronize(d)
-        t1 = time.perf_counter()
-        tm[k] += t1 - t0
-        return t1
-
+    lap, tm = stopwatch(timings, d, ("kernel", "repair_stitch", "convert"))
     for lay in plan_groups(shapes, L):
         if lay.total_chains == 0:
             continue
         t0 = time.perf_counter()
         rigs = [HotPath(np.array([c.K for c in sequences[i][2]]), np.array([c.Rt for c in sequences[i][2]]), device=d)
                 for i in lay.seq_ids]
-        kps_h, cnt_h = pack_group(lay, sequences, L)
-        kps, counts = torch.from_numpy(kps_h).to(d), torch.from_numpy(cnt_h).to(d)
+        kps, counts = map(uploader(d), pack_group(lay, sequences, L))
         out = run_chains_fused(rigs[0], kps, counts, L, t_max=t_max, rigs=rigs, rig_of_chain=lay.rig_of_chain)
         t0 = lap("kernel", t0)
         repair_chains(rigs[0], kps, counts, out)

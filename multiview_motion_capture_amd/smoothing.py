@@ -9,7 +9,7 @@ the missing ones included),
 
 over x_t = the 39 stage-1 parameters of frame t (root translation, the Euler angles of the 12 joints whose rotation moves an observed
 joint: the columns of the IK's stage 1).  The other 6 joints' angles and the bone lengths are held per frame.  r_tv is
-solve_pose_reproj's residual (inverse_kinematics.py:219-234) at frame t's lengths; V_t is the body fit's selection (body_fit.py: the
+solve_pose_reproj's residual (inverse_kinematics.py:219-234) at frame t's lengths; V_t is the selection (sequences.select_views: the
 pose nearest to the record's joints per camera, MAX_DIST, MIN_SCORE) on the input record; a frame that is missing or has no selected
 view has no data term.  Wv, Wa are diagonal: root_* on the translation (px^2 / m^2), ang_* on the angles (px^2 / rad^2).
 
@@ -31,8 +31,9 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from .body_fit import MAX_DIST, MIN_SCORE, _record_arrays
-from .sequences import SequenceInput, check_sequences
+from .body_fit import MAX_DIST, MIN_SCORE
+from .sequences import (SequenceInput, check_records, new_record, no_sequences, plan_groups, pose_slot, pose_tuples, select_views,
+                        stack_group, stopwatch)
 
 # Default prior weights: tools/smooth_weight_sweep.py on synthetic scene walks with ground truth (profiles/smooth_weight_sweep.json)
 ROOT_VEL, ROOT_ACC = 1e4, 1e4    # px^2 / m^2
@@ -131,24 +132,8 @@ def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_byte
 
 
 def _check(sequences, tracklets_per_sequence):
-    if len(tracklets_per_sequence) != len(sequences):
-        raise ValueError(f"smooth_sequences: {len(tracklets_per_sequence)} record lists for {len(sequences)} sequences")
-    shapes = check_sequences(sequences, "smooth_sequences")
-    recs = []
-    for s, (tl, (F, C, _)) in enumerate(zip(tracklets_per_sequence, shapes)):
-        if C > MAX_VIEWS:
-            raise ValueError(f"sequence {s}: {C} cameras, at most {MAX_VIEWS}")
-        rr = []
-        for j, t in enumerate(tl):
-            where = f"sequence {s}, record {j}"
-            fr, par, jn = _record_arrays(t, F, where)
-            if np.any(np.diff(fr) <= 0):
-                raise ValueError(f"{where}: frame indices must increase")
-            if not np.all(np.isfinite(par)):
-                raise ValueError(f"{where}: parameters must be finite")
-            rr.append((fr, par, jn))
-        recs.append(rr)
-    return shapes, recs
+    return check_records(sequences, tracklets_per_sequence, "smooth_sequences", increasing=True, finite=True,
+                         cameras=(1, MAX_VIEWS, f"sequence {{s}}: {{C}} cameras, at most {MAX_VIEWS}"))
 
 
 def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], root_vel: float = ROOT_VEL,
@@ -169,80 +154,43 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     "select", "blocks", "solve", "records"} (synchronising between the parts)."""
     t_start = time.perf_counter()
     w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
-    if len(sequences) == 0:
-        if len(tracklets_per_sequence):
-            raise ValueError("smooth_sequences: records without sequences")
+    if no_sequences(sequences, tracklets_per_sequence, "smooth_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence)
     import torch
 
     from . import device as dev
     d = torch.device(device)
-    tm = {"prepare": time.perf_counter() - t_start, "select": 0.0, "blocks": 0.0, "solve": 0.0, "records": 0.0}
-
-    def lap(k, t0):
-        if timings is not None:
-            torch.cuda.synchronize(d)
-        t1 = time.perf_counter()
-        tm[k] += t1 - t0
-        return t1
-
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(d)
+    T = dev.uploader(d)
+    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records"))
+    tm["prepare"] = time.perf_counter() - t_start
     out: List[list] = [[None] * len(r) for r in recs]
-    by_c = {}
-    for i, (_, C, _) in enumerate(shapes):
-        by_c.setdefault(C, []).append(i)
     per_row = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
-    for C, ids in by_c.items():
-        items = [(i, j) for i in ids for j in range(len(recs[i]))]
-        if not items:
+    for lay in plan_groups(shapes, 1):
+        if not any(recs[i] for i in lay.seq_ids):
             continue
         t0 = time.perf_counter()
-        Pg = max(shapes[i][2] for i in ids)
-        f_off = np.concatenate([[0], np.cumsum([shapes[i][0] for i in ids])]).astype(np.int64)
-        ks = [np.asarray(sequences[i][0]) for i in ids]
-        dt = np.float32 if all(k.dtype == np.float32 for k in ks) else np.float64
-        kps = np.zeros((int(f_off[-1]), C, Pg, ks[0].shape[3], 3), dtype=dt)
-        cnt = np.zeros((int(f_off[-1]), C), dtype=np.int32)
-        for r, i in enumerate(ids):
-            kps[f_off[r]:f_off[r + 1], :, :ks[r].shape[2]] = ks[r]
-            cnt[f_off[r]:f_off[r + 1]] = np.asarray(sequences[i][1])
-        Pm = np.array([[np.asarray(c.P, np.float64).reshape(3, 4) for c in sequences[i][2]] for i in ids])
-        rig_of_seq = {i: r for r, i in enumerate(ids)}
+        grp = stack_group(lay, sequences)
         t0 = lap("prepare", t0)
-        # selection on the record frames, in (sequence, record, frame) order (body_fit.fit_sequences' problems)
-        fr = [recs[i][j][0] for i, j in items]
-        n_of = np.array([f.shape[0] for f in fr], dtype=np.int64)
-        rec_lo = np.concatenate([[0], np.cumsum(n_of)]).astype(np.int64)
-        frame_of = np.concatenate([f + f_off[rig_of_seq[i]] for f, (i, _) in zip(fr, items)]).astype(np.int32)
-        rig_of = np.repeat(np.array([rig_of_seq[i] for i, _ in items], dtype=np.int32), n_of)
-        rank = np.repeat(np.array([j for _, j in items], dtype=np.int32), n_of)
-        joints = np.concatenate([recs[i][j][2] for i, j in items])
-        order = np.argsort(frame_of, kind="stable").astype(np.int32)
-        fs = frame_of[order]
-        lo = np.searchsorted(fs, frame_of, side="left").astype(np.int32)
-        hi = np.searchsorted(fs, frame_of, side="right").astype(np.int32)
-        k17, c17 = dev.ingest(T(kps), T(cnt))
-        Pm_d = T(Pm)
-        members, n_views, _, _ = dev.body_observe(k17, c17, Pm_d, T(frame_of), T(rig_of), T(joints), T(order), T(lo), T(hi), T(rank),
-                                                  MAX_DIST, MIN_SCORE)
-        mem_h = members.cpu().numpy()
-        nv_h = n_views.cpu().numpy()
+        sel = select_views(grp, recs, d, MAX_DIST, MIN_SCORE)      # on the record frames
+        items, rec_lo, C, k17, Pm_d = sel.items, sel.rec_lo, lay.n_views, sel.k17, sel.Pm_d
+        mem_h = sel.members.cpu().numpy()
+        nv_h = sel.n_views.cpu().numpy()
         t0 = lap("select", t0)
         # full trajectories of the identities with two frames or more
         traj = []
-        multi = [a for a in range(len(items)) if fr[a].shape[0] >= 2]
-        inits = initial_trajectories([fr[a] for a in multi], [recs[items[a][0]][items[a][1]][1] for a in multi])
+        multi = [a for a in range(len(items)) if sel.n_of[a] >= 2]
+        inits = initial_trajectories([recs[items[a][0]][items[a][1]][0] for a in multi], [recs[items[a][0]][items[a][1]][1] for a in multi])
         for a, (x0, filled) in zip(multi, inits):
             i, j = items[a]
-            f = fr[a]
+            f = recs[i][j][0]
             m = x0.shape[0]
             mem = -np.ones((m, C), np.int32)
             nvf = np.zeros(m, np.int32)
             rows = f - f[0]
             mem[rows] = mem_h[rec_lo[a]:rec_lo[a + 1]]
             nvf[rows] = nv_h[rec_lo[a]:rec_lo[a + 1]]
-            traj.append((a, x0, filled, mem, nvf, rig_of_seq[i]))
+            traj.append((a, x0, filled, mem, nvf, int(sel.rig_of[rec_lo[a]])))
         t0 = lap("prepare", t0)
         res = {}
         cap = max(1, int(max_work_bytes) // per_row)
@@ -284,7 +232,7 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 res[p[0]] = (xs[sl], jn[sl], inf[s])
             lap("records", t0)
         t0 = time.perf_counter()
-        _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, Pg)
+        _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, sel.Pg)
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
@@ -292,46 +240,32 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
 
 
 def _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, Pg):
-    from .inverse_kinematics import PoseShapeParam
-    from .motion_capture import MvTracklet
-    from .pose_def import KpsFormat, Pose
     tr = {p[0]: p for p in traj}
-    ones = np.ones((18, 1))
     for a, (i, j) in enumerate(items):
         src = tracklets_per_sequence[i][j]
-        f = recs[i][j][0]
+        f, par, jnt = recs[i][j]
         if a in tr:
             _, _, filled, mem, nvf, _ = tr[a]
             xs, jn, inf = res[a]
-            frm = np.arange(f[0], f[-1] + 1)
-            keep = np.ones(frm.size, bool) if fill_gaps else ~filled
-            idx = np.flatnonzero(keep)
-            poses = [(int(frm[k]), PoseShapeParam(xs[k, :3].copy(), xs[k, 3:57].reshape(18, 3).copy(), xs[k, 57:].copy()),
-                      Pose(KpsFormat.BASIC_18, jn[k].copy(), ones.copy(), None)) for k in idx]
+            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
+            poses = pose_tuples(f[0] + idx, xs[idx], jn[idx])
             cost = np.array([inf[0], inf[1], inf[2], inf[3]])
             n_t = int(inf[4])
             trials = [int(v) for v in inf[8:8 + n_t]]
             filled_k, views_k, mem_k = filled[idx], nvf[idx], mem[idx]
         else:   # one frame: nothing to smooth (a copy of the input's pose)
-            _, par, jnt = recs[i][j]
-            poses = [(int(f[0]), PoseShapeParam(par[0, :3].copy(), par[0, 3:57].reshape(18, 3).copy(), par[0, 57:].copy()),
-                      Pose(KpsFormat.BASIC_18, jnt[0].copy(), ones.copy(), None))]
+            poses = pose_tuples(f[:1], par[:1], jnt[:1])
             cost = np.zeros(4)
             trials = []
             filled_k = np.zeros(1, bool)
             views_k = nv_h[rec_lo[a]:rec_lo[a + 1]].astype(np.int32)
             mem_k = mem_h[rec_lo[a]:rec_lo[a + 1]]
-        t = MvTracklet(src.track_id, poses[0][0], poses[0][1], poses[0][2])
-        t.frame_idxs = [p[0] for p in poses]
-        t.poses = poses
-        t.state = src.state
-        t.hits = src.hits
-        t.time_since_update = getattr(src, "time_since_update", 0)
+        t = new_record(src.track_id, poses, src)
         if getattr(src, "bone_lens", None) is not None:
             t.bone_lens = np.array(src.bone_lens, np.float64).copy()
         t.smooth_filled = np.asarray(filled_k, bool)
         t.smooth_views = np.asarray(views_k, np.int32)
-        t.smooth_select = np.where(mem_k >= 0, mem_k % Pg, -1).astype(np.int32)
+        t.smooth_select = pose_slot(mem_k, Pg)
         t.smooth_cost = cost
         t.smooth_trials = trials
         out[i][j] = t
