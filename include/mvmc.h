@@ -664,6 +664,34 @@ int mvmc_rig_step_robust(double* X, double* X_trial, const double* uv, const int
                          double loss_px, mvmcStream_t stream);
 int mvmc_rig_weights(const double* X, const double* uv, const int32_t* tile, const double* cams, int n_points, int n_tiles, int n_seqs,
                      int n_views, int loss, double loss_px, double* w, mvmcStream_t stream);
+/* The two halves of a trial with intrinsic unknowns (restated in tests/rig_intr_np.py).  A camera with islot >= 0 has n_intr more
+ * unknowns: n_intr = 1 phi (K00, K01, K11 <- e^phi x themselves), n_intr = 3 also dcx, dcy (added to K02, K12).  Their rows of an
+ * observation are d(u, v)/dphi = (u - cx, v - cy), d/dcx = (1, 0), d/dcy = (0, 1), times sqrt(w) with a loss.
+ *   islot (S,C) i32: the camera's position among the sequence's cameras with free intrinsics (ascending with the camera) or -1 = K
+ *     held.  Camera 0 has slot -1 (its pose is held) and may have islot >= 0; a camera whose observations left has both -1
+ *   K0 (S,C,3) f64: fx, cx, cy of the input K, the centre of the prior
+ *   focal_sigma (relative), centre_sigma (px): the prior E_prior = 1/2 sum (phi / focal_sigma)^2 + 1/2 sum (dcx^2 + dcy^2) /
+ *     centre_sigma^2 over the cameras with islot >= 0, phi = log(K00 / fx0) accumulated over the call; +inf = no term.  They are
+ *     scalars of the launch so that the entry can refuse them.  E_prior is part of every cost in info and of the decision, and of
+ *     the diagonal and gradient of the intrinsic columns
+ *   cams is updated in K as well on an accepted trial; cams_trial carries the trial K
+ * Layout of the reduced system: one contiguous block per camera in camera order, its 6 pose columns if slot >= 0, then its n_intr
+ * intrinsic columns if islot >= 0; M = 6 (C - 1) + n_intr C columns, identity on those past the sequence's own.  red (S,
+ * mvmc_rig_red_doubles_intr) is that M x M matrix, the gradient (M), the step (M); part has mvmc_rig_part_doubles_intr per tile.
+ * In |d|_inf the intrinsic steps count as phi and dc / fx.  The gauge rescale moves no intrinsic.  The stacked product runs on the
+ * matrix cores: variant must be 1.  MVMC_RIG_LOSS_NONE is the plain cost plus prior.  n_intr outside {1, 3}, a sigma that is <= 0 or
+ * NaN, variant != 1: MVMC_ERR_ARG, nothing launched.  Everything else is as in the entries above. */
+long long mvmc_rig_part_doubles_intr(int n_views, int n_intr);   /* -1: n_views outside 2 .. MVMC_RIG_MAX_CAMS or n_intr not 1 or 3 */
+long long mvmc_rig_red_doubles_intr(int n_views, int n_intr);
+int mvmc_rig_accumulate_intr(const double* X, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                             const double* cams, double* cams_trial, int32_t* ctl, double* info, int n_points, int n_tiles, int n_seqs,
+                             int n_views, int max_iter, double mu0, int variant, double* part, double* red, int loss, double loss_px,
+                             int n_intr, const int32_t* islot, const double* K0, double focal_sigma, double centre_sigma,
+                             mvmcStream_t stream);
+int mvmc_rig_step_intr(double* X, double* X_trial, const double* uv, const int32_t* tile, const int32_t* seq, const int32_t* slot,
+                       double* cams, const double* cams_trial, int32_t* ctl, double* info, const double* red, int n_points, int n_tiles,
+                       int n_seqs, int n_views, int max_iter, double ftol, double xtol, double* part2, int loss, double loss_px,
+                       int n_intr, const int32_t* islot, const double* K0, double focal_sigma, double centre_sigma, mvmcStream_t stream);
 
 /* ---- lens distortion at the door of the pipeline (multiview_motion_capture_amd/lens.py; restated in tests/lens_np.py).  No counterpart
  * in the reference, whose only projection is project_3d_points_to_image_plane_without_distortion (mv_math_util.py).  Every other entry

@@ -42,6 +42,7 @@ SYMBOLS = (
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
     "mvmc_rig_accumulate_robust", "mvmc_rig_step_robust", "mvmc_rig_weights",
+    "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
     "mvmc_lens_undistort", "mvmc_lens_distort",
     "mvmc_pair_moments", "mvmc_pair_consensus", "mvmc_pair_refit",
 )
@@ -163,6 +164,10 @@ def load():
         "mvmc_rig_accumulate_robust": [vp] * 9 + [i32] * 5 + [f64, i32, vp, vp, i32, f64, vp],
         "mvmc_rig_step_robust": [vp] * 11 + [i32] * 5 + [f64, f64, vp, i32, f64, vp],
         "mvmc_rig_weights": [vp] * 4 + [i32] * 5 + [f64, vp, vp],
+        "mvmc_rig_part_doubles_intr": [i32, i32],
+        "mvmc_rig_red_doubles_intr": [i32, i32],
+        "mvmc_rig_accumulate_intr": [vp] * 9 + [i32] * 5 + [f64, i32, vp, vp, i32, f64, i32, vp, vp, f64, f64, vp],
+        "mvmc_rig_step_intr": [vp] * 11 + [i32] * 5 + [f64, f64, vp, i32, f64, i32, vp, vp, f64, f64, vp],
         "mvmc_lens_undistort": [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp],
         "mvmc_lens_distort": [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp],
         "mvmc_pair_moments": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
@@ -171,7 +176,8 @@ def load():
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
                 "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong,
-                "mvmc_rig_part_doubles": C.c_longlong, "mvmc_rig_red_doubles": C.c_longlong}
+                "mvmc_rig_part_doubles": C.c_longlong, "mvmc_rig_red_doubles": C.c_longlong,
+                "mvmc_rig_part_doubles_intr": C.c_longlong, "mvmc_rig_red_doubles_intr": C.c_longlong}
     # A build of another revision loaded through MVMC_LIB_PATH for a same-box A/B comparison (tools/lib_diff.py, tools/*_ab.sh) may
     # lack entry points that were added since WITHIN the same ABI version (checked above); only then is a missing symbol skipped -- the
     # shipped library must export every one.

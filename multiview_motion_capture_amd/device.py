@@ -710,6 +710,70 @@ def rig_step_robust(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, ti
                                             float(loss_px), _stream()), "mvmc_rig_step_robust")
 
 
+def rig_work_intr(n_tiles: int, n_seqs: int, n_views: int, n_intr: int, dev):
+    """rig_work for the entries with intrinsic unknowns (mvmc_rig_part_doubles_intr, mvmc_rig_red_doubles_intr)."""
+    lib = _cabi.load()
+    pd, rd = int(lib.mvmc_rig_part_doubles_intr(int(n_views), int(n_intr))), int(lib.mvmc_rig_red_doubles_intr(int(n_views), int(n_intr)))
+    if pd < 0 or rd < 0:
+        raise ValueError(f"rig_work_intr: {n_views} cameras outside 2 .. {_cabi.RIG_MAX_CAMS} or n_intr {n_intr} not 1 or 3")
+    return (torch.empty((max(n_tiles, 1), pd), dtype=torch.float64, device=dev),
+            torch.empty((max(n_tiles, 1), 4), dtype=torch.float64, device=dev), torch.zeros((n_seqs, rd), dtype=torch.float64, device=dev))
+
+
+def _rig_req_intr(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_intr, islot, K0):
+    """The buffers of a trial with intrinsic unknowns.  n_intr is checked by the entry itself (red's width only where it is valid)."""
+    N, S, Cn = X.shape[0], seq.shape[0], slot.shape[1]
+    _req(X, torch.float64, "X", (N, 3))
+    _req(uv, torch.float64, "uv", (N, Cn, 2))
+    _req(tile, torch.int32, "tile", (None, 4))
+    _req(seq, torch.int32, "seq", (S, 4))
+    _req(slot, torch.int32, "slot", (S, Cn))
+    _req(islot, torch.int32, "islot", (S, Cn))
+    _req(K0, torch.float64, "K0", (S, Cn, 3))
+    _req(cams, torch.float64, "cams", (S, Cn, _cabi.RIG_CAM_DOUBLES))
+    _req(cams_trial, torch.float64, "cams_trial", (S, Cn, _cabi.RIG_CAM_DOUBLES))
+    _req(ctl, torch.int32, "ctl", (S, 4))
+    _req(info, torch.float64, "info", (S, _cabi.RIG_INFO_DOUBLES))
+    rd = int(_cabi.load().mvmc_rig_red_doubles_intr(Cn, int(n_intr)))
+    _req(red, torch.float64, "red", (S, rd if rd >= 0 else None))
+    return N, int(tile.shape[0]), S, Cn
+
+
+def rig_accumulate_intr(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor, cams: torch.Tensor,
+                        cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, max_iter: int, mu0: float, part: torch.Tensor,
+                        red: torch.Tensor, n_intr: int, islot: torch.Tensor, K0: torch.Tensor, focal_sigma: float, centre_sigma: float,
+                        variant: int = 1, loss: int = 0, loss_px: float = 0.0) -> None:
+    """rig_accumulate_robust with n_intr (1: phi, 3: phi, dcx, dcy) intrinsic unknowns per camera with islot >= 0 and a Gaussian
+    prior about K0 (S,C,3: fx, cx, cy) of focal_sigma (relative) and centre_sigma (px), +inf = none
+    (include/mvmc.h: mvmc_rig_accumulate_intr)."""
+    N, T, S, Cn = _rig_req_intr(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_intr, islot, K0)
+    pd = int(_cabi.load().mvmc_rig_part_doubles_intr(Cn, int(n_intr)))
+    _req(part, torch.float64, "part", (None, pd if pd >= 0 else None))
+    if part.shape[0] < T:
+        raise ValueError(f"part: {part.shape[0]} rows for {T} tiles")
+    check(_cabi.load().mvmc_rig_accumulate_intr(_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
+                                                N, T, S, Cn, int(max_iter), float(mu0), int(variant), _p(part), _p(red), int(loss),
+                                                float(loss_px), int(n_intr), _p(islot), _p(K0), float(focal_sigma), float(centre_sigma),
+                                                _stream()), "mvmc_rig_accumulate_intr")
+
+
+def rig_step_intr(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
+                  cams: torch.Tensor, cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, red: torch.Tensor, max_iter: int,
+                  ftol: float, xtol: float, part2: torch.Tensor, n_intr: int, islot: torch.Tensor, K0: torch.Tensor, focal_sigma: float,
+                  centre_sigma: float, loss: int = 0, loss_px: float = 0.0) -> None:
+    """rig_step_robust with intrinsic unknowns (include/mvmc.h: mvmc_rig_step_intr): every cost includes the prior, and cams takes the
+    trial K of an accepted trial."""
+    N, T, S, Cn = _rig_req_intr(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_intr, islot, K0)
+    _req(X_trial, torch.float64, "X_trial", (N, 3))
+    _req(part2, torch.float64, "part2", (None, 4))
+    if part2.shape[0] < T:
+        raise ValueError(f"part2: {part2.shape[0]} rows for {T} tiles")
+    check(_cabi.load().mvmc_rig_step_intr(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl),
+                                          _p(info), _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), int(loss),
+                                          float(loss_px), int(n_intr), _p(islot), _p(K0), float(focal_sigma), float(centre_sigma),
+                                          _stream()), "mvmc_rig_step_intr")
+
+
 def rig_weights(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, cams: torch.Tensor, loss: int, loss_px: float) -> torch.Tensor:
     """The loss's weight of every observation at (X, cams) (include/mvmc.h: mvmc_rig_weights) -> w (N,C) f64, NaN where the camera
     does not observe the point (and on points outside every tile)."""

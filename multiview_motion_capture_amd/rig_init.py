@@ -18,7 +18,10 @@ association.  The walk must COVER the volume: a person who wanders 0.2 m around 
      every edge after the first from the median ratio of the depths two edges give the same points; composition;
   6. polish: rig_refine's bundle adjustment (camera 0 held) on the walk's own points, a (frame, joint) that >= 2 views see; by
      default plain least squares behind the ``polish_px`` gate, with ``polish_loss="huber" | "cauchy"`` rig_refine's robust loss at
-     ``polish_loss_px`` pixels, which keeps detections with exchanged limbs that pass the gate from pulling on the rig;
+     ``polish_loss_px`` pixels, which keeps detections with exchanged limbs that pass the gate from pulling on the rig; with
+     ``polish_intrinsics="focal" | "focal+centre"`` rig_refine's intrinsic unknowns with their prior (``polish_focal_sigma``,
+     ``polish_centre_sigma_px``) for a K that is only nominal -- the pair stage keeps the nominal K, and with two cameras the polish
+     is skipped as without it, so no intrinsic is estimated there;
   7. metric scale from ``baseline=(i, j, metres)`` or, without one, from the limb lengths of the default skeleton -- an average-adult
      assumption good to about +-10 %, stated and not measured; ``world="floor"`` turns the result upright: +z the mean direction hips
      -> shoulders, z = 0 at the median of the lower ankle, x camera 0's optical axis along the floor, the origin below camera 0.
@@ -38,7 +41,7 @@ import numpy as np
 
 from . import body_fit
 from .common import Calib
-from .rig_refine import LOSS_PX, MAX_CAMS, MAX_ITER_CAP, RigRefinement, check_loss, decode, solve_group
+from .rig_refine import LOSS_PX, MAX_CAMS, MAX_ITER_CAP, RigRefinement, check_intrinsics, check_loss, decode, solve_group
 from .sequences import stopwatch
 
 MAX_SAMPLE, MAX_ROUNDS = 32, 8            # include/mvmc.h: MVMC_RIGINIT_MAX_SAMPLE, MVMC_RIGINIT_MAX_ROUNDS
@@ -87,9 +90,11 @@ def _cameras(cams, who):
 
 
 def check_calibrate(sequences, hypotheses, sample_frames, inlier_px, min_score, min_pair_inliers, refit_rounds, polish_iter, polish_px,
-                    baseline, world, polish_loss=None, polish_loss_px=LOSS_PX, polish_ftol=None):
+                    baseline, world, polish_loss=None, polish_loss_px=LOSS_PX, polish_ftol=None, polish_intrinsics=None,
+                    polish_focal_sigma=None, polish_centre_sigma_px=None):
     """The input checks of calibrate_rigs, before any device work: ValueError, or (per sequence (F, C, P), cameras, baselines)."""
     check_loss("calibrate_rigs", polish_loss, polish_loss_px, polish_ftol, None)
+    check_intrinsics("calibrate_rigs", polish_intrinsics, polish_focal_sigma, polish_centre_sigma_px)
     if len(sequences) == 0:
         raise ValueError("calibrate_rigs: no sequences")
     if not 1 <= int(hypotheses) <= 65535:
@@ -246,7 +251,8 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
                    min_score: float = body_fit.MIN_SCORE, min_pair_inliers: int = 100, refit_rounds: int = 3, polish_iter: int = 10,
                    polish_px: float = body_fit.MAX_DIST, baseline=None, world: str = "camera0", seed: int = 0, device="cuda:0",
                    timings: Optional[dict] = None, detail: Optional[list] = None, polish_loss: Optional[str] = None,
-                   polish_loss_px: float = LOSS_PX, polish_ftol: Optional[float] = None) -> List[RigCalibration]:
+                   polish_loss_px: float = LOSS_PX, polish_ftol: Optional[float] = None, polish_intrinsics: Optional[str] = None,
+                   polish_focal_sigma: Optional[float] = None, polish_centre_sigma_px: Optional[float] = None) -> List[RigCalibration]:
     """Calibrate the rig of every sequence -- (kps25 (F_s,C_s,P_s,25|17,3), counts (F_s,C_s), cameras: per view a Calib, whose Rt is
     ignored, or (K, (w, h))) -- from the one person who walks through it.  -> one RigCalibration per sequence; a rig that cannot be
     calibrated comes back with ``stop`` saying why and calibs None.  baseline: (i, j, metres) for every sequence, or a list with one
@@ -254,9 +260,13 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
     (synchronising between the parts).  detail: a list that receives per sequence what the kernels returned for its pairs -- what the
     tests compare.  polish_loss: None (plain least squares, the code path without these arguments), "huber" or "cauchy" at
     polish_loss_px pixels (rig_refine's loss); polish_ftol: the polish's ftol, None = the body fit's constant.  With a loss the polish
-    makes more trials (it converges linearly) and ``polish`` carries the loss's fields; rms_px stays the plain rms."""
+    makes more trials (it converges linearly) and ``polish`` carries the loss's fields; rms_px stays the plain rms.
+    polish_intrinsics: None (K as given), "focal" or "focal+centre": rig_refine's intrinsic unknowns in the polish, with the prior
+    polish_focal_sigma (relative) and polish_centre_sigma_px (px) about the given K ("focal+centre" needs the latter); the calibs then
+    carry the polished K and ``polish`` the intrinsics' fields.  The pair stage always works on the given K."""
     shapes, cams, bases = check_calibrate(sequences, hypotheses, sample_frames, inlier_px, min_score, min_pair_inliers, refit_rounds,
-                                          polish_iter, polish_px, baseline, world, polish_loss, polish_loss_px, polish_ftol)
+                                          polish_iter, polish_px, baseline, world, polish_loss, polish_loss_px, polish_ftol,
+                                          polish_intrinsics, polish_focal_sigma, polish_centre_sigma_px)
     import torch
 
     from . import device as dev
@@ -346,15 +356,16 @@ def calibrate_rigs(sequences: Sequence[tuple], hypotheses: int = 128, sample_fra
         any_c = obs.shape[0] > 0
         g = solve_group(T(obs) if any_c else None, T(rig_c) if any_c else None, T(np.einsum("scij,scjk->scik", Kin, Rtin)) if any_c else None,
                         Kin, Rtin, n, C, d, int(polish_iter), float(polish_px), float(min_score), 2, int(min_pair_inliers), 1, lap,
-                        polish_loss, polish_loss_px, polish_ftol, None)
+                        polish_loss, polish_loss_px, polish_ftol, None, polish_intrinsics, polish_focal_sigma, polish_centre_sigma_px)
         for r, s in enumerate(ids):
-            pol = decode(g, r, cams[s], Rtin[r], polish_loss, polish_loss_px)
+            pol = decode(g, r, cams[s], Rtin[r], polish_loss, polish_loss_px, intrinsics=polish_intrinsics)
             Rt_new = np.array([c.Rt for c in pol.calibs])
             wh = [w for _, w in cams[s]]
             X = np.full((cand[r].shape[0], 3), np.nan)
             X[np.flatnonzero(is_c[r])[g.is_pt[g.seq_of == r]]] = g.points(r)
             Rt_fin, X_fin, src = finish(Rt_new, X.reshape(-1, 17, 3), bases[s], world)
-            out[s].calibs = [Calib.from_k_rt(Ks[s][c].copy(), Rt_fin[c], wh[c]) for c in range(C)]
+            K_fin = Ks[s] if pol.K_after is None else pol.K_after
+            out[s].calibs = [Calib.from_k_rt(K_fin[c].copy(), Rt_fin[c], wh[c]) for c in range(C)]
             out[s].rms_px, out[s].scale_source, out[s].polish, out[s].points = pol.rms_after, src, pol, X_fin
         lap("polish")
     if timings is not None:

@@ -24,12 +24,23 @@ calibration a day old) by a bundle adjustment over the keypoints of the people t
   e. after every accepted trial the camera centres and points are scaled about camera 0's centre so that the distance from camera 0
      to the first free camera keeps its input length (an exact gauge move).
 
-It does not touch intrinsics or distortion, does no time synchronisation and is no calibration from scratch: the input rig must be
-good enough for the tracker to produce records.
+  f. ``intrinsics="focal" | "focal+centre"`` (opt-in) adds per camera a log-scale phi of the focal length (K[0,0], K[0,1], K[1,1] <-
+     e^phi x themselves) and, with "focal+centre", additive dcx, dcy on the principal point, with a Gaussian prior about the input K
+     (``focal_sigma`` relative, ``centre_sigma_px`` px; E_prior = 1/2 sum (phi / sigma_f)^2 + 1/2 sum (dcx^2 + dcy^2) / sigma_c^2,
+     part of every cost the rules read).  Camera 0's pose stays held, its intrinsics are free; a camera held for too few observations
+     keeps its K too; ``intrinsics_held`` names cameras whose K is trusted.  What the geometry allows (measured on rigs that fixate
+     one point, tests/test_rig_intr_cpu.py): with the focal lengths alone the only null direction of the reduced matrix at three or
+     more cameras is the scale gauge, at two cameras there is one more; with the principal points there are three more at any
+     camera count.  So "focal+centre" without a finite ``centre_sigma_px``, and any mode on a two-camera sequence without a finite
+     ``focal_sigma``, are refused with ValueError.  The price of a free focal length is its correlation with depth: the camera
+     centres come out less sharp along the optical axes than with a known K.
+
+It does not estimate distortion, a free aspect ratio or skew, shares no intrinsics between cameras or sequences, does no time
+synchronisation and is no calibration from scratch: the input rig must be good enough for the tracker to produce records.
 
 Device code: csrc/mvmc_rigfit.hip (include/mvmc.h: mvmc_rig_start, mvmc_rig_accumulate, mvmc_rig_step; with a loss
-mvmc_rig_accumulate_robust, mvmc_rig_step_robust, mvmc_rig_weights); NumPy restatement: tests/rig_refine_np.py, with a loss
-tests/rig_robust_np.py.  Sequences with the same number of cameras share every launch, each with its own rig; there is no host
+mvmc_rig_accumulate_robust, mvmc_rig_step_robust, mvmc_rig_weights; with intrinsics mvmc_rig_accumulate_intr, mvmc_rig_step_intr);
+NumPy restatement: tests/rig_refine_np.py, with a loss tests/rig_robust_np.py, with intrinsics tests/rig_intr_np.py.  Sequences with the same number of cameras share every launch, each with its own rig; there is no host
 synchronisation between the trials and one read-back per group.
 """
 from __future__ import annotations
@@ -51,6 +62,7 @@ MAX_ITER_CAP = 24    # MVMC_RIG_MAX_ITER
 STOP = {0: "running", 1: "xtol", 2: "ftol", 3: "few_cameras", 4: "few_points", 5: "max_iter"}   # MVMC_RIG_STOP_*
 LOSS = {None: 0, "huber": 1, "cauchy": 2}    # MVMC_RIG_LOSS_*
 LOSS_PX = 6.0        # three times a 2 px detector noise; a choice, not a tuned optimum
+INTRINSICS = {None: 0, "focal": 1, "focal+centre": 3}    # unknowns per camera: n_intr of mvmc_rig_accumulate_intr
 
 
 @dataclass
@@ -72,6 +84,12 @@ class RigRefinement:
     loss_px: Optional[float] = None
     downweighted: Optional[np.ndarray] = None   # (C,) share of the camera's observations with final w < 0.5 (NaN without any)
     weights: Optional[np.ndarray] = None        # (N, C) final w, NaN where not observed; only with return_weights=True
+    # filled only with intrinsics.  calibs then carry K_after; cost includes the prior; rms_before / rms_after stay the plain rms
+    intrinsics: Optional[str] = None
+    K_before: Optional[np.ndarray] = None       # (C,3,3)
+    K_after: Optional[np.ndarray] = None        # (C,3,3)
+    k_moved: Optional[np.ndarray] = None        # (C,3): phi, dcx, dcy; zeros where the camera's K was held
+    cost_prior: Optional[float] = None          # E_prior at K_after
 
 
 def check_loss(who, loss, loss_px, ftol, xtol):
@@ -85,11 +103,47 @@ def check_loss(who, loss, loss_px, ftol, xtol):
             raise ValueError(f"{who}: {name} must be None or a finite number >= 0")
 
 
+def check_intrinsics(who, intrinsics, focal_sigma, centre_sigma_px, intrinsics_held=(), n_cams=()):
+    """The checks of the intrinsics arguments, before any device work: ValueError, or (n_intr, sigma_f, sigma_c) with +inf for no
+    term.  n_cams: the camera counts of the sequences the two-camera refusal and intrinsics_held are checked against.  Both refusals
+    come from null spaces of the reduced matrix (module docstring, f)."""
+    if intrinsics not in INTRINSICS:
+        raise ValueError(f'{who}: intrinsics is None, "focal" or "focal+centre"')
+    sig = []
+    for name, v in (("focal_sigma", focal_sigma), ("centre_sigma_px", centre_sigma_px)):
+        sig.append(np.inf if v is None else float(v))
+        if not sig[-1] > 0.0:
+            raise ValueError(f"{who}: {name} must be None or a number > 0")
+    held = [int(c) for c in intrinsics_held]
+    if intrinsics is None:
+        return 0, sig[0], sig[1]
+    if intrinsics == "focal+centre" and not np.isfinite(sig[1]):
+        raise ValueError(f'{who}: intrinsics="focal+centre" needs a finite centre_sigma_px (the principal points are not observable '
+                         f"from the reprojections alone)")
+    for C in n_cams:
+        if C == 2 and not np.isfinite(sig[0]):
+            raise ValueError(f"{who}: intrinsics on a two-camera sequence need a finite focal_sigma (two focal lengths are not "
+                             f"observable from the reprojections alone)")
+        if any(not 0 <= c < C for c in held):
+            raise ValueError(f"{who}: intrinsics_held names a camera outside 0 .. {C - 1}")
+    return INTRINSICS[intrinsics], sig[0], sig[1]
+
+
+def intrinsic_slots(held, n_intr, intrinsics_held=()):
+    """held (S,C) bool -> islot (S,C) i32: the camera's position among the sequence's cameras with free intrinsics, or -1.  Camera 0's
+    are free; a camera held for too few observations (it left the problem) and the cameras of intrinsics_held keep their K."""
+    free = np.full(held.shape, n_intr > 0)
+    free[:, 1:] &= ~held[:, 1:]
+    free[:, [int(c) for c in intrinsics_held]] = False
+    return np.where(free, np.cumsum(free, axis=1) - 1, -1).astype(np.int32)
+
+
 def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step, loss=None,
-                 loss_px=LOSS_PX, ftol=None, xtol=None):
+                 loss_px=LOSS_PX, ftol=None, xtol=None, intrinsics=None, focal_sigma=None, centre_sigma_px=None, intrinsics_held=()):
     """The input checks of refine_rigs, before any device work: ValueError, or (shapes, per sequence the records' (frames, params,
     joints) arrays)."""
     check_loss("refine_rigs", loss, loss_px, ftol, xtol)
+    check_intrinsics("refine_rigs", intrinsics, focal_sigma, centre_sigma_px)
 
     def own():
         if int(min_views) < 2:
@@ -100,8 +154,10 @@ def check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score,
             raise ValueError(f"refine_rigs: 0 <= max_iter <= {MAX_ITER_CAP} required")
         if not (float(max_px) > 0.0 and float(min_score) >= 0.0 and int(min_cam_obs) >= 0):
             raise ValueError("refine_rigs: max_px > 0, min_score >= 0 and min_cam_obs >= 0 required")
-    return check_records(sequences, tracklets_per_sequence, "refine_rigs", own,
-                         cameras=(2, MAX_CAMS, f"refine_rigs: sequence {{s}} has {{C}} cameras, 2 .. {MAX_CAMS} required"))
+    out = check_records(sequences, tracklets_per_sequence, "refine_rigs", own,
+                        cameras=(2, MAX_CAMS, f"refine_rigs: sequence {{s}} has {{C}} cameras, 2 .. {MAX_CAMS} required"))
+    check_intrinsics("refine_rigs", intrinsics, focal_sigma, centre_sigma_px, intrinsics_held, [len(q[2]) for q in sequences])
+    return out
 
 
 def _per_camera(seq_of, obs, n_seqs):
@@ -177,6 +233,9 @@ class GroupSolve:
     dev_pt: np.ndarray           # (n,) bool: is_pt of the solved sequences
     e_plain: Optional[np.ndarray] = None    # with a loss (S, 2): the plain 1/2 sum r^2 before and after
     w_h: Optional[np.ndarray] = None        # with a loss (points of dev_pt, C): the final weights
+    islot: Optional[np.ndarray] = None      # with intrinsics (S, C): the camera's intrinsic block or -1
+    K0: Optional[np.ndarray] = None         # with intrinsics (S, C, 3, 3): the input K
+    sigma: tuple = (np.inf, np.inf)         # with intrinsics: the prior's focal_sigma, centre_sigma_px (+inf: no term)
 
     _host: Optional[tuple] = None           # points(): X_d and X0_d read back once, and each sequence's first row of X_d
 
@@ -191,11 +250,13 @@ class GroupSolve:
 
 
 def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, loss=None,
-                loss_px=LOSS_PX, ftol=None, xtol=None) -> GroupSolve:
+                loss_px=LOSS_PX, ftol=None, xtol=None, intrinsics=None, focal_sigma=None, centre_sigma_px=None,
+                intrinsics_held=()) -> GroupSolve:
     """Steps b - e on the candidates of a group of S sequences of C cameras: what refine_rigs does after its selection, and what
     rig_init.calibrate_rigs polishes with.  obs_d (n,C,3) f64 device: u, v, score per candidate and camera (None: no candidate);
     rig_c (n,) i32 device: the candidate's sequence; Pm_d (S,C,3,4) device; Kin (S,C,3,3), Rtin (S,C,3,4) host; lap: the caller's
-    stopwatch (sequences.stopwatch), which gets "start" and "trials"."""
+    stopwatch (sequences.stopwatch), which gets "start" and "trials".  intrinsics: None runs the entries without intrinsic unknowns;
+    "focal" / "focal+centre" the _intr entries (the problem is still packed on the input K)."""
     import torch
 
     from . import _cabi
@@ -234,7 +295,13 @@ def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_sc
     Xt_d = X_d.clone()
     tile_d, seq_d, slot_d, cams_d, info_d, ctl_d = T(tile), T(seq), T(slot), T(cams), T(info), T(ctl)
     camt_d = cams_d.clone()
+    n_intr, sig_f, sig_c = check_intrinsics("solve_group", intrinsics, focal_sigma, centre_sigma_px)
     part, part2, red = dev.rig_work(tile.shape[0], S, C, d)
+    if n_intr:
+        # the plain cost below keeps the work buffers of the entries without intrinsics; the trials get their own
+        islot = intrinsic_slots(held, n_intr, intrinsics_held)
+        islot_d, K0_d = T(islot), T(np.ascontiguousarray(Kin[:, :, [0, 0, 1], [0, 2, 2]]))
+        part_i, _, red_i = dev.rig_work_intr(tile.shape[0], S, C, n_intr, d)
     ftol, xtol = LM_FTOL if ftol is None else float(ftol), LM_XTOL if xtol is None else float(xtol)
     code, px = LOSS[loss], 0.0 if loss is None else float(loss_px)      # MVMC_RIG_LOSS_NONE: the kernels of the entries without a loss
     extra = []
@@ -246,16 +313,30 @@ def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_sc
                            variant)
         return info2[:, 0]
 
-    if run.any():
-        if code:
-            extra.append(plain_cost())
-        for _ in range(max(int(max_iter), 1)):
+    def accumulate():
+        if n_intr:
+            dev.rig_accumulate_intr(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part_i, red_i, n_intr,
+                                    islot_d, K0_d, sig_f, sig_c, variant, code, px)
+        else:
             dev.rig_accumulate_robust(X_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, max_iter, LM_MU0, part, red, variant,
                                       code, px)
+
+    def step():
+        if n_intr:
+            dev.rig_step_intr(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red_i, max_iter, ftol, xtol, part2,
+                              n_intr, islot_d, K0_d, sig_f, sig_c, code, px)
+        else:
+            dev.rig_step_robust(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, ftol, xtol, part2,
+                                code, px)
+
+    if run.any():
+        if code or n_intr:
+            extra.append(plain_cost())
+        for _ in range(max(int(max_iter), 1)):
+            accumulate()
             if int(max_iter):
-                dev.rig_step_robust(X_d, Xt_d, uv_d, tile_d, seq_d, slot_d, cams_d, camt_d, ctl_d, info_d, red, max_iter, ftol, xtol,
-                                    part2, code, px)
-        if code:
+                step()
+        if code or n_intr:
             extra += [plain_cost(), dev.rig_weights(X_d, uv_d, tile_d, cams_d, code, px).reshape(-1)]
     lap("trials")
     back = torch.cat([cams_d.reshape(-1), info_d.reshape(-1), ctl_d.reshape(-1).double()] + extra).cpu().numpy()   # the one read-back
@@ -266,10 +347,22 @@ def solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_sc
     g = GroupSolve(dist, seq_of, obs, held, is_pt, n_pts, n_obs, run, cams_h, info_h, ctl_h, X0_d, X_d, dev_pt)
     if extra:
         g.e_plain, g.w_h = back[n_fix:n_fix + 2 * S].reshape(2, S).T, back[n_fix + 2 * S:].reshape(-1, C)
+    if n_intr:
+        g.islot, g.K0, g.sigma = islot, np.array(Kin, np.float64), (sig_f, sig_c)
     return g
 
 
-def decode(g: GroupSolve, r: int, cameras, Rtin, loss=None, loss_px=LOSS_PX, return_weights=False) -> RigRefinement:
+def _intrinsic_record(g: GroupSolve, r: int, intrinsics):
+    """The intrinsics' fields of sequence r: K_before, K_after, k_moved and cost_prior from the one read-back."""
+    K0, K1 = g.K0[r], g.cams_h[r, :, :9].reshape(-1, 3, 3).copy()
+    free, full = g.islot[r] >= 0, INTRINSICS[intrinsics] == 3
+    dk = np.stack([np.log(K1[:, 0, 0] / K0[:, 0, 0]), K1[:, 0, 2] - K0[:, 0, 2], K1[:, 1, 2] - K0[:, 1, 2]], axis=1)
+    dk = np.where(free[:, None], dk, 0.0) * np.array([1.0, full, full])
+    e = 0.5 * float(np.sum((dk[:, 0] / g.sigma[0]) ** 2) + np.sum((dk[:, 1:] / g.sigma[1]) ** 2))
+    return dict(intrinsics=intrinsics, K_before=K0.copy(), K_after=K1, k_moved=dk, cost_prior=e)
+
+
+def decode(g: GroupSolve, r: int, cameras, Rtin, loss=None, loss_px=LOSS_PX, return_weights=False, intrinsics=None) -> RigRefinement:
     """Sequence r of a solved group as its RigRefinement.  cameras: per view (K, (w, h)); Rtin (C,3,4): the rig it started from."""
     C = g.held.shape[1]
     Rt_new = np.concatenate([g.cams_h[r, :, 9:18].reshape(C, 3, 3), g.cams_h[r, :, 18:21, None]], axis=2)
@@ -295,7 +388,13 @@ def decode(g: GroupSolve, r: int, cameras, Rtin, loss=None, loss_px=LOSS_PX, ret
             if return_weights:
                 rob["weights"] = w.copy()
             rb, ra = (float(np.sqrt(2.0 * e / n_o)) for e in g.e_plain[r])
-    calibs = [Calib.from_k_rt(np.array(K, np.float64), Rt_new[k].copy(), wh) for k, (K, wh) in enumerate(cameras)]
+    Ks = [np.array(K, np.float64) for K, _ in cameras]
+    if intrinsics is not None:
+        rob.update(_intrinsic_record(g, r, intrinsics))
+        Ks = [K.copy() for K in rob["K_after"]]
+        if g.run[r] and g.e_plain is not None:           # the PLAIN rms in place of the cost's, which includes the prior
+            rb, ra = (float(np.sqrt(2.0 * e / n_o)) for e in g.e_plain[r])
+    calibs = [Calib.from_k_rt(Ks[k], Rt_new[k].copy(), wh) for k, (_, wh) in enumerate(cameras)]
     return RigRefinement(calibs=calibs, rms_before=rb, rms_after=ra, n_points=int(g.n_pts[r]), n_obs=n_o, obs_per_camera=g.n_obs[r].copy(),
                          held=g.held[r].copy(), cost=cost, trials=trials, stop=STOP[int(g.ctl_h[r, 0])], moved=_moved(Rtin, Rt_new), **rob)
 
@@ -304,7 +403,9 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
                 max_px: float = body_fit.MAX_DIST, min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100,
                 frame_step: int = 1, device="cuda:0", timings: Optional[dict] = None, variant: int = 1,
                 problems: Optional[list] = None, loss: Optional[str] = None, loss_px: float = LOSS_PX, ftol: Optional[float] = None,
-                xtol: Optional[float] = None, return_weights: bool = False) -> List[RigRefinement]:
+                xtol: Optional[float] = None, return_weights: bool = False, intrinsics: Optional[str] = None,
+                focal_sigma: Optional[float] = None, centre_sigma_px: Optional[float] = None,
+                intrinsics_held: Sequence[int] = ()) -> List[RigRefinement]:
     """Refine the rig of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows track_sequences
     takes -- from its MvTracklet records.  -> one RigRefinement per sequence; the inputs are not touched.
     timings: a dict that receives the seconds spent in {"select", "start", "trials", "records"} (synchronising between the parts).
@@ -312,11 +413,17 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
     (dict X0 (N,3), uv (N,C,2), cand (n,C,3), rows (N,): the candidates that became points) -- what the tests compare.
     loss: None (the plain least squares, the code path without these arguments), "huber" or "cauchy" at loss_px pixels, behind the
     two max_px gates; the records then carry loss, loss_px, downweighted and (return_weights=True) weights, their cost is the robust
-    E, and rms_before / rms_after stay the plain rms.  ftol, xtol: the stop tolerances, None = the body fit's constants."""
+    E, and rms_before / rms_after stay the plain rms.  ftol, xtol: the stop tolerances, None = the body fit's constants.
+    intrinsics: None (K is taken as given, the code path without these arguments), "focal" (one log-scale per camera) or
+    "focal+centre" (and the principal point), with a Gaussian prior about the input K of focal_sigma (relative) and centre_sigma_px
+    (px), None = no term; intrinsics_held: cameras whose K is kept.  "focal+centre" without a finite centre_sigma_px, and intrinsics
+    on a two-camera sequence without a finite focal_sigma, raise ValueError: those unknowns are not observable (module docstring, f).
+    The records then carry intrinsics, K_before, K_after, k_moved and cost_prior, their calibs carry K_after, and cost includes the
+    prior."""
     if no_sequences(sequences, tracklets_per_sequence, "refine_rigs"):
         return []
     shapes, recs = check_refine(sequences, tracklets_per_sequence, max_iter, max_px, min_score, min_views, min_cam_obs, frame_step, loss,
-                                loss_px, ftol, xtol)
+                                loss_px, ftol, xtol, intrinsics, focal_sigma, centre_sigma_px, intrinsics_held)
     import torch
 
     from . import device as dev
@@ -348,11 +455,11 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
                 obs_d = rig_c = Pm_d = None
         lap("select", t0)
         g = solve_group(obs_d, rig_c, Pm_d, Kin, Rtin, S, C, d, max_iter, max_px, min_score, min_views, min_cam_obs, variant, lap, loss,
-                        loss_px, ftol, xtol)
+                        loss_px, ftol, xtol, intrinsics, focal_sigma, centre_sigma_px, intrinsics_held)
         if problems is not None and obs_d is not None:
             cand, X0 = obs_d.cpu().numpy(), g.X0_d.cpu().numpy()
         for r, i in enumerate(ids):
-            out[i] = decode(g, r, [(c.K, c.img_wh_size) for c in sequences[i][2]], Rtin[r], loss, loss_px, return_weights)
+            out[i] = decode(g, r, [(c.K, c.img_wh_size) for c in sequences[i][2]], Rtin[r], loss, loss_px, return_weights, intrinsics)
             if problems is not None and obs_d is not None:
                 m = g.seq_of == r
                 pr = g.is_pt[m]
@@ -367,8 +474,11 @@ def refine_rigs(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequ
 def refine_rig(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, max_iter: int = 10, max_px: float = body_fit.MAX_DIST,
                min_score: float = body_fit.MIN_SCORE, min_views: int = 2, min_cam_obs: int = 100, frame_step: int = 1, device="cuda:0",
                timings: Optional[dict] = None, loss: Optional[str] = None, loss_px: float = LOSS_PX, ftol: Optional[float] = None,
-               xtol: Optional[float] = None, return_weights: bool = False) -> RigRefinement:
+               xtol: Optional[float] = None, return_weights: bool = False, intrinsics: Optional[str] = None,
+               focal_sigma: Optional[float] = None, centre_sigma_px: Optional[float] = None,
+               intrinsics_held: Sequence[int] = ()) -> RigRefinement:
     """refine_rigs for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> RigRefinement."""
     return refine_rigs([(kps, counts, calibs)], [tracklets], max_iter=max_iter, max_px=max_px, min_score=min_score, min_views=min_views,
                        min_cam_obs=min_cam_obs, frame_step=frame_step, device=device, timings=timings, loss=loss, loss_px=loss_px,
-                       ftol=ftol, xtol=xtol, return_weights=return_weights)[0]
+                       ftol=ftol, xtol=xtol, return_weights=return_weights, intrinsics=intrinsics, focal_sigma=focal_sigma,
+                       centre_sigma_px=centre_sigma_px, intrinsics_held=intrinsics_held)[0]
