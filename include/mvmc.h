@@ -539,6 +539,29 @@ int mvmc_smooth_step(const mvmcSkeleton* skel_host, double* x, double* x_trial, 
                      int n_frames, double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol,
                      double xtol, int max_iter, int phase, int32_t* ctl, double* info, double* work, mvmcStream_t stream);
 
+/* The per-frame covariance of the smoothed trajectory, one 256-lane workgroup per identity (csrc/mvmc_smooth_cov.hip).  At the final x
+ * the Laplace / Gauss-Newton covariance of E is sigma^2 A^-1, A = the data blocks at x + the exact prior Hessian (the matrix
+ * mvmc_smooth_step factors).  The launch factors A + mu diag A with the smoother's own sweep, then one backward recursion over the
+ * factor (Takahashi's selected inverse) gives the diagonal blocks Sigma_tt of its inverse row by row.  mu >= 0 is a small damping: at
+ * mu = 0 the matrix is singular for this skeleton (the Rz angles of the two knees are stage-1 columns but move no joint, and the
+ * prior sees differences only), the joints' covariances do not depend on mu to first order.  From each Sigma_tt, while it is on the chip:
+ *   jcov (N, 18, 6) f64 out: C_K = D_K Sigma_tt D_K^T of every skeleton joint K, D_K = d X_K / d x_t (3 x MVMC_SMOOTH_K); the six
+ *        values (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), m^2 per px^2 (unit variance: the host applies the noise scale);
+ *   pvar (N, MVMC_SMOOTH_K) f64 out: the diagonal of Sigma_tt, m^2 or rad^2 per px^2;
+ *   cinfo (n_ids, MVMC_SMOOTH_COV_INFO_DOUBLES) f64 out: {status, E_data at x, n_res = 2 x the (selected view, observed joint) pairs
+ *        whose score is not zero, edof = sum_t tr(Sigma_tt J_t^T J_t), 0...}.  status 0: solved.  1: the factor has a pivot
+ *        that is not positive and finite -- every jcov / pvar row of the identity is NaN (n_res, edof too), the recursion is not run.
+ *        2: an identity of fewer than two rows, nothing solved, NaN rows.
+ * x (N,68) f64 the final point; blk (N, MVMC_SMOOTH_BLOCK_DOUBLES) f64 the data blocks AT x (one buffer of mvmc_smooth_blocks' two);
+ * id_lo, the weights, kps17, Pmats, rig_of and members as the two entries above take them (the rows' scores give n_res); work (N,
+ * MVMC_SMOOTH_WORK_DOUBLES) f64 is overwritten with the factor.  Every sum runs in a fixed order inside the identity's own
+ * workgroup: the same bits alone, in a batch and from run to run.  Nothing is allocated or synchronised inside. */
+#define MVMC_SMOOTH_COV_INFO_DOUBLES 8
+int mvmc_smooth_cov(const mvmcSkeleton* skel_host, const double* x, const double* blk, const int32_t* id_lo, int n_ids, int n_frames,
+                    double root_vel, double root_acc, double ang_vel, double ang_acc, double mu, const double* kps17, int n_views,
+                    int p_max, const double* Pmats, const int32_t* rig_of, const int32_t* members, double* work, double* jcov, double* pvar,
+                    double* cinfo, mvmcStream_t stream);
+
 /* ---- fixed-lag smoothing of live sessions (multiview_motion_capture_amd/live_smoothing.py).  The objective is the trajectory
  * smoother's above; the problem is a short sliding window per live identity (one tracklet of one session), and ONE launch does a whole
  * tick of every identity of every session: one 256-lane workgroup per item.  State that stays on the device between ticks, per

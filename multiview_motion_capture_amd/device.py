@@ -461,6 +461,33 @@ def smooth_step(x: torch.Tensor, x_trial: torch.Tensor, blk: torch.Tensor, id_lo
           "mvmc_smooth_step")
 
 
+def smooth_cov(x: torch.Tensor, blk: torch.Tensor, id_lo: torch.Tensor, weights, mu: float, kps17: torch.Tensor, Pmats: torch.Tensor,
+               rig_of: torch.Tensor, members: torch.Tensor, work: torch.Tensor, jcov: torch.Tensor, pvar: torch.Tensor,
+               cinfo: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None) -> None:
+    """The per-frame covariance of the smoothed trajectory at x (include/mvmc.h: mvmc_smooth_cov), one workgroup per identity; blk
+    (N,820) the data blocks AT x, weights = (root_vel, root_acc, ang_vel, ang_acc), mu the damping of the inverted A + mu diag A.
+    work (N,3940) is overwritten; jcov (N,18,6), pvar (N,39) and cinfo (n_ids,8) are filled (unit variance)."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    N = x.shape[0]
+    n_ids = id_lo.shape[0] - 1
+    _req(x, torch.float64, "x", (N, 68))
+    _req(blk, torch.float64, "blk", (N, _cabi.SMOOTH_BLOCK_DOUBLES))
+    _req(id_lo, torch.int32, "id_lo", (n_ids + 1,))
+    _req(rig_of, torch.int32, "rig_of", (N,))
+    _req(members, torch.int32, "members", (N, Cn))
+    _req(work, torch.float64, "work", (N, _cabi.SMOOTH_WORK_DOUBLES))
+    _req(jcov, torch.float64, "jcov", (N, _cabi.SMOOTH_JOINTS, 6))
+    _req(pvar, torch.float64, "pvar", (N, _cabi.SMOOTH_K))
+    _req(cinfo, torch.float64, "cinfo", (n_ids, _cabi.SMOOTH_COV_INFO_DOUBLES))
+    rv, ra, av, aa = (float(w) for w in weights)
+    check(_cabi.load().mvmc_smooth_cov(C.byref(sk), _p(x), _p(blk), _p(id_lo), n_ids, N, rv, ra, av, aa, float(mu), _p(kps17), Cn, P,
+                                       _p(Pmats), _p(rig_of), _p(members), _p(work), _p(jcov), _p(pvar), _p(cinfo), _stream()),
+          "mvmc_smooth_cov")
+
+
 def smooth_window_work(n_items: int, window: int, dev) -> torch.Tensor:
     """Workspace of mvmc_smooth_window for ``n_items`` identities of one tick, sized by the identities active in the tick
     (include/mvmc.h: mvmc_smooth_window_work_doubles)."""

@@ -20,8 +20,9 @@ nearest earlier record frame's.  The solve is Levenberg-Marquardt, (A + mu diag 
 the exact prior Hessian, factored exactly by a block-banded Cholesky; mu starts at LM_MU0, / 10 after an accepted trial, x 10 after a
 rejected one; stop on max_iter, LM_XTOL or LM_FTOL, as the body fit's length step.
 
-Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; selection: mvmc_body_observe); NumPy
-restatement: tests/smooth_np.py.  Sequences with the same number of cameras share every launch, each with its own rig.
+Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; selection: mvmc_body_observe), the optional
+per-frame covariance csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov); NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py.
+Sequences with the same number of cameras share every launch, each with its own rig.
 """
 from __future__ import annotations
 
@@ -41,10 +42,12 @@ ANG_VEL, ANG_ACC = 1e4, 1e4      # px^2 / rad^2
 LM_MU0 = 1e-3       # Marquardt's damping: (A + mu diag(A)) d = -g, mu dimensionless
 LM_FTOL = 1e-12     # stop: predicted or achieved reduction below LM_FTOL E
 LM_XTOL = 1e-10     # stop: |d|_inf below LM_XTOL (m / rad)
+COV_MU = 1e-8       # covariance="joints" inverts A + COV_MU diag A: A alone is singular (the knees' Rz angles move no joint)
 MAX_ITER_CAP = 24   # include/mvmc.h: MVMC_SMOOTH_INFO_DOUBLES - 8
 MAX_VIEWS = 64      # include/mvmc.h: MVMC_SMOOTH_MAX_VIEWS
 MAX_WORK_BYTES = 1 << 30
 _BLOCK, _WORK = 820, 3940   # include/mvmc.h: doubles per row
+_JOINTS, _K, _COV_INFO = 18, 39, 8   # include/mvmc.h: skeleton joints, MVMC_SMOOTH_K, MVMC_SMOOTH_COV_INFO_DOUBLES
 
 
 def stage1_columns() -> np.ndarray:
@@ -131,6 +134,19 @@ def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_byte
     return w
 
 
+def _check_covariance(covariance, noise_px):
+    if covariance is not None and not (isinstance(covariance, str) and covariance == "joints"):
+        raise ValueError(f"smooth_sequences: covariance must be None or \"joints\", got {covariance!r}")
+    if noise_px is None:
+        return None
+    if covariance is None:
+        raise ValueError("smooth_sequences: noise_px without covariance=\"joints\" has nothing to scale")
+    if isinstance(noise_px, (str, bytes, bool)) or not isinstance(noise_px, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(noise_px) or not noise_px > 0:
+        raise ValueError(f"smooth_sequences: noise_px must be None or a finite number > 0, got {noise_px!r}")
+    return float(noise_px)
+
+
 def _check(sequences, tracklets_per_sequence):
     return check_records(sequences, tracklets_per_sequence, "smooth_sequences", increasing=True, finite=True,
                          cameras=(1, MAX_VIEWS, f"sequence {{s}}: {{C}} cameras, at most {MAX_VIEWS}"))
@@ -139,7 +155,7 @@ def _check(sequences, tracklets_per_sequence):
 def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], root_vel: float = ROOT_VEL,
                      root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
                      fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0",
-                     timings: Optional[dict] = None) -> List[list]:
+                     timings: Optional[dict] = None, covariance: Optional[str] = None, noise_px: Optional[float] = None) -> List[list]:
     """Smooth every identity of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows
     track_sequences and fit_sequences take -- from its MvTracklet records (fit_sequences, track_sequences, run_main_batched,
     MvTracker.update_4d, LivePool).  Returns, per sequence, NEW records in the input order (the inputs are not touched): the same
@@ -151,9 +167,21 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     Sequences with the same camera count share every launch; max_work_bytes caps the device workspace (~45 KB per frame): a group
     larger than the cap runs as several launch sequences one after another (an identity larger than the cap gets one of its own).
     timings: a dict that receives the seconds spent in {"prepare" (input checks, unwrapping and interpolation, packing and uploads),
-    "select", "blocks", "solve", "records"} (synchronising between the parts)."""
+    "select", "blocks", "solve", "records"} (synchronising between the parts), and "covariance" when that is asked for.
+    covariance="joints" (default None: nothing below is computed or set): how far each pose can be trusted.  After the solve, one more
+    launch per partition (include/mvmc.h: mvmc_smooth_cov) takes the diagonal blocks of (A + COV_MU diag A)^-1 at the returned
+    trajectory, A = the Gauss-Newton data blocks + the exact prior Hessian: the Laplace covariance of E (the damping because A alone
+    is singular: the two knees' Rz angles move no joint; their smooth_param_sigma is large and says only that), conditional on the
+    six held joints' angles, the per-frame bone lengths, the rig and the view selection.  Every record gets, rows as ``poses``:
+    ``smooth_noise_px`` = noise_px if given, else sqrt(2 E_data / (smooth_nres - smooth_edof)) (NaN when that is not positive): the noise of a score-1 keypoint in
+    pixels; ``smooth_joint_cov`` (n,18,3,3) m^2 = smooth_noise_px^2 D_K Sigma_tt D_K^T per skeleton joint; ``smooth_joint_sigma`` (n,18)
+    m = sqrt(trace); ``smooth_param_sigma`` (n,39) m / rad in stage1_columns() order; ``smooth_edof`` = tr(A^-1 J^T J), ``smooth_nres``
+    the residuals with a non-zero score, ``smooth_cov_status`` 0 solved, 1 A is singular (NaN arrays), 2 a record of fewer than two
+    frames (NaN arrays).  The prior is a regulariser with swept weights, not a fitted motion model: the calibration of these numbers is
+    measured, not promised."""
     t_start = time.perf_counter()
     w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
+    noise_px = _check_covariance(covariance, noise_px)
     if no_sequences(sequences, tracklets_per_sequence, "smooth_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence)
@@ -162,10 +190,12 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     from . import device as dev
     d = torch.device(device)
     T = dev.uploader(d)
-    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records"))
+    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records") + (("covariance",) if covariance else ()))
     tm["prepare"] = time.perf_counter() - t_start
     out: List[list] = [[None] * len(r) for r in recs]
     per_row = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
+    if covariance:
+        per_row += 8 * (_JOINTS * 6 + _K)
     for lay in plan_groups(shapes, 1):
         if not any(recs[i] for i in lay.seq_ids):
             continue
@@ -225,14 +255,29 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 t0 = lap("blocks", t0)
                 dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info, work)
                 t0 = lap("solve", t0)
+            cov = None
+            if covariance:
+                # the blocks AT x (the loop's last blocks are the last trial's, which may have been rejected) into buffer 0, steered
+                # by a control word of its own: the solve's ctl and info stay as they are, and blk is not read again
+                ctl_x = torch.zeros((len(part), 4), dtype=torch.int32, device=d)
+                ctl_x[:, 1] = 1
+                jcov = torch.empty((N, _JOINTS, 6), dtype=torch.float64, device=d)
+                pvar = torch.empty((N, _K), dtype=torch.float64, device=d)
+                cinfo = torch.empty((len(part), _COV_INFO), dtype=torch.float64, device=d)
+                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x, id_of_d, ctl_x, blk)
+                dev.smooth_cov(x, blk[0], id_lo_d, w, COV_MU, k17, Pm_d, rig_d, mem_d, work, jcov, pvar, cinfo)
+                t0 = lap("covariance", t0)
+                cov = (jcov.cpu().numpy(), pvar.cpu().numpy(), cinfo.cpu().numpy())
             jn = dev.fk(x).cpu().numpy()
             xs, inf = x.cpu().numpy(), info.cpu().numpy()
             for s, p in enumerate(part):
                 sl = slice(id_lo[s], id_lo[s + 1])
-                res[p[0]] = (xs[sl], jn[sl], inf[s])
+                res[p[0]] = (xs[sl], jn[sl], inf[s]) + ((cov[0][sl], cov[1][sl], cov[2][s]) if cov else ())
             lap("records", t0)
         t0 = time.perf_counter()
         _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, sel.Pg)
+        if covariance:
+            _covariance_fields(out, items, traj, res, fill_gaps, noise_px)
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
@@ -246,7 +291,7 @@ def _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, r
         f, par, jnt = recs[i][j]
         if a in tr:
             _, _, filled, mem, nvf, _ = tr[a]
-            xs, jn, inf = res[a]
+            xs, jn, inf = res[a][:3]
             idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
             poses = pose_tuples(f[0] + idx, xs[idx], jn[idx])
             cost = np.array([inf[0], inf[1], inf[2], inf[3]])
@@ -271,9 +316,39 @@ def _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, r
         out[i][j] = t
 
 
+def _covariance_fields(out, items, traj, res, fill_gaps, noise_px):
+    """The smooth_* covariance attributes of the group's records (smooth_sequences' docstring), from the unit-variance device outputs."""
+    tr = {p[0]: p for p in traj}
+    for a, (i, j) in enumerate(items):
+        t = out[i][j]
+        if a in tr:
+            filled = tr[a][2]
+            jc6, pv, ci = res[a][3:6]
+            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
+            status, e_data, n_res, edof = int(ci[0]), float(ci[1]), ci[2], float(ci[3])
+            jc = jc6[idx][:, :, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, _JOINTS, 3, 3)
+            pv = pv[idx]
+        else:   # fewer than two frames: nothing was solved
+            status, e_data, n_res, edof = 2, 0.0, np.nan, np.nan
+            jc, pv = np.full((1, _JOINTS, 3, 3), np.nan), np.full((1, _K), np.nan)
+        if noise_px is not None:
+            s = noise_px
+        else:
+            s = math.sqrt(2.0 * e_data / (n_res - edof)) if status == 0 and n_res - edof > 0 else math.nan
+        t.smooth_noise_px = float(s)
+        t.smooth_joint_cov = (s * s) * jc
+        t.smooth_joint_sigma = np.sqrt((s * s) * (jc[:, :, 0, 0] + jc[:, :, 1, 1] + jc[:, :, 2, 2]))
+        t.smooth_param_sigma = np.sqrt((s * s) * pv)
+        t.smooth_edof = edof
+        t.smooth_nres = int(n_res) if status == 0 else 0
+        t.smooth_cov_status = status
+
+
 def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, root_vel: float = ROOT_VEL,
                      root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
-                     fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0", timings: Optional[dict] = None) -> list:
+                     fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0", timings: Optional[dict] = None,
+                     covariance: Optional[str] = None, noise_px: Optional[float] = None) -> list:
     """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records."""
     return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel, ang_acc=ang_acc,
-                            max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings)[0]
+                            max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings,
+                            covariance=covariance, noise_px=noise_px)[0]
