@@ -656,29 +656,74 @@ def rig_start(obs: torch.Tensor, rig_of: torch.Tensor, Pmats: torch.Tensor, min_
     return X0, dist
 
 
-def rig_work(n_tiles: int, n_seqs: int, n_views: int, dev):
-    """(part (T, mvmc_rig_part_doubles), part2 (T,4), red (S, mvmc_rig_red_doubles)) of mvmc_rig_accumulate / mvmc_rig_step."""
+def _rig_doubles(n_views: int, n_intr=None):
+    """(doubles of part per tile, doubles of red per sequence) of the trial entries -- n_intr None: those without intrinsic unknowns;
+    -1 where the library refuses the sizes."""
     lib = _cabi.load()
-    pd, rd = int(lib.mvmc_rig_part_doubles(int(n_views))), int(lib.mvmc_rig_red_doubles(int(n_views)))
-    if pd < 0 or rd < 0:
-        raise ValueError(f"rig_work: {n_views} cameras outside 2 .. {_cabi.RIG_MAX_CAMS}")
+    if n_intr is None:
+        return int(lib.mvmc_rig_part_doubles(int(n_views))), int(lib.mvmc_rig_red_doubles(int(n_views)))
+    return int(lib.mvmc_rig_part_doubles_intr(int(n_views), int(n_intr))), int(lib.mvmc_rig_red_doubles_intr(int(n_views), int(n_intr)))
+
+
+def _rig_work(pd: int, rd: int, n_tiles: int, n_seqs: int, dev):
     return (torch.empty((max(n_tiles, 1), pd), dtype=torch.float64, device=dev),
             torch.empty((max(n_tiles, 1), 4), dtype=torch.float64, device=dev), torch.zeros((n_seqs, rd), dtype=torch.float64, device=dev))
 
 
-def _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red):
-    N, S, Cn = X.shape[0], seq.shape[0], slot.shape[1]
+def rig_work(n_tiles: int, n_seqs: int, n_views: int, dev):
+    """(part (T, mvmc_rig_part_doubles), part2 (T,4), red (S, mvmc_rig_red_doubles)) of mvmc_rig_accumulate / mvmc_rig_step."""
+    pd, rd = _rig_doubles(n_views)
+    if pd < 0 or rd < 0:
+        raise ValueError(f"rig_work: {n_views} cameras outside 2 .. {_cabi.RIG_MAX_CAMS}")
+    return _rig_work(pd, rd, n_tiles, n_seqs, dev)
+
+
+def rig_work_intr(n_tiles: int, n_seqs: int, n_views: int, n_intr: int, dev):
+    """rig_work for the entries with intrinsic unknowns (mvmc_rig_part_doubles_intr, mvmc_rig_red_doubles_intr)."""
+    pd, rd = _rig_doubles(n_views, n_intr)
+    if pd < 0 or rd < 0:
+        raise ValueError(f"rig_work_intr: {n_views} cameras outside 2 .. {_cabi.RIG_MAX_CAMS} or n_intr {n_intr} not 1 or 3")
+    return _rig_work(pd, rd, n_tiles, n_seqs, dev)
+
+
+def _rig_trial(name, X, X_trial, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, scalars, work, loss=None, intr=None):
+    """What the six wrappers of the trial entries share: the buffers' checks and the call of the entry ``name``.  X_trial None: an
+    accumulate entry (scalars max_iter, mu0, variant; work is part), else a step entry (scalars max_iter, ftol, xtol; work is part2).
+    loss: None or (loss, loss_px); intr: None or (n_intr, islot, K0, focal_sigma, centre_sigma) -- n_intr is checked by the entry
+    itself (the widths of red and part only where it is valid)."""
+    N, T, S, Cn = X.shape[0], int(tile.shape[0]), seq.shape[0], slot.shape[1]
     _req(X, torch.float64, "X", (N, 3))
     _req(uv, torch.float64, "uv", (N, Cn, 2))
     _req(tile, torch.int32, "tile", (None, 4))
     _req(seq, torch.int32, "seq", (S, 4))
     _req(slot, torch.int32, "slot", (S, Cn))
+    if intr is not None:
+        _req(intr[1], torch.int32, "islot", (S, Cn))
+        _req(intr[2], torch.float64, "K0", (S, Cn, 3))
     _req(cams, torch.float64, "cams", (S, Cn, _cabi.RIG_CAM_DOUBLES))
     _req(cams_trial, torch.float64, "cams_trial", (S, Cn, _cabi.RIG_CAM_DOUBLES))
     _req(ctl, torch.int32, "ctl", (S, 4))
     _req(info, torch.float64, "info", (S, _cabi.RIG_INFO_DOUBLES))
-    _req(red, torch.float64, "red", (S, int(_cabi.load().mvmc_rig_red_doubles(Cn))))
-    return N, int(tile.shape[0]), S, Cn
+    pd, rd = _rig_doubles(Cn, None if intr is None else intr[0])
+    _req(red, torch.float64, "red", (S, rd if rd >= 0 else None))
+    if X_trial is None:
+        what = "part"
+        _req(work, torch.float64, what, (None, pd if pd >= 0 else None))
+        args = [_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info), N, T, S, Cn, int(scalars[0]),
+                float(scalars[1]), int(scalars[2]), _p(work), _p(red)]
+    else:
+        what = "part2"
+        _req(X_trial, torch.float64, "X_trial", (N, 3))
+        _req(work, torch.float64, what, (None, 4))
+        args = [_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info), _p(red), N, T, S, Cn,
+                int(scalars[0]), float(scalars[1]), float(scalars[2]), _p(work)]
+    if work.shape[0] < T:
+        raise ValueError(f"{what}: {work.shape[0]} rows for {T} tiles")
+    if loss is not None:
+        args += [int(loss[0]), float(loss[1])]
+    if intr is not None:
+        args += [int(intr[0]), _p(intr[1]), _p(intr[2]), float(intr[3]), float(intr[4])]
+    check(getattr(_cabi.load(), name)(*args, _stream()), name)
 
 
 def rig_accumulate(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor, cams: torch.Tensor,
@@ -686,13 +731,7 @@ def rig_accumulate(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: t
                    red: torch.Tensor, variant: int = 1) -> None:
     """First half of a trial of the rig refinement (include/mvmc.h: mvmc_rig_accumulate): the reduced camera system of every running
     sequence at (X, cams) and its mu into red, its solution and the trial cameras.  variant 1: matrix cores, 0: FMAs."""
-    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
-    _req(part, torch.float64, "part", (None, int(_cabi.load().mvmc_rig_part_doubles(Cn))))
-    if part.shape[0] < T:
-        raise ValueError(f"part: {part.shape[0]} rows for {T} tiles")
-    check(_cabi.load().mvmc_rig_accumulate(_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info), N, T,
-                                           S, Cn, int(max_iter), float(mu0), int(variant), _p(part), _p(red), _stream()),
-          "mvmc_rig_accumulate")
+    _rig_trial("mvmc_rig_accumulate", X, None, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, (max_iter, mu0, variant), part)
 
 
 def rig_step(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
@@ -700,70 +739,23 @@ def rig_step(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: tor
              ftol: float, xtol: float, part2: torch.Tensor) -> None:
     """Second half of a trial (include/mvmc.h: mvmc_rig_step): the points' steps, the trial cost, accept / reject with the gauge
     rescale, the stop rules.  X, cams, ctl and info are updated in place."""
-    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
-    _req(X_trial, torch.float64, "X_trial", (N, 3))
-    _req(part2, torch.float64, "part2", (None, 4))
-    if part2.shape[0] < T:
-        raise ValueError(f"part2: {part2.shape[0]} rows for {T} tiles")
-    check(_cabi.load().mvmc_rig_step(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
-                                     _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), _stream()),
-          "mvmc_rig_step")
+    _rig_trial("mvmc_rig_step", X, X_trial, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, (max_iter, ftol, xtol), part2)
 
 
 def rig_accumulate_robust(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
                           cams: torch.Tensor, cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, max_iter: int, mu0: float,
                           part: torch.Tensor, red: torch.Tensor, variant: int = 1, loss: int = 0, loss_px: float = 0.0) -> None:
     """rig_accumulate with a robust loss (include/mvmc.h: mvmc_rig_accumulate_robust): loss 0 none, 1 Huber, 2 Cauchy at loss_px."""
-    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
-    _req(part, torch.float64, "part", (None, int(_cabi.load().mvmc_rig_part_doubles(Cn))))
-    if part.shape[0] < T:
-        raise ValueError(f"part: {part.shape[0]} rows for {T} tiles")
-    check(_cabi.load().mvmc_rig_accumulate_robust(_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
-                                                  N, T, S, Cn, int(max_iter), float(mu0), int(variant), _p(part), _p(red), int(loss),
-                                                  float(loss_px), _stream()), "mvmc_rig_accumulate_robust")
+    _rig_trial("mvmc_rig_accumulate_robust", X, None, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, (max_iter, mu0, variant), part,
+               loss=(loss, loss_px))
 
 
 def rig_step_robust(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
                     cams: torch.Tensor, cams_trial: torch.Tensor, ctl: torch.Tensor, info: torch.Tensor, red: torch.Tensor, max_iter: int,
                     ftol: float, xtol: float, part2: torch.Tensor, loss: int = 0, loss_px: float = 0.0) -> None:
     """rig_step with a robust loss (include/mvmc.h: mvmc_rig_step_robust): the trial cost and every cost in info are sum rho."""
-    N, T, S, Cn = _rig_req(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red)
-    _req(X_trial, torch.float64, "X_trial", (N, 3))
-    _req(part2, torch.float64, "part2", (None, 4))
-    if part2.shape[0] < T:
-        raise ValueError(f"part2: {part2.shape[0]} rows for {T} tiles")
-    check(_cabi.load().mvmc_rig_step_robust(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl),
-                                            _p(info), _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), int(loss),
-                                            float(loss_px), _stream()), "mvmc_rig_step_robust")
-
-
-def rig_work_intr(n_tiles: int, n_seqs: int, n_views: int, n_intr: int, dev):
-    """rig_work for the entries with intrinsic unknowns (mvmc_rig_part_doubles_intr, mvmc_rig_red_doubles_intr)."""
-    lib = _cabi.load()
-    pd, rd = int(lib.mvmc_rig_part_doubles_intr(int(n_views), int(n_intr))), int(lib.mvmc_rig_red_doubles_intr(int(n_views), int(n_intr)))
-    if pd < 0 or rd < 0:
-        raise ValueError(f"rig_work_intr: {n_views} cameras outside 2 .. {_cabi.RIG_MAX_CAMS} or n_intr {n_intr} not 1 or 3")
-    return (torch.empty((max(n_tiles, 1), pd), dtype=torch.float64, device=dev),
-            torch.empty((max(n_tiles, 1), 4), dtype=torch.float64, device=dev), torch.zeros((n_seqs, rd), dtype=torch.float64, device=dev))
-
-
-def _rig_req_intr(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_intr, islot, K0):
-    """The buffers of a trial with intrinsic unknowns.  n_intr is checked by the entry itself (red's width only where it is valid)."""
-    N, S, Cn = X.shape[0], seq.shape[0], slot.shape[1]
-    _req(X, torch.float64, "X", (N, 3))
-    _req(uv, torch.float64, "uv", (N, Cn, 2))
-    _req(tile, torch.int32, "tile", (None, 4))
-    _req(seq, torch.int32, "seq", (S, 4))
-    _req(slot, torch.int32, "slot", (S, Cn))
-    _req(islot, torch.int32, "islot", (S, Cn))
-    _req(K0, torch.float64, "K0", (S, Cn, 3))
-    _req(cams, torch.float64, "cams", (S, Cn, _cabi.RIG_CAM_DOUBLES))
-    _req(cams_trial, torch.float64, "cams_trial", (S, Cn, _cabi.RIG_CAM_DOUBLES))
-    _req(ctl, torch.int32, "ctl", (S, 4))
-    _req(info, torch.float64, "info", (S, _cabi.RIG_INFO_DOUBLES))
-    rd = int(_cabi.load().mvmc_rig_red_doubles_intr(Cn, int(n_intr)))
-    _req(red, torch.float64, "red", (S, rd if rd >= 0 else None))
-    return N, int(tile.shape[0]), S, Cn
+    _rig_trial("mvmc_rig_step_robust", X, X_trial, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, (max_iter, ftol, xtol), part2,
+               loss=(loss, loss_px))
 
 
 def rig_accumulate_intr(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor, cams: torch.Tensor,
@@ -773,15 +765,8 @@ def rig_accumulate_intr(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, s
     """rig_accumulate_robust with n_intr (1: phi, 3: phi, dcx, dcy) intrinsic unknowns per camera with islot >= 0 and a Gaussian
     prior about K0 (S,C,3: fx, cx, cy) of focal_sigma (relative) and centre_sigma (px), +inf = none
     (include/mvmc.h: mvmc_rig_accumulate_intr)."""
-    N, T, S, Cn = _rig_req_intr(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_intr, islot, K0)
-    pd = int(_cabi.load().mvmc_rig_part_doubles_intr(Cn, int(n_intr)))
-    _req(part, torch.float64, "part", (None, pd if pd >= 0 else None))
-    if part.shape[0] < T:
-        raise ValueError(f"part: {part.shape[0]} rows for {T} tiles")
-    check(_cabi.load().mvmc_rig_accumulate_intr(_p(X), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl), _p(info),
-                                                N, T, S, Cn, int(max_iter), float(mu0), int(variant), _p(part), _p(red), int(loss),
-                                                float(loss_px), int(n_intr), _p(islot), _p(K0), float(focal_sigma), float(centre_sigma),
-                                                _stream()), "mvmc_rig_accumulate_intr")
+    _rig_trial("mvmc_rig_accumulate_intr", X, None, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, (max_iter, mu0, variant), part,
+               loss=(loss, loss_px), intr=(n_intr, islot, K0, focal_sigma, centre_sigma))
 
 
 def rig_step_intr(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, seq: torch.Tensor, slot: torch.Tensor,
@@ -790,15 +775,8 @@ def rig_step_intr(X: torch.Tensor, X_trial: torch.Tensor, uv: torch.Tensor, tile
                   centre_sigma: float, loss: int = 0, loss_px: float = 0.0) -> None:
     """rig_step_robust with intrinsic unknowns (include/mvmc.h: mvmc_rig_step_intr): every cost includes the prior, and cams takes the
     trial K of an accepted trial."""
-    N, T, S, Cn = _rig_req_intr(X, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, n_intr, islot, K0)
-    _req(X_trial, torch.float64, "X_trial", (N, 3))
-    _req(part2, torch.float64, "part2", (None, 4))
-    if part2.shape[0] < T:
-        raise ValueError(f"part2: {part2.shape[0]} rows for {T} tiles")
-    check(_cabi.load().mvmc_rig_step_intr(_p(X), _p(X_trial), _p(uv), _p(tile), _p(seq), _p(slot), _p(cams), _p(cams_trial), _p(ctl),
-                                          _p(info), _p(red), N, T, S, Cn, int(max_iter), float(ftol), float(xtol), _p(part2), int(loss),
-                                          float(loss_px), int(n_intr), _p(islot), _p(K0), float(focal_sigma), float(centre_sigma),
-                                          _stream()), "mvmc_rig_step_intr")
+    _rig_trial("mvmc_rig_step_intr", X, X_trial, uv, tile, seq, slot, cams, cams_trial, ctl, info, red, (max_iter, ftol, xtol), part2,
+               loss=(loss, loss_px), intr=(n_intr, islot, K0, focal_sigma, centre_sigma))
 
 
 def rig_weights(X: torch.Tensor, uv: torch.Tensor, tile: torch.Tensor, cams: torch.Tensor, loss: int, loss_px: float) -> torch.Tensor:

@@ -187,6 +187,35 @@ def test_several_sequences_in_one_launch():
         assert a["ctl"][s, 0] == STOP_XTOL and a["ctl"][s, 1] < 6
 
 
+# ---- c2. the entries without intrinsics are the case without intrinsic columns ----
+@pytest.mark.parametrize("n_intr", [1, 3])
+@pytest.mark.parametrize("name", ["c2", "c4_held_mid", "c8"])
+def test_pose_only_is_the_case_without_intrinsic_columns(name, n_intr):
+    """tests/rig_cases.py's problems through the _intr entries with every islot = -1 (K0 the input K, finite sigmas, no loss) against
+    mvmc_rig_accumulate / mvmc_rig_step with the case's own parameters, after one trial and after the whole solve: X, cams, cams_trial,
+    ctl, info and part2 bit-identical; the leading 6 n_free rows and columns of S and entries of g and d bit-identical; the rest of red
+    exactly the identity, with zeros in g and d."""
+    from test_gpu_rig_kernels import device_solve as plain_solve
+    c, p = rc.case(name), rc.params(name)
+    prob, K, Rt = c["prob"], c["K"], c["Rt"]
+    C = K.shape[0]
+    mode = {1: dict(intrinsics="focal", focal_sigma=0.05), 3: dict(intrinsics="focal+centre", focal_sigma=0.05, centre_sigma_px=10.0)}[n_intr]
+    M0, M, m = 6 * (C - 1), 6 * (C - 1) + n_intr * C, 6 * int((~prob["held"]).sum())
+    for steps in (1, None):
+        a = plain_solve([prob], K, [Rt], steps=steps, **p)
+        b = device_solve([prob], [K], [Rt], steps=steps, intrinsics_held=tuple(range(C)), **mode, **p)
+        assert (b["islot"] == -1).all()
+        for k in ("X", "cams", "cams_trial", "ctl", "info", "part2"):
+            assert np.array_equal(a[k], b[k], equal_nan=True), (k, steps)
+        ra, rb = a["red"][0], b["red"][0]
+        Sa, ga, da = ra[:M0 * M0].reshape(M0, M0), ra[M0 * M0:M0 * M0 + M0], ra[M0 * M0 + M0:]
+        Sb, gb, db = rb[:M * M].reshape(M, M), rb[M * M:M * M + M], rb[M * M + M:]
+        assert np.array_equal(Sa[:m, :m], Sb[:m, :m]) and np.array_equal(ga[:m], gb[:m]) and np.array_equal(da[:m], db[:m]), steps
+        assert np.array_equal(Sb[m:, m:], np.eye(M - m)) and not Sb[:m, m:].any() and not Sb[m:, :m].any(), steps
+        assert not gb[m:].any() and not db[m:].any(), steps
+        assert a["ctl"][0, 1] >= 1
+
+
 # ---- d. the argument checks ----
 def test_argument_checks_launch_nothing():
     """n_intr outside {1, 3}, a sigma that is <= 0 or NaN and variant 0 (refused on these entries: the stacked product runs on the

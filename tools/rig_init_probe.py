@@ -56,7 +56,7 @@ def merge(path, stats):
     with open(stats) as f:
         for r in csv.DictReader(f):
             r = {k.lower(): v for k, v in r.items()}
-            m = re.search(r"(pair|rig)_\w+(<\w+>)?", r.get("name", ""))
+            m = re.search(r"(pair|rig)_\w+(<[\w, ]+>)?", r.get("name", ""))
             if m:
                 rows.append({"kernel": m.group(0), "calls": int(r["calls"]), "total_us": float(r["totaldurationns"]) / 1e3,
                              "mean_us": float(r["averagens"]) / 1e3, "max_us": float(r["maxns"]) / 1e3})

@@ -1,5 +1,7 @@
 """Cost of the rig refinement's intrinsic unknowns (rig_refine.refine_rigs(intrinsics=...)) beside the refinement without them, in one run:
     python tools/rig_intr_probe.py [--sizes 1 8 64] [--frames 300] [--repeats 3] [--out profiles/rig_intr_probe.json]
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/rig_intr_probe.py --sizes 64 --trace-run
+(--trace-run: three trials per way at the largest size, for a kernel trace.)
 The sequences are tools/rig_refine_probe.py's (synth.generate(frames, 5, 4, seed_s, walk="scene"), each rig perturbed by 1 degree /
 3 cm) with every camera's focal length off by a seeded U(-3 %, +3 %); the records come from track_sequences on that rig.  Per S:
   trial_ms    device-event milliseconds of ONE trial's two entries at the packed start state of the S problems -- accumulate (tile
@@ -106,6 +108,7 @@ def main():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--trace-run", action="store_true")
     args = ap.parse_args()
     from multiview_motion_capture_amd import _cabi
     from multiview_motion_capture_amd.rig_refine import refine_rigs
@@ -116,7 +119,15 @@ def main():
     recs_all = track_sequences(seqs_all)
     probs_all = []
     refine_rigs(seqs_all, recs_all, max_iter=0, problems=probs_all)
-    modes = {"None": {}, "focal": dict(intrinsics="focal"), "focal+centre": dict(intrinsics="focal+centre", centre_sigma_px=CENTRE_SIGMA_PX)}
+    if args.trace_run:
+        import torch
+        st = pack(seqs_all, probs_all)
+        for _ in range(3):
+            for _, n in WAYS:
+                one_trial(st, n)
+        torch.cuda.synchronize()
+        return
+    modes ={"None": {}, "focal": dict(intrinsics="focal"), "focal+centre": dict(intrinsics="focal+centre", centre_sigma_px=CENTRE_SIGMA_PX)}
     res = {"frames_per_sequence": args.frames, "views": 5, "people": 4, "max_iter": 10, "focal_off_pct": 3.0, "centre_sigma_px": CENTRE_SIGMA_PX,
            "build": _cabi.build_info(), "sizes": {}}
     for S in args.sizes:

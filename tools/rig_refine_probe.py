@@ -55,7 +55,7 @@ def merge(path, stats):
         for r in csv.DictReader(f):
             r = {k.lower(): v for k, v in r.items()}
             if "rig_" in r.get("name", ""):
-                rows.append({"kernel": re.search(r"rig_\w+(<\w+>)?", r["name"]).group(0), "calls": int(r["calls"]), "total_us": float(r["totaldurationns"]) / 1e3,
+                rows.append({"kernel": re.search(r"rig_\w+(<[\w, ]+>)?", r["name"]).group(0), "calls": int(r["calls"]), "total_us": float(r["totaldurationns"]) / 1e3,
                              "mean_us": float(r["averagens"]) / 1e3, "max_us": float(r["maxns"]) / 1e3})
     res["trace_run_S64_kernels"] = rows
     text = json.dumps(res)

@@ -99,9 +99,9 @@ def merge(path, stats):
                 rows[m.group(0)] = {"calls": int(r["calls"]), "mean_us": float(r["averagens"]) / 1e3, "max_us": float(r["maxns"]) / 1e3}
     res["trace_run_kernels"] = rows
     ratio = {}
-    for k, v in rows.items():
-        m = re.fullmatch(r"(rig_\w+_kernel)<(.*?)([12])>", k)
-        base = rows.get(f"{m.group(1)}<{m.group(2)}0>") if m else None
+    for k, v in rows.items():   # rig_accum_kernel<MFMA, LOSS, NI>, rig_backsub_kernel<LOSS, NI>
+        m = re.fullmatch(r"(rig_(?:accum|backsub)_kernel)<(.*?)([12]), (\d)>", k)
+        base = rows.get(f"{m.group(1)}<{m.group(2)}0, {m.group(4)}>") if m else None
         if base:
             ratio[k] = v["mean_us"] / base["mean_us"]
     res["trace_run_ratio_to_loss_none"] = ratio
