@@ -591,6 +591,34 @@ int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* kps17, int n
                        double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
                        double* work, long long work_doubles, mvmcStream_t stream);
 
+/* ---- a robust loss on the smoothers' keypoint residuals (restated in tests/smooth_robust_np.py).  For one (selected view, observed
+ * joint) pair of a row: score s, plain pixel residual (ru, rv) = proj(X_k) - obs, e^2 = ru^2 + rv^2, delta = loss_px > 0 (pixels),
+ *   MVMC_SMOOTH_LOSS_HUBER   rho = 1/2 e^2, w = 1 for e <= delta; otherwise rho = delta (e - 1/2 delta), w = delta / e
+ *   MVMC_SMOOTH_LOSS_CAUCHY  rho = 1/2 delta^2 log1p(e^2 / delta^2), w = 1 / (1 + e^2 / delta^2)
+ * The score stays outside the loss: E_data = sum s^2 rho replaces 1/2 sum s^2 e^2 wherever a cost is read or written, and at every
+ * linearisation the pair's contribution to the blocks is multiplied by w (iteratively reweighted, no second-order correction); a pair
+ * with s = 0 contributes nothing.  The blocks keep their layout (J^T W J upper triangle, J^T W r, sum s^2 rho), so the step, the sweep
+ * and the covariance entry read them as they are; the prior is not touched.  Every buffer and precondition is that of the entry
+ * without _robust.  MVMC_SMOOTH_LOSS_NONE runs that entry's kernel (loss_px is not read); a loss outside these three, or with a loss a
+ * loss_px that is not a finite number > 0: MVMC_ERR_ARG.
+ * The weights entry, one wave per row, does FK and the projections only: w (N, C, 16) f64 out, the weight of camera c's member and
+ * observed joint k (the IK's observation order) at x (N,68) -- 1 with MVMC_SMOOTH_LOSS_NONE -- and NaN where the camera has no member
+ * in the row or the pair's score is 0. ---- */
+#define MVMC_SMOOTH_LOSS_NONE 0
+#define MVMC_SMOOTH_LOSS_HUBER 1
+#define MVMC_SMOOTH_LOSS_CAUCHY 2
+int mvmc_smooth_blocks_robust(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                              const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of, const int32_t* ctl,
+                              int n_frames, double* blk, int loss, double loss_px, mvmcStream_t stream);
+int mvmc_smooth_obs_weights(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                            const int32_t* rig_of, const int32_t* members, const double* x, int n_frames, int loss, double loss_px,
+                            double* w, mvmcStream_t stream);
+int mvmc_smooth_window_robust(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats, int n_rigs,
+                              const int32_t* items, int n_items, const double* new_params, const int32_t* new_members, int n_new,
+                              double* rows, int32_t* members, int32_t* count, int n_slots, int window, int n_iter, double root_vel,
+                              double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
+                              double* work, long long work_doubles, int loss, double loss_px, mvmcStream_t stream);
+
 /* ---- re-linking of the records of one person (multiview_motion_capture_amd/relinking.py).  No counterpart in the reference.  Per
  * sequence, its records in (first frame, track id) order are the nodes; record a may be followed by record b when 1 <= gap =
  * first(b) - last(a) <= max_gap, at the cost mean_k |last_joints(a)[k] + v gap - first_joints(b)[k]| (metres; v = the mean of a's end

@@ -5,10 +5,12 @@
 //   blocks  ONE wave per (identity, frame): FK, the stage-1 residual and its analytic Jacobian (angular velocity x lever arm through the
 //           projection), reduced per observed joint first (W_k = sum_v s^2 (du du^T + dv dv^T), t_k = sum_v s (du fu + dv fv)), then
 //           J^T J = sum_k D_k^T W_k D_k and J^T r = sum_k D_k^T t_k with D_k = d X_k / d x (3 x 39): the upper triangle, J^T r and E_t of
-//           the frame into one of two block buffers (the other holds the blocks of the accepted point);
+//           the frame into one of two block buffers (the other holds the blocks of the accepted point); with a robust loss
+//           (mvmc_smooth_blocks_robust) the blocks of the reweighted model, the same layout: J^T W J, J^T W r, sum s^2 rho;
 //   step    ONE 256-lane workgroup per identity: the accept / reject decision on the last trial (E summed in a fixed order), then one
 //           block-banded solve of (A + mu diag(A)) d = -g over all the identity's frames (mvmc_smooth_sweep.h, the sweep the live
 //           smoother runs too; the factor goes to the caller's workspace), and the next trial point.
+//   weights ONE wave per row, after the solve: FK and the projections alone, the loss's weight of every (camera, observed joint) pair.
 // Every sum runs in a fixed order inside one identity's own lanes: an identity's numbers depend on nothing else in the launch.
 #define MVMC_DEVICE_ONLY
 #include "mvmc_common.h"
@@ -21,18 +23,49 @@ namespace {
 #include "mvmc_smooth_row.h"
 #include "mvmc_smooth_sweep.h"
 
+template <int LOSS>
 __global__ void __launch_bounds__(64) smooth_blocks_kernel(Ik1Tables T, const double* __restrict__ kps17, const double* __restrict__ Pmats,
                                                            int C, int Pmax, const int32_t* __restrict__ rig_of,
                                                            const int32_t* __restrict__ members, const double* __restrict__ xe,
                                                            const int32_t* __restrict__ id_of, const int32_t* __restrict__ ctl,
-                                                           int n_frames, double* __restrict__ blk) {
+                                                           int n_frames, double* __restrict__ blk, double loss_px) {
     __shared__ SmBlkLds L;
     const int f = blockIdx.x;
     const int id = uni((int)id_of[f]);
     if (uni((int)ctl[id * 4]) != 0) return;                      // stopped identity: nothing to evaluate
     const int buf = 1 - uni((int)ctl[id * 4 + 1]);               // the buffer that does not hold the accepted point's blocks
-    sm_row_block(T, L, kps17, Pmats + (size_t)rig_of[f] * C * 12, C, Pmax, members + (size_t)f * C, xe + (size_t)f * 68,
-                 blk + ((size_t)buf * n_frames + f) * SM_BLK);
+    sm_row_block<LOSS>(T, L, kps17, Pmats + (size_t)rig_of[f] * C * 12, C, Pmax, members + (size_t)f * C, xe + (size_t)f * 68,
+                       blk + ((size_t)buf * n_frames + f) * SM_BLK, loss_px);
+}
+
+// ---- weights ----
+struct SmPosLds { double Rl[18 * 9], Rg[18 * 9], pos[18 * 3]; };
+
+// One row per wave: w[f][c][k] = the loss's weight of camera c's member and observed joint k at x, NaN without a member or a score.
+// Every slot of the row is written exactly once, by the lane that owns it.
+template <int LOSS>
+__global__ void __launch_bounds__(64) smooth_obs_weights_kernel(Ik1Tables T, const double* __restrict__ kps17,
+                                                                const double* __restrict__ Pmats, int C, int Pmax,
+                                                                const int32_t* __restrict__ rig_of, const int32_t* __restrict__ members,
+                                                                const double* __restrict__ xe, double loss_px, double* __restrict__ wout) {
+    __shared__ SmPosLds L;
+    const int f = blockIdx.x, lane = threadIdx.x & 63;
+    sm_row_fk<false>(T, L, xe + (size_t)f * 68);
+    const double* Prig = Pmats + (size_t)rig_of[f] * C * 12;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    for (int i = lane; i < C * NOBS; i += 64) {
+        const int c = i / NOBS, k = i - c * NOBS, m = members[(size_t)f * C + c];
+        double wl = nan;
+        if (m >= 0) {
+            const int K = kIkSkel[k];
+            double ob0, ob1, s, w, u, vv, rho;
+            sm_pair(kps17 + (size_t)m * 51, Prig + (size_t)((m / Pmax) % C) * 12, kIkObs[k], L.pos[3 * K], L.pos[3 * K + 1],
+                    L.pos[3 * K + 2], ob0, ob1, s, w, u, vv);
+            const double ru = u - ob0, rv = vv - ob1;
+            if (s != 0.0) sm_rho_w<LOSS>(ru * ru + rv * rv, loss_px, rho, wl);
+        }
+        wout[((size_t)f * C + c) * NOBS + k] = wl;
+    }
 }
 
 // ---- step ----
@@ -122,16 +155,45 @@ __global__ void __launch_bounds__(SM_THREADS) smooth_step_kernel(Ik1Tables T, do
 
 }  // namespace
 
-extern "C" int mvmc_smooth_blocks(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
-                                  const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of, const int32_t* ctl,
-                                  int n_frames, double* blk, mvmcStream_t stream) {
+extern "C" int mvmc_smooth_blocks_robust(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                         const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of,
+                                         const int32_t* ctl, int n_frames, double* blk, int loss, double loss_px, mvmcStream_t stream) {
     if (!skel_host || n_frames < 0 || n_views <= 0 || n_views > MVMC_SMOOTH_MAX_VIEWS || p_max <= 0) return MVMC_ERR_ARG;
+    if (!sm_loss_ok(loss, loss_px)) return MVMC_ERR_ARG;
     if (n_frames == 0) return MVMC_OK;
     if (!kps17 || !Pmats || !rig_of || !members || !x || !id_of || !ctl || !blk) return MVMC_ERR_ARG;
     Ik1Tables T;
     if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(smooth_blocks_kernel, dim3(n_frames), dim3(64), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, rig_of,
-                       members, x, id_of, ctl, n_frames, blk);
+    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_blocks_kernel<MVMC_SMOOTH_LOSS_HUBER>
+                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_blocks_kernel<MVMC_SMOOTH_LOSS_CAUCHY>
+                                                    : smooth_blocks_kernel<MVMC_SMOOTH_LOSS_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(n_frames), dim3(64), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, rig_of, members, x,
+                       id_of, ctl, n_frames, blk, loss_px);
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
+}
+
+extern "C" int mvmc_smooth_blocks(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                  const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of, const int32_t* ctl,
+                                  int n_frames, double* blk, mvmcStream_t stream) {
+    return mvmc_smooth_blocks_robust(skel_host, kps17, n_views, p_max, Pmats, rig_of, members, x, id_of, ctl, n_frames, blk,
+                                     MVMC_SMOOTH_LOSS_NONE, 0.0, stream);
+}
+
+extern "C" int mvmc_smooth_obs_weights(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                       const int32_t* rig_of, const int32_t* members, const double* x, int n_frames, int loss,
+                                       double loss_px, double* w, mvmcStream_t stream) {
+    if (!skel_host || n_frames < 0 || n_views <= 0 || n_views > MVMC_SMOOTH_MAX_VIEWS || p_max <= 0) return MVMC_ERR_ARG;
+    if (!sm_loss_ok(loss, loss_px)) return MVMC_ERR_ARG;
+    if (n_frames == 0) return MVMC_OK;
+    if (!kps17 || !Pmats || !rig_of || !members || !x || !w) return MVMC_ERR_ARG;
+    Ik1Tables T;
+    if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
+    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_obs_weights_kernel<MVMC_SMOOTH_LOSS_HUBER>
+                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_obs_weights_kernel<MVMC_SMOOTH_LOSS_CAUCHY>
+                                                    : smooth_obs_weights_kernel<MVMC_SMOOTH_LOSS_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(n_frames), dim3(64), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, rig_of, members, x,
+                       loss_px, w);
     MVMC_CHECK_LAUNCH();
     return MVMC_OK;
 }

@@ -24,34 +24,21 @@ struct SmBlkLds {
     int nv;
 };
 
-// One row on the calling wave: members (C) pose indices or -1, Prig the row's rig (C,3,4), x the row's 68 parameters -> out (SM_BLK)
-__device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, const double* __restrict__ kps17,
-                                             const double* __restrict__ Prig, int C, int Pmax, const int32_t* __restrict__ members,
-                                             const double* __restrict__ x, double* __restrict__ out) {
+// FK of one row on the calling wave: x the row's 68 parameters -> L.Rl, L.Rg (local and global rotations) and L.pos (joints); AXES: L.ax
+// too, the Euler axes of every joint in the global frame.  L.pos is complete on return; L.ax needs one MVMC_WAVE_SYNC more.
+template <bool AXES, class Lds>
+__device__ __forceinline__ void sm_row_fk(const Ik1Tables& T, Lds& L, const double* __restrict__ x) {
     const int lane = threadIdx.x & 63;
-    if (lane == 0) {
-        int n = 0;
-        for (int c = 0; c < C; ++c) {
-            const int m = members[c];
-            if (m >= 0 && n < MVMC_SMOOTH_MAX_VIEWS) { L.mq[n] = m; L.mc[n] = (m / Pmax) % C; ++n; }
-        }
-        L.nv = n;
-    }
-    MVMC_WAVE_SYNC();
-    const int nv = uni(L.nv);
-    if (nv == 0) {   // no data: the prior alone places the frame
-        for (int i = lane; i < SM_BLK; i += 64) out[i] = 0.0;
-        return;
-    }
     if (lane < 18) {
         euler_to_rot(x + 3 + 3 * lane, &L.Rl[9 * lane]);
-        // the Euler axes in the parent's frame (oracle/trf_np.py: ik_jacobian): x, Rx y, Rx Ry z
-        const double a0 = x[3 + 3 * lane], a1 = x[4 + 3 * lane];
-        const double ca = cos(a0), sa = sin(a0), cb = cos(a1), sb = sin(a1);
-        double* A = &L.ax[9 * lane];
-        A[0] = 1.0; A[1] = 0.0; A[2] = 0.0;
-        A[3] = 0.0; A[4] = ca; A[5] = sa;
-        A[6] = sb; A[7] = -sa * cb; A[8] = ca * cb;
+        if constexpr (AXES) {   // the Euler axes in the parent's frame (oracle/trf_np.py: ik_jacobian): x, Rx y, Rx Ry z
+            const double a0 = x[3 + 3 * lane], a1 = x[4 + 3 * lane];
+            const double ca = cos(a0), sa = sin(a0), cb = cos(a1), sb = sin(a1);
+            double* A = &L.ax[9 * lane];
+            A[0] = 1.0; A[1] = 0.0; A[2] = 0.0;
+            A[3] = 0.0; A[4] = ca; A[5] = sa;
+            A[6] = sb; A[7] = -sa * cb; A[8] = ca * cb;
+        }
     }
     if (lane < 3) L.pos[lane] = x[lane];
     MVMC_WAVE_SYNC();
@@ -72,20 +59,86 @@ __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, co
         }
         MVMC_WAVE_SYNC();
     }
-    double axl[9];
-    if (lane < 18) {
+    if constexpr (AXES) {
+        double axl[9];
+        if (lane < 18) {
 #pragma unroll
-        for (int e = 0; e < 9; ++e) axl[e] = L.ax[9 * lane + e];
+            for (int e = 0; e < 9; ++e) axl[e] = L.ax[9 * lane + e];
+        }
+        MVMC_WAVE_SYNC();
+        if (lane < 18) {   // axes into the global frame: R_parent a (the root's parent frame is the world)
+            const int p = T.parents[lane];
+            for (int c = 0; c < 3; ++c)
+                for (int e = 0; e < 3; ++e)
+                    L.ax[9 * lane + 3 * c + e] = p < 0 ? axl[3 * c + e]
+                                                       : L.Rg[9 * p + 3 * e] * axl[3 * c] + L.Rg[9 * p + 3 * e + 1] * axl[3 * c + 1] +
+                                                             L.Rg[9 * p + 3 * e + 2] * axl[3 * c + 2];
+        }
+    }
+}
+
+// One (view, observed joint) pair: kp the view's pose (17,3), P its camera (3,4), obs the joint's row of it (17: the mid spine of the
+// shoulders and hips, its score their product), X the joint -> the observation (ob0, ob1), its score s, and the projection (u, vv)
+// with its depth w
+__device__ __forceinline__ void sm_pair(const double* __restrict__ kp, const double* __restrict__ P, int obs, double X0, double X1,
+                                        double X2, double& ob0, double& ob1, double& s, double& w, double& u, double& vv) {
+    if (obs < 17) { ob0 = kp[obs * 3]; ob1 = kp[obs * 3 + 1]; s = kp[obs * 3 + 2]; }
+    else {
+        const double sh0 = 0.5 * (kp[5 * 3] + kp[6 * 3]), hp0 = 0.5 * (kp[11 * 3] + kp[12 * 3]);
+        const double sh1 = 0.5 * (kp[5 * 3 + 1] + kp[6 * 3 + 1]), hp1 = 0.5 * (kp[11 * 3 + 1] + kp[12 * 3 + 1]);
+        ob0 = 0.5 * (sh0 + hp0); ob1 = 0.5 * (sh1 + hp1);
+        s = kp[5 * 3 + 2] * kp[6 * 3 + 2];
+        s *= kp[11 * 3 + 2] * kp[12 * 3 + 2];
+    }
+    const double h0 = P[0] * X0 + P[1] * X1 + P[2] * X2 + P[3];
+    const double h1 = P[4] * X0 + P[5] * X1 + P[6] * X2 + P[7];
+    const double h2 = P[8] * X0 + P[9] * X1 + P[10] * X2 + P[11];
+    w = 1e-5 + h2;
+    u = h0 / w;
+    vv = h1 / w;
+}
+
+// The robust loss on one (selected view, observed joint) pair (include/mvmc.h: MVMC_SMOOTH_LOSS_*; tests/smooth_robust_np.py): e2 the
+// squared length of the PLAIN pixel residual, delta = loss_px -> rho and the weight w of the reweighted model.  Huber's e = 0 is inside.
+template <int LOSS>
+__device__ __forceinline__ void sm_rho_w(double e2, double delta, double& rho, double& w) {
+    if constexpr (LOSS == MVMC_SMOOTH_LOSS_HUBER) {
+        const double e = sqrt(e2);
+        if (e <= delta) { rho = 0.5 * e2; w = 1.0; }
+        else { rho = delta * (e - 0.5 * delta); w = delta / e; }
+    } else if constexpr (LOSS == MVMC_SMOOTH_LOSS_CAUCHY) {
+        const double q = e2 / (delta * delta);
+        rho = 0.5 * delta * delta * log1p(q);
+        w = 1.0 / (1.0 + q);
+    } else {
+        rho = 0.5 * e2; w = 1.0;
+    }
+}
+
+// One row on the calling wave: members (C) pose indices or -1, Prig the row's rig (C,3,4), x the row's 68 parameters -> out (SM_BLK).
+// LOSS = MVMC_SMOOTH_LOSS_NONE is the arithmetic without a loss, operation for operation (loss_px is not read).  With a loss the pair's
+// rho and w are taken in registers inside the view loop: W_k and t_k carry w s^2, E = sum s^2 rho; the score stays outside the loss, and
+// a pair whose score is 0 contributes nothing whatever its residual.  The reductions and the LDS are the same for every LOSS.
+template <int LOSS>
+__device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, const double* __restrict__ kps17,
+                                             const double* __restrict__ Prig, int C, int Pmax, const int32_t* __restrict__ members,
+                                             const double* __restrict__ x, double* __restrict__ out, double loss_px) {
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) {
+        int n = 0;
+        for (int c = 0; c < C; ++c) {
+            const int m = members[c];
+            if (m >= 0 && n < MVMC_SMOOTH_MAX_VIEWS) { L.mq[n] = m; L.mc[n] = (m / Pmax) % C; ++n; }
+        }
+        L.nv = n;
     }
     MVMC_WAVE_SYNC();
-    if (lane < 18) {   // axes into the global frame: R_parent a (the root's parent frame is the world)
-        const int p = T.parents[lane];
-        for (int c = 0; c < 3; ++c)
-            for (int e = 0; e < 3; ++e)
-                L.ax[9 * lane + 3 * c + e] = p < 0 ? axl[3 * c + e]
-                                                   : L.Rg[9 * p + 3 * e] * axl[3 * c] + L.Rg[9 * p + 3 * e + 1] * axl[3 * c + 1] +
-                                                         L.Rg[9 * p + 3 * e + 2] * axl[3 * c + 2];
+    const int nv = uni(L.nv);
+    if (nv == 0) {   // no data: the prior alone places the frame
+        for (int i = lane; i < SM_BLK; i += 64) out[i] = 0.0;
+        return;
     }
+    sm_row_fk<true>(T, L, x);
     // residual and the per-joint blocks: lane (k, r) = observed joint k in the views r, r + 4, ... (as ik1_eval)
     const int k = lane & 15, r = lane >> 4;
     const double X0 = L.pos[3 * kIkSkel[k]], X1 = L.pos[3 * kIkSkel[k] + 1], X2 = L.pos[3 * kIkSkel[k] + 2];
@@ -94,39 +147,38 @@ __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, co
     for (int v = r; v < nv; v += 4) {
         const double* kp = kps17 + (size_t)L.mq[v] * 51;
         const double* P = Prig + (size_t)L.mc[v] * 12;
-        double ob0, ob1, s;
-        if (obs < 17) { ob0 = kp[obs * 3]; ob1 = kp[obs * 3 + 1]; s = kp[obs * 3 + 2]; }
-        else {
-            const double sh0 = 0.5 * (kp[5 * 3] + kp[6 * 3]), hp0 = 0.5 * (kp[11 * 3] + kp[12 * 3]);
-            const double sh1 = 0.5 * (kp[5 * 3 + 1] + kp[6 * 3 + 1]), hp1 = 0.5 * (kp[11 * 3 + 1] + kp[12 * 3 + 1]);
-            ob0 = 0.5 * (sh0 + hp0); ob1 = 0.5 * (sh1 + hp1);
-            s = kp[5 * 3 + 2] * kp[6 * 3 + 2];
-            s *= kp[11 * 3 + 2] * kp[12 * 3 + 2];
+        double ob0, ob1, s, w, u, vv;
+        sm_pair(kp, P, obs, X0, X1, X2, ob0, ob1, s, w, u, vv);
+        // the pair's terms: f2 += its cost, W_k += cw (du du^T + dv dv^T), t_k += ct (du gu + dv gv)
+        double cw, ct, gu, gv;
+        if constexpr (LOSS == MVMC_SMOOTH_LOSS_NONE) {
+            const double fu = (u - ob0) * s, fv = (vv - ob1) * s;
+            f2 += fu * fu + fv * fv;
+            cw = s * s; ct = s; gu = fu; gv = fv;
+        } else {
+            const double ru = u - ob0, rv = vv - ob1;
+            double rho, wl;
+            sm_rho_w<LOSS>(ru * ru + rv * rv, loss_px, rho, wl);
+            const bool live = s != 0.0;
+            f2 += live ? s * s * rho : 0.0;
+            cw = ct = live ? wl * (s * s) : 0.0; gu = ru; gv = rv;
         }
-        const double h0 = P[0] * X0 + P[1] * X1 + P[2] * X2 + P[3];
-        const double h1 = P[4] * X0 + P[5] * X1 + P[6] * X2 + P[7];
-        const double h2 = P[8] * X0 + P[9] * X1 + P[10] * X2 + P[11];
-        const double w = 1e-5 + h2;
-        const double u = h0 / w, vv = h1 / w;
-        const double fu = (u - ob0) * s, fv = (vv - ob1) * s;
-        f2 += fu * fu + fv * fv;
         double du[3], dv[3];
         for (int c = 0; c < 3; ++c) {
             du[c] = (P[c] - u * P[8 + c]) / w;
             dv[c] = (P[4 + c] - vv * P[8 + c]) / w;
         }
-        const double s2 = s * s;
-        o[0] += s2 * (du[0] * du[0] + dv[0] * dv[0]);
-        o[1] += s2 * (du[0] * du[1] + dv[0] * dv[1]);
-        o[2] += s2 * (du[0] * du[2] + dv[0] * dv[2]);
-        o[3] += s2 * (du[1] * du[1] + dv[1] * dv[1]);
-        o[4] += s2 * (du[1] * du[2] + dv[1] * dv[2]);
-        o[5] += s2 * (du[2] * du[2] + dv[2] * dv[2]);
-        o[6] += s * (du[0] * fu + dv[0] * fv);
-        o[7] += s * (du[1] * fu + dv[1] * fv);
-        o[8] += s * (du[2] * fu + dv[2] * fv);
+        o[0] += cw * (du[0] * du[0] + dv[0] * dv[0]);
+        o[1] += cw * (du[0] * du[1] + dv[0] * dv[1]);
+        o[2] += cw * (du[0] * du[2] + dv[0] * dv[2]);
+        o[3] += cw * (du[1] * du[1] + dv[1] * dv[1]);
+        o[4] += cw * (du[1] * du[2] + dv[1] * dv[2]);
+        o[5] += cw * (du[2] * du[2] + dv[2] * dv[2]);
+        o[6] += ct * (du[0] * gu + dv[0] * gv);
+        o[7] += ct * (du[1] * gu + dv[1] * gv);
+        o[8] += ct * (du[2] * gu + dv[2] * gv);
     }
-    const double E = 0.5 * wave_sum(f2);
+    const double E = LOSS == MVMC_SMOOTH_LOSS_NONE ? 0.5 * wave_sum(f2) : wave_sum(f2);   // 1/2 sum (s e)^2, or sum s^2 rho
 #pragma unroll
     for (int e = 0; e < 9; ++e) {
         o[e] += xor_lane<16>(o[e]);
@@ -219,6 +271,12 @@ __device__ __forceinline__ double sm_prior_grad(const double* __restrict__ x, in
         ga += (c == i ? -2.0 : 1.0) * acc;
     }
     return wv * gv + wa * ga;
+}
+
+// the (loss, loss_px) pair of the *_robust entries: a loss of the three, and with one a loss_px that is a finite number > 0
+inline bool sm_loss_ok(int loss, double loss_px) {
+    if (loss < MVMC_SMOOTH_LOSS_NONE || loss > MVMC_SMOOTH_LOSS_CAUCHY) return false;
+    return loss == MVMC_SMOOTH_LOSS_NONE || (loss_px > 0.0 && loss_px <= 1.7976931348623157e308);   // (NaN fails both)
 }
 
 inline bool sm_tables(const mvmcSkeleton* skel_host, Ik1Tables* T) {

@@ -8,6 +8,8 @@
 //   per trial, inside the launch: the row blocks of the free rows on the workgroup's four waves (mvmc_smooth_row.h), the accept /
 //           reject decision, one block-banded solve over the free rows (mvmc_smooth_sweep.h, the sweep the offline smoother runs too),
 //           the next trial point.
+// mvmc_smooth_window_robust: the same launch with the row blocks of the robust loss (mvmc_smooth_row.h: sm_row_block<LOSS>); the LDS
+// and the workspace are the same for every loss.
 // Every sum runs in a fixed order inside one identity's own lanes: an identity's numbers depend on nothing else in the launch.
 #define MVMC_DEVICE_ONLY
 #include "mvmc_common.h"
@@ -36,12 +38,13 @@ union SwLds {
 };
 static_assert(sizeof(SwLds) <= 160 * 1024, "LDS of one workgroup");
 
+template <int LOSS>
 __global__ void __launch_bounds__(SM_THREADS) smooth_window_kernel(
     Ik1Tables T, const double* __restrict__ kps17, const double* __restrict__ Pmats, int C, int Pmax, int n_rigs,
     const int32_t* __restrict__ items, const double* __restrict__ new_params, const int32_t* __restrict__ new_members, int n_new,
     double* __restrict__ rows, int32_t* __restrict__ members, int32_t* __restrict__ count, int n_slots, int W, int n_iter,
     double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* __restrict__ info,
-    double* __restrict__ work, int work_rows) {
+    double* __restrict__ work, int work_rows, double loss_px) {
     __shared__ SwLds LL;
     const int tid = threadIdx.x, wave = tid >> 6, it = blockIdx.x;
     const int32_t* im = items + (size_t)it * SW_ITEM;
@@ -100,8 +103,8 @@ __global__ void __launch_bounds__(SM_THREADS) smooth_window_kernel(
     auto eval_blocks = [&](const double* p, int b) {
         __syncthreads();   // (the LDS changes hands: sweep -> blocks; p is complete)
         for (int r = wave; r < m; r += 4)
-            sm_row_block(T, LL.blk[wave], kps17, Prig, C, Pmax, mring + (size_t)((lo + h + r) % SW_RING) * C, p + (size_t)(h + r) * 68,
-                         blocks_of(r, b));
+            sm_row_block<LOSS>(T, LL.blk[wave], kps17, Prig, C, Pmax, mring + (size_t)((lo + h + r) % SW_RING) * C,
+                               p + (size_t)(h + r) * 68, blocks_of(r, b), loss_px);
         __syncthreads();
     };
     eval_blocks(x, 0);
@@ -159,25 +162,40 @@ extern "C" long long mvmc_smooth_window_work_doubles(int n_items, int window) {
     return (long long)n_items * (SW_PER_ITEM + (long long)window * SW_PER_ROW);
 }
 
-extern "C" int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
-                                  int n_rigs, const int32_t* items, int n_items, const double* new_params, const int32_t* new_members,
-                                  int n_new, double* rows, int32_t* members, int32_t* count, int n_slots, int window, int n_iter,
-                                  double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol,
-                                  double* info, double* work, long long work_doubles, mvmcStream_t stream) {
+extern "C" int mvmc_smooth_window_robust(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                         int n_rigs, const int32_t* items, int n_items, const double* new_params,
+                                         const int32_t* new_members, int n_new, double* rows, int32_t* members, int32_t* count,
+                                         int n_slots, int window, int n_iter, double root_vel, double root_acc, double ang_vel,
+                                         double ang_acc, double mu0, double ftol, double xtol, double* info, double* work,
+                                         long long work_doubles, int loss, double loss_px, mvmcStream_t stream) {
     if (!skel_host || n_items < 0 || n_new < 0 || n_slots < 0 || n_rigs < 1 || n_views <= 0 || n_views > MVMC_SMOOTH_MAX_VIEWS ||
         p_max <= 0)
         return MVMC_ERR_ARG;
     if (window < 2 || window > SW_MAXW || n_iter < 1 || n_iter > SW_INFO - 8) return MVMC_ERR_ARG;
     if (!(root_vel >= 0.0) || !(root_acc >= 0.0) || !(ang_vel >= 0.0) || !(ang_acc >= 0.0) || !(mu0 > 0.0)) return MVMC_ERR_ARG;
+    if (!sm_loss_ok(loss, loss_px)) return MVMC_ERR_ARG;
     if (n_items == 0) return MVMC_OK;
     if (!kps17 || !Pmats || !items || !rows || !members || !count || !info || !work || (n_new > 0 && (!new_params || !new_members)))
         return MVMC_ERR_ARG;
     if (work_doubles < mvmc_smooth_window_work_doubles(n_items, window)) return MVMC_ERR_ARG;
     Ik1Tables T;
     if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(smooth_window_kernel, dim3(n_items), dim3(SM_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max,
-                       n_rigs, items, new_params, new_members, n_new, rows, members, count, n_slots, window, n_iter, root_vel, root_acc,
-                       ang_vel, ang_acc, mu0, ftol, xtol, info, work, n_items * window);
+    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_window_kernel<MVMC_SMOOTH_LOSS_HUBER>
+                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_window_kernel<MVMC_SMOOTH_LOSS_CAUCHY>
+                                                    : smooth_window_kernel<MVMC_SMOOTH_LOSS_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(n_items), dim3(SM_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, n_rigs, items,
+                       new_params, new_members, n_new, rows, members, count, n_slots, window, n_iter, root_vel, root_acc, ang_vel,
+                       ang_acc, mu0, ftol, xtol, info, work, n_items * window, loss_px);
     MVMC_CHECK_LAUNCH();
     return MVMC_OK;
+}
+
+extern "C" int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                  int n_rigs, const int32_t* items, int n_items, const double* new_params, const int32_t* new_members,
+                                  int n_new, double* rows, int32_t* members, int32_t* count, int n_slots, int window, int n_iter,
+                                  double root_vel, double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol,
+                                  double* info, double* work, long long work_doubles, mvmcStream_t stream) {
+    return mvmc_smooth_window_robust(skel_host, kps17, n_views, p_max, Pmats, n_rigs, items, n_items, new_params, new_members, n_new, rows,
+                                     members, count, n_slots, window, n_iter, root_vel, root_acc, ang_vel, ang_acc, mu0, ftol, xtol, info,
+                                     work, work_doubles, MVMC_SMOOTH_LOSS_NONE, 0.0, stream);
 }

@@ -422,9 +422,24 @@ def body_lengths(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor,
                                          float(xtol), _p(info), _p(work), _stream()), "mvmc_body_lengths")
     return info
 
+def smooth_loss_args(loss, loss_px, what: str):
+    """loss (None, "huber", "cauchy") and loss_px -> the (int, double) pair of the *_robust entries (include/mvmc.h: MVMC_SMOOTH_LOSS_*)."""
+    codes = {None: _cabi.SMOOTH_LOSS_NONE, "huber": _cabi.SMOOTH_LOSS_HUBER, "cauchy": _cabi.SMOOTH_LOSS_CAUCHY}
+    if not (loss is None or isinstance(loss, str)) or loss not in codes:
+        raise ValueError(f"{what}: loss must be None, \"huber\" or \"cauchy\", got {loss!r}")
+    if loss is None:
+        return codes[loss], 0.0      # (not read)
+    if loss_px is None:
+        raise ValueError(f"{what}: loss {loss!r} needs a loss_px")
+    return codes[loss], float(loss_px)
+
+
 def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,
-                  id_of: torch.Tensor, ctl: torch.Tensor, blk: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None) -> None:
-    """The data blocks of the trajectory smoother at x (include/mvmc.h: mvmc_smooth_blocks), one wave per row, into blk (2,N,820)."""
+                  id_of: torch.Tensor, ctl: torch.Tensor, blk: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None, *,
+                  loss: Optional[str] = None, loss_px: Optional[float] = None) -> None:
+    """The data blocks of the trajectory smoother at x (include/mvmc.h: mvmc_smooth_blocks), one wave per row, into blk (2,N,820).
+    loss "huber" / "cauchy" with loss_px > 0 (pixels): the blocks of the reweighted model, J^T W J, J^T W r and sum s^2 rho
+    (mvmc_smooth_blocks_robust); loss=None is the plain entry."""
     sk = skeleton if skeleton is not None else make_skeleton()
     F, Cn, P = kps17.shape[:3]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -436,8 +451,32 @@ def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor
     _req(members, torch.int32, "members", (N, Cn))
     _req(ctl, torch.int32, "ctl", (None, 4))
     _req(blk, torch.float64, "blk", (2, N, _cabi.SMOOTH_BLOCK_DOUBLES))
-    check(_cabi.load().mvmc_smooth_blocks(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of), _p(ctl),
-                                          N, _p(blk), _stream()), "mvmc_smooth_blocks")
+    if loss is None:
+        check(_cabi.load().mvmc_smooth_blocks(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of), _p(ctl),
+                                              N, _p(blk), _stream()), "mvmc_smooth_blocks")
+        return
+    code, px = smooth_loss_args(loss, loss_px, "smooth_blocks")
+    check(_cabi.load().mvmc_smooth_blocks_robust(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
+                                                 _p(ctl), N, _p(blk), code, px, _stream()), "mvmc_smooth_blocks_robust")
+
+
+def smooth_obs_weights(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,
+                       loss: Optional[str], loss_px: Optional[float], skeleton: Optional[MvmcSkeleton] = None) -> torch.Tensor:
+    """The loss's weight of every (camera, observed joint) pair of every row at x (include/mvmc.h: mvmc_smooth_obs_weights), one wave
+    per row -> w (N,C,16) f64: NaN where the camera has no member in the row or the pair's score is 0; loss=None gives 1 elsewhere."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    N = x.shape[0]
+    _req(x, torch.float64, "x", (N, 68))
+    _req(rig_of, torch.int32, "rig_of", (N,))
+    _req(members, torch.int32, "members", (N, Cn))
+    code, px = smooth_loss_args(loss, loss_px, "smooth_obs_weights")
+    w = torch.empty((N, Cn, 16), dtype=torch.float64, device=x.device)
+    check(_cabi.load().mvmc_smooth_obs_weights(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), N, code, px,
+                                               _p(w), _stream()), "mvmc_smooth_obs_weights")
+    return w
 
 
 def smooth_step(x: torch.Tensor, x_trial: torch.Tensor, blk: torch.Tensor, id_lo: torch.Tensor, weights, mu0: float, ftol: float,
@@ -499,10 +538,12 @@ def smooth_window_work(n_items: int, window: int, dev) -> torch.Tensor:
 
 def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, new_params: torch.Tensor, new_members: torch.Tensor,
                   rows: torch.Tensor, members: torch.Tensor, count: torch.Tensor, window: int, n_iter: int, weights, mu0: float,
-                  ftol: float, xtol: float, skeleton: Optional[MvmcSkeleton] = None) -> torch.Tensor:
+                  ftol: float, xtol: float, skeleton: Optional[MvmcSkeleton] = None, *, loss: Optional[str] = None,
+                  loss_px: Optional[float] = None) -> torch.Tensor:
     """One tick of the live smoother for every item (include/mvmc.h: mvmc_smooth_window), one launch.  kps17 (F,C,P,17,3) the
     sessions' keypoint ring; Pmats (R,C,3,4); items (n,8) i32; new_params (B,68), new_members (B,C) the tick's data rows; rows
-    (n_slots,66,68), members (n_slots,66,C), count (n_slots,2) the identities' device state, updated in place.  -> info (n,16)."""
+    (n_slots,66,68), members (n_slots,66,C), count (n_slots,2) the identities' device state, updated in place.  -> info (n,16).
+    loss "huber" / "cauchy" with loss_px > 0: the same launch on the robust data term (mvmc_smooth_window_robust)."""
     sk = skeleton if skeleton is not None else make_skeleton()
     F, Cn, P = kps17.shape[:3]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -519,10 +560,17 @@ def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor,
     rv, ra, av, aa = (float(w) for w in weights)
     info = torch.empty((n, _cabi.SMOOTH_WIN_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
     work = smooth_window_work(n, window, rows.device)
-    check(_cabi.load().mvmc_smooth_window(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(new_params),
-                                          _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window), int(n_iter), rv, ra,
-                                          av, aa, float(mu0), float(ftol), float(xtol), _p(info), _p(work), int(work.numel()), _stream()),
-          "mvmc_smooth_window")
+    if loss is None:
+        check(_cabi.load().mvmc_smooth_window(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(new_params),
+                                              _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window), int(n_iter), rv, ra,
+                                              av, aa, float(mu0), float(ftol), float(xtol), _p(info), _p(work), int(work.numel()), _stream()),
+              "mvmc_smooth_window")
+        return info
+    code, px = smooth_loss_args(loss, loss_px, "smooth_window")
+    check(_cabi.load().mvmc_smooth_window_robust(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n,
+                                                 _p(new_params), _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window),
+                                                 int(n_iter), rv, ra, av, aa, float(mu0), float(ftol), float(xtol), _p(info), _p(work),
+                                                 int(work.numel()), code, px, _stream()), "mvmc_smooth_window_robust")
     return info
 
 

@@ -19,6 +19,11 @@ The rows, their members, the row counts and the sessions' rings of the last ``wi
 between ticks.  A tick costs a number of launches that does not depend on sessions or identities (ingest, selection, exactly one
 mvmc_smooth_window, FK of the rows read back) and one synchronisation, the read-back.  NumPy restatement: tests/live_smooth_np.py.
 INTEGRATION.md section C.5.
+
+loss="huber" / "cauchy" at loss_px pixels puts smoothing.py's robust loss on the window's data terms: the tick's one launch is then
+mvmc_smooth_window_robust (the same state, workspace and outputs; ``solved``'s cost holds the robust E_data).  loss=None is the plain
+launch, bit for bit.  The live path sets no weights attribute: which keypoints were voted down is the offline smoother's
+``smooth_obs_weight``.
 """
 from __future__ import annotations
 
@@ -29,7 +34,7 @@ import numpy as np
 
 from .body_fit import MAX_DIST, MIN_SCORE
 from .sequences import frame_buckets, new_record, pose_slot, pose_tuples
-from .smoothing import ANG_ACC, ANG_VEL, LM_FTOL, LM_MU0, LM_XTOL, ROOT_ACC, ROOT_VEL, unwrap_euler_many
+from .smoothing import ANG_ACC, ANG_VEL, LM_FTOL, LM_MU0, LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, check_loss, unwrap_euler_many
 from .tracker import T_WIDE
 
 WINDOW_MAX = 32     # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
@@ -104,8 +109,10 @@ class LiveSmoother:
 
     def __init__(self, n_views: int, capacity: int, p_max: int = 8, window: int = 24, lag: int = 8, n_iter: int = 2,
                  root_vel: float = ROOT_VEL, root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC,
-                 device=None, skeleton=None):
+                 device=None, skeleton=None, loss: Optional[str] = None, loss_px: float = LOSS_PX):
         self.w = check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc)
+        loss_px = check_loss("LiveSmoother", loss, loss_px)
+        self._rob = dict(loss=loss, loss_px=loss_px) if loss is not None else {}     # loss=None: the launch without the arguments
         if int(capacity) < 1 or not 1 <= int(n_views) <= MAX_VIEWS or int(p_max) < 1:
             raise ValueError(f"LiveSmoother: capacity >= 1, 1 <= n_views <= {MAX_VIEWS} and p_max >= 1 required")
         self.C, self.P, self.capacity = int(n_views), int(p_max), int(capacity)
@@ -327,7 +334,7 @@ class LiveSmoother:
         parts = []
         if items:
             info = dev.smooth_window(st["kps"], st["Pm"], T(np.array(items, np.int32)), newp_d, mem_d, st["rows"], st["members"],
-                                     st["count"], W, self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton)
+                                     st["count"], W, self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton, **self._rob)
             parts.append(info.reshape(-1))
         Pg = [p for p in (P_fin, st["rows"].view(-1, 68).index_select(0, slot_idx(want)) if want else None) if p is not None]
         n_rows = len(want_fin) + len(want)

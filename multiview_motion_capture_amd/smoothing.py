@@ -20,8 +20,17 @@ nearest earlier record frame's.  The solve is Levenberg-Marquardt, (A + mu diag 
 the exact prior Hessian, factored exactly by a block-banded Cholesky; mu starts at LM_MU0, / 10 after an accepted trial, x 10 after a
 rejected one; stop on max_iter, LM_XTOL or LM_FTOL, as the body fit's length step.
 
-Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; selection: mvmc_body_observe), the optional
-per-frame covariance csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov); NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py.
+loss="huber" / "cauchy" (default None: the quadratic data term above) puts a robust loss on every (selected view, observed joint)
+pair: with the pair's score s, its plain pixel residual of length e and delta = loss_px, the data term is sum s^2 rho(e^2), Huber
+rho = 1/2 e^2 for e <= delta and delta (e - 1/2 delta) beyond, Cauchy rho = 1/2 delta^2 log1p(e^2 / delta^2) (rig_refine's two
+losses; the score stays outside, so loss_px is in pixels whatever the detector's confidence).  Every linearisation multiplies the
+pair's Jacobian rows and residual by sqrt(w), w = 1 or delta / e (Huber), 1 / (1 + e^2 / delta^2) (Cauchy): iteratively reweighted
+least squares without a second-order term; the Levenberg-Marquardt rules, the sweep and the prior are untouched, and the view gate of
+the selection still comes first.  It is for the keypoint the gate cannot see: one limb exchanged, one joint put on the neighbour.
+
+Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; with a loss mvmc_smooth_blocks_robust and
+mvmc_smooth_obs_weights; selection: mvmc_body_observe), the optional per-frame covariance csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov);
+NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py, tests/smooth_robust_np.py.
 Sequences with the same number of cameras share every launch, each with its own rig.
 """
 from __future__ import annotations
@@ -42,12 +51,15 @@ ANG_VEL, ANG_ACC = 1e4, 1e4      # px^2 / rad^2
 LM_MU0 = 1e-3       # Marquardt's damping: (A + mu diag(A)) d = -g, mu dimensionless
 LM_FTOL = 1e-12     # stop: predicted or achieved reduction below LM_FTOL E
 LM_XTOL = 1e-10     # stop: |d|_inf below LM_XTOL (m / rad)
+LOSS_PX = 6.0       # the robust loss's scale in pixels, rig_refine's default: three times a 2 px detector noise
+LOSSES = (None, "huber", "cauchy")
 COV_MU = 1e-8       # covariance="joints" inverts A + COV_MU diag A: A alone is singular (the knees' Rz angles move no joint)
 MAX_ITER_CAP = 24   # include/mvmc.h: MVMC_SMOOTH_INFO_DOUBLES - 8
 MAX_VIEWS = 64      # include/mvmc.h: MVMC_SMOOTH_MAX_VIEWS
 MAX_WORK_BYTES = 1 << 30
 _BLOCK, _WORK = 820, 3940   # include/mvmc.h: doubles per row
 _JOINTS, _K, _COV_INFO = 18, 39, 8   # include/mvmc.h: skeleton joints, MVMC_SMOOTH_K, MVMC_SMOOTH_COV_INFO_DOUBLES
+_OBS = 16                            # observed joints of a view (the IK's observation rows): mvmc_smooth_obs_weights' last axis
 
 
 def stage1_columns() -> np.ndarray:
@@ -147,6 +159,16 @@ def _check_covariance(covariance, noise_px):
     return float(noise_px)
 
 
+def check_loss(who: str, loss, loss_px) -> float:
+    """The robust-loss arguments of smooth_sequences and LiveSmoother (host only) -> loss_px as a float."""
+    if not (loss is None or isinstance(loss, str)) or loss not in LOSSES:
+        raise ValueError(f"{who}: loss must be None, \"huber\" or \"cauchy\", got {loss!r}")
+    if isinstance(loss_px, (str, bytes, bool)) or not isinstance(loss_px, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(loss_px) or not loss_px > 0:
+        raise ValueError(f"{who}: loss_px must be a finite number > 0, got {loss_px!r}")
+    return float(loss_px)
+
+
 def _check(sequences, tracklets_per_sequence):
     return check_records(sequences, tracklets_per_sequence, "smooth_sequences", increasing=True, finite=True,
                          cameras=(1, MAX_VIEWS, f"sequence {{s}}: {{C}} cameras, at most {MAX_VIEWS}"))
@@ -155,7 +177,8 @@ def _check(sequences, tracklets_per_sequence):
 def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], root_vel: float = ROOT_VEL,
                      root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
                      fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0",
-                     timings: Optional[dict] = None, covariance: Optional[str] = None, noise_px: Optional[float] = None) -> List[list]:
+                     timings: Optional[dict] = None, covariance: Optional[str] = None, noise_px: Optional[float] = None,
+                     loss: Optional[str] = None, loss_px: float = LOSS_PX) -> List[list]:
     """Smooth every identity of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows
     track_sequences and fit_sequences take -- from its MvTracklet records (fit_sequences, track_sequences, run_main_batched,
     MvTracker.update_4d, LivePool).  Returns, per sequence, NEW records in the input order (the inputs are not touched): the same
@@ -178,10 +201,22 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     m = sqrt(trace); ``smooth_param_sigma`` (n,39) m / rad in stage1_columns() order; ``smooth_edof`` = tr(A^-1 J^T J), ``smooth_nres``
     the residuals with a non-zero score, ``smooth_cov_status`` 0 solved, 1 A is singular (NaN arrays), 2 a record of fewer than two
     frames (NaN arrays).  The prior is a regulariser with swept weights, not a fitted motion model: the calibration of these numbers is
-    measured, not promised."""
+    measured, not promised.
+    loss="huber" / "cauchy" at loss_px pixels (default None: nothing below is computed or set, the launches and the bits are those of
+    a call without the argument): the robust data term of the module's docstring.  Every blocks launch of the solve and of the
+    covariance is the robust one; ``smooth_cost`` holds the robust E_data = sum s^2 rho; after the solve one more launch per partition
+    (mvmc_smooth_obs_weights) takes the weights at the returned trajectory, and every record gets ``smooth_obs_weight`` (n, C, 16),
+    rows as ``poses``: the weight of camera c and observed joint k (the IK's observation order: COCO's 16 joints without the nose,
+    then the mid spine), NaN where the camera has no selected pose in the row or the keypoint's score is 0 -- filled rows and
+    one-frame records are all NaN.  It tells which keypoints of which camera were voted down.  timings gets a "weights" part.
+    With covariance="joints" the launch inverts J^T W J + the prior at the final weights, and smooth_edof and smooth_nres are defined
+    as above on the weighted blocks; the ESTIMATED smooth_noise_px is then biased low, because rho <= 1/2 e^2 shrinks E_data while
+    smooth_nres still counts every residual: under a loss noise_px= is the honest choice."""
     t_start = time.perf_counter()
     w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
     noise_px = _check_covariance(covariance, noise_px)
+    loss_px = check_loss("smooth_sequences", loss, loss_px)
+    rob = dict(loss=loss, loss_px=loss_px) if loss is not None else {}     # loss=None: the calls without the arguments
     if no_sequences(sequences, tracklets_per_sequence, "smooth_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence)
@@ -190,7 +225,8 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     from . import device as dev
     d = torch.device(device)
     T = dev.uploader(d)
-    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records") + (("covariance",) if covariance else ()))
+    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records") + (("covariance",) if covariance else ())
+                        + (("weights",) if loss is not None else ()))
     tm["prepare"] = time.perf_counter() - t_start
     out: List[list] = [[None] * len(r) for r in recs]
     per_row = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
@@ -222,8 +258,8 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
             nvf[rows] = nv_h[rec_lo[a]:rec_lo[a + 1]]
             traj.append((a, x0, filled, mem, nvf, int(sel.rig_of[rec_lo[a]])))
         t0 = lap("prepare", t0)
-        res = {}
-        cap = max(1, int(max_work_bytes) // per_row)
+        res, obs_w = {}, {}
+        cap = max(1, int(max_work_bytes) // (per_row + (8 * _OBS * C if loss is not None else 0)))   # (the weights: (C, 16) per row)
         at = 0
         while at < len(traj):
             b = at + 1
@@ -251,7 +287,7 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
             id_of_d, id_lo_d = T(id_of), T(id_lo)
             t0 = lap("prepare", t0)
             for phase in range(int(max_iter) + 1):
-                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x if phase == 0 else xt, id_of_d, ctl, blk)
+                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x if phase == 0 else xt, id_of_d, ctl, blk, **rob)
                 t0 = lap("blocks", t0)
                 dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info, work)
                 t0 = lap("solve", t0)
@@ -264,20 +300,28 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 jcov = torch.empty((N, _JOINTS, 6), dtype=torch.float64, device=d)
                 pvar = torch.empty((N, _K), dtype=torch.float64, device=d)
                 cinfo = torch.empty((len(part), _COV_INFO), dtype=torch.float64, device=d)
-                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x, id_of_d, ctl_x, blk)
+                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x, id_of_d, ctl_x, blk, **rob)
                 dev.smooth_cov(x, blk[0], id_lo_d, w, COV_MU, k17, Pm_d, rig_d, mem_d, work, jcov, pvar, cinfo)
                 t0 = lap("covariance", t0)
                 cov = (jcov.cpu().numpy(), pvar.cpu().numpy(), cinfo.cpu().numpy())
+            if loss is not None:
+                wts = dev.smooth_obs_weights(k17, Pm_d, rig_d, mem_d, x, loss, loss_px)
+                t0 = lap("weights", t0)
+                wts_h = wts.cpu().numpy()
             jn = dev.fk(x).cpu().numpy()
             xs, inf = x.cpu().numpy(), info.cpu().numpy()
             for s, p in enumerate(part):
                 sl = slice(id_lo[s], id_lo[s + 1])
                 res[p[0]] = (xs[sl], jn[sl], inf[s]) + ((cov[0][sl], cov[1][sl], cov[2][s]) if cov else ())
+                if loss is not None:
+                    obs_w[p[0]] = wts_h[sl]
             lap("records", t0)
         t0 = time.perf_counter()
         _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, sel.Pg)
         if covariance:
             _covariance_fields(out, items, traj, res, fill_gaps, noise_px)
+        if loss is not None:
+            _weight_fields(out, items, traj, obs_w, fill_gaps, C)
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
@@ -344,11 +388,24 @@ def _covariance_fields(out, items, traj, res, fill_gaps, noise_px):
         t.smooth_cov_status = status
 
 
+def _weight_fields(out, items, traj, obs_w, fill_gaps, C):
+    """smooth_obs_weight (n, C, 16) of the group's records, rows as poses; a one-frame record has nothing solved: NaN."""
+    tr = {p[0]: p for p in traj}
+    for a, (i, j) in enumerate(items):
+        if a in tr:
+            filled = tr[a][2]
+            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
+            out[i][j].smooth_obs_weight = obs_w[a][idx].copy()
+        else:
+            out[i][j].smooth_obs_weight = np.full((1, C, _OBS), np.nan)
+
+
 def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, root_vel: float = ROOT_VEL,
                      root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
                      fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0", timings: Optional[dict] = None,
-                     covariance: Optional[str] = None, noise_px: Optional[float] = None) -> list:
+                     covariance: Optional[str] = None, noise_px: Optional[float] = None, loss: Optional[str] = None,
+                     loss_px: float = LOSS_PX) -> list:
     """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records."""
     return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel, ang_acc=ang_acc,
                             max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings,
-                            covariance=covariance, noise_px=noise_px)[0]
+                            covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px)[0]
