@@ -303,6 +303,29 @@ int mvmc_debug_eigh(const double* A, const double* g, int n_problems, int n, dou
 int mvmc_debug_trstep(const double* B, const double* r, int n_problems, int m, int n, double Delta, double alpha0,
                       double* step, double* out4, double* phase_cycles, mvmcStream_t stream);
 
+/* The forms of the temporal layer that only the chain kernels run, on caller-supplied data (tests/test_gpu_track_kernels.py compares
+ * them with mvmc_st_affinity / mvmc_track_assign / mvmc_track_commit bit for bit).
+ * mvmc_debug_st_affinity_wg: arguments and results of mvmc_st_affinity; one workgroup of nt_threads (256 or 512) per chain runs the
+ *   graph builder with the 2-D / 2-D block taken from pair_form: 0 = computed in place (as mvmc_st_affinity does on one wave),
+ *   1 = made ahead by one thread per ordered pose pair from the keypoints in global memory (the chain kernel's small layout),
+ *   2 = made ahead by per-view-pair line tables from keypoints staged in LDS (its big layout).  MVMC_ERR_UNSUPPORTED where
+ *   t_max + n_views p_max > MVMC_MAX_NODES or the workgroup would need more than 160 KB of LDS.
+ * mvmc_debug_track_wave: one 64-lane wave per chain.  phase 0 = mvmc_track_assign's arguments and results by the ballot form of the
+ *   assignment (n_members (B, t_max + k_max) i32 or NULL: with it the member count of every problem slot is written there and rows of
+ *   `members` are valid in [0, count) only, no -1 padding); phase 1 = mvmc_track_commit's by the multi-lane commit.  Pointers that
+ *   the phase does not use may be NULL.  MVMC_ERR_UNSUPPORTED where t_max > 16, n_views > 16 or n_views p_max > 64 (the chain
+ *   layouts' bounds, which the ballot words assume). */
+int mvmc_debug_st_affinity_wg(const double* kps17, const int32_t* counts, const int32_t* frame_idx, const double* track_joints,
+                              const int32_t* n_tracks, const double* Pmats, const double* F2, int n_chains, int n_views, int p_max,
+                              int t_max, double min_score, int nt_threads, int pair_form, double* W, double* D,
+                              int32_t* group_counts, mvmcStream_t stream);
+int mvmc_debug_track_wave(int phase, const int32_t* labels_sp, const int32_t* ncl_sp, const int32_t* labels_st,
+                          const int32_t* ncl_st, const int32_t* counts, const int32_t* frame_idx, int32_t* n_tracks,
+                          double* track_params, int n_chains, int n_views, int p_max, int t_max, int k_max, int v_max,
+                          int32_t* members, int32_t* n_members, uint8_t* cold, double* init_params, int32_t* status, int32_t* n_new,
+                          const double* ik_params, const double* ik_joints, int n_inits, double* track_joints, int32_t* meta,
+                          int32_t* next_id, int32_t* n_dead, int32_t* slot_src, int32_t* overflow, mvmcStream_t stream);
+
 /* ONE trust-region model and ONE trial step of the production IK solver from a caller-given iterate -- the unit in which the
  * reference's recorded iterates are compared (tests/golden/ik_trf_traces.npz: x_k, Delta_k, alpha_k of SciPy's trf_no_bounds,
  * trf.py:466-500, as called from inverse_kinematics.py:236,274).  The device functions are the solver's own.

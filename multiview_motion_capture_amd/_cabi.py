@@ -48,6 +48,7 @@ SYMBOLS = (
     "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
     "mvmc_lens_undistort", "mvmc_lens_distort",
     "mvmc_pair_moments", "mvmc_pair_consensus", "mvmc_pair_refit",
+    "mvmc_debug_st_affinity_wg", "mvmc_debug_track_wave",
 )
 
 
@@ -137,6 +138,8 @@ def load():
         "mvmc_track_assign": [vp] * 8 + [i32] * 6 + [vp] * 7,
         "mvmc_track_commit": [vp] * 4 + [i32] * 4 + [vp] * 9,
         "mvmc_debug_eigh": [vp, vp, i32, i32, vp, vp, vp, vp, vp],
+        "mvmc_debug_st_affinity_wg": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f64, i32, i32, vp, vp, vp, vp],
+        "mvmc_debug_track_wave": [i32] + [vp] * 8 + [i32] * 6 + [vp] * 8 + [i32] + [vp] * 7,
         "mvmc_debug_trstep": [vp, vp, i32, i32, i32, f64, f64, vp, vp, vp, vp],
         "mvmc_chain_run": [SK, C.POINTER(MvmcChainBuffers), vp],
         "mvmc_chain_run_rigs": [SK, C.POINTER(MvmcChainBuffers), vp, i32, vp],

@@ -162,7 +162,7 @@ template <> union ChainArena<true> {
     AlsGenLds<80, 32, 512> als_wide;   // graphs beyond als5 (a ninth tracklet and more: rank 18 .. 32, n <= 80)
     struct { Ik1Shared ik[8]; int mq[64]; unsigned short mc[64]; } ikp;   // eight waves: the eight people of config 5 are solved side by side
     // affinity_wave at N = 64: 64 * 51 + 64 * 64 + 64 + 16 = 7440; st_affinity_wave at NS = 80: 80 * 80 + 6 + 80, + the frame's keypoints
-    // + the pose-pair block; the line tables of st_pose_pairs_lines (2 * 4 * P * 68 doubles) use st_affinity_wave's part
+    // + the pose-pair block; the line tables of st_pose_pairs_lines (2 * 4 * P * 85 doubles) use st_affinity_wave's part
     double graph[CH_EOFF_BIG + 64 * 64];
 };
 static_assert(CH_EOFF >= 48 * 48 + 10 + 48 && CH_EOFF + 40 * 40 >= 40 * 51 + 40 * 40 + 40 + 8, "graph scratch covers both graph builders");
@@ -204,7 +204,7 @@ __device__ __noinline__ void chain_graph_temporal(ChainArena<BIG>& arena_in, Cha
         kf = arena.graph + CH_KOFF_BIG;
         st_stage_keypoints(kf, A.kps17, f, C, P);
         __syncthreads();
-        if (2 * 4 * P * 68 <= CH_KOFF_BIG && C * P <= 64) {       // the pair errors by line tables (config 5: P = 8)
+        if (2 * 4 * P * 85 <= CH_KOFF_BIG && C * P <= 64) {       // the pair errors by line tables (config 5: P = 8)
             st_pose_pairs_lines<ChainCfg<BIG>::NT>(arena.graph + CH_EOFF_BIG, arena.graph, kf, A.counts, f, F2, C, P, 0.1);
             Epre = arena.graph + CH_EOFF_BIG;
         }

@@ -37,20 +37,30 @@ __global__ void fmats_p_kernel(const double* __restrict__ Pm, int C, double* __r
             F2[idx * 9 + i * 3 + j] = det4(P1 + rp[j][0] * 4, P1 + rp[j][1] * 4, P2 + rp[i][0] * 4, P2 + rp[i][1] * 4);
 }
 
-// The epipolar line of a point under F (transposed = false: l = F x, the line in the other image) or under F^T, scaled as
-// calc_epipolar_error scales it (by 1 / sqrt(a^2 + b^2) unless that is zero), and the norm of the SCALED (a, b) the distance divides by.
-// Shared by epipolar_error and the line tables of st_pose_pairs_lines, so that both form the same expressions.
-__device__ __forceinline__ void epi_line(const double* F, double x, double y, bool transposed, double& a, double& b, double& c, double& nrm) {
-    if (!transposed) { a = F[0] * x + F[1] * y + F[2]; b = F[3] * x + F[4] * y + F[5]; c = F[6] * x + F[7] * y + F[8]; }
-    else             { a = F[0] * x + F[3] * y + F[6]; b = F[1] * x + F[4] * y + F[7]; c = F[2] * x + F[5] * y + F[8]; }
-    const double nu = a * a + b * b, sc = nu != 0.0 ? 1.0 / sqrt(nu) : 1.0;
-    a *= sc; b *= sc; c *= sc;
-    nrm = sqrt(a * a + b * b);
+// The epipolar line of a point under F (transposed = false: l = F x, the line in the other image) or under F^T, as calc_epipolar_error
+// scales it (by sc = 1 / sqrt(a^2 + b^2) unless that is zero): a, b SCALED, c0 and sc apart, and nrm = the norm of the scaled (a, b) the
+// distance divides by.  For the line tables of st_pose_pairs_lines, which must give epipolar_error's bits: written out operation by
+// operation (every fused multiply-add is an fma() here, every other product and sum is rounded on its own) as epipolar_error below
+// compiles.  Left to the compiler's contraction, the scaled c was fused into the distance's sum where it lives in a register
+// (epipolar_error: fma(c0, sc, ...)) and rounded where it went through a table, and the two forms of one pair's error were 1 ulp apart
+// on a few per cent of the pairs (tests/test_gpu_track_kernels.py compares them bit for bit).
+__device__ __forceinline__ double epi_lin(double fx, double fy, double f1, double x, double y) { return f1 + fma(x, fx, y * fy); }
+__device__ __forceinline__ void epi_line(const double* F, double x, double y, bool transposed, double& a, double& b, double& c0, double& sc,
+                                         double& nrm) {
+    double a0, b0;
+    if (!transposed) { a0 = epi_lin(F[0], F[1], F[2], x, y); b0 = epi_lin(F[3], F[4], F[5], x, y); c0 = epi_lin(F[6], F[7], F[8], x, y); }
+    else             { a0 = epi_lin(F[0], F[3], F[6], x, y); b0 = epi_lin(F[1], F[4], F[7], x, y); c0 = epi_lin(F[2], F[5], F[8], x, y); }
+    const double nu = fma(a0, a0, b0 * b0);
+    sc = nu != 0.0 ? 1.0 / sqrt(nu) : 1.0;
+    a = a0 * sc; b = b0 * sc;
+    nrm = sqrt(fma(a, a, b * b));
 }
-__device__ __forceinline__ double epi_dist(double a, double b, double c, double nrm, double x, double y) { return fabs(a * x + b * y + c) / nrm; }
+__device__ __forceinline__ double epi_dist(double a, double b, double c0, double sc, double nrm, double x, double y) {
+    return fabs(fma(c0, sc, fma(x, a, y * b))) / nrm;
+}
 
-// mean over valid joints of the symmetric point-to-epiline distance; NaN if none is valid (epi_line / epi_dist above are these
-// expressions, factored out for the line tables; tests/test_gpu_config5_c8p8.py compares the two forms bit for bit)
+// mean over valid joints of the symmetric point-to-epiline distance; NaN if none is valid.  (Left as plain expressions: what the
+// compiler makes of them is what epi_line / epi_dist above spell out, and tests/test_gpu_track_kernels.py holds the two together.)
 __device__ __noinline__ double epipolar_error(const double* F, const double* k1, const double* k2, double min_score) {
     double total = 0.0;
     int cnt = 0;
@@ -127,9 +137,10 @@ __device__ __forceinline__ void st_pose_pairs(double* E, const double* __restric
 // fit st_affinity_wave's part of the scratch, which is idle until the block is complete): four tables -- poses of u under F_uv, poses
 // of v under F_uv^T, poses of v under F_vu, poses of u under F_vu^T (the two fundamental matrices are made independently, so (i, j) and
 // (j, i) are different numbers, as in the reference, motion_capture.py:672-700) -- then one thread per ordered pair sums the joints in
-// order with one division per line where epipolar_error does two square roots and two divisions: the same expressions on the same
+// order with one division per line where epipolar_error does two square roots and two divisions: the same operations on the same
 // operands (epi_line / epi_dist), bit for bit, in a third of the square roots and divisions.
-// Ls: 2 * 4 * P * 68 doubles of LDS; kf: the frame's keypoints in LDS; every thread of the workgroup calls; ends synchronised.
+// Ls: 2 * 4 * P * 85 doubles of LDS (17 joints x {a, b, c0, sc, nrm} per pose and table); kf: the frame's keypoints in LDS; every thread
+// of the workgroup calls; ends synchronised.
 template <int NT>
 __device__ __forceinline__ void st_pose_pairs_lines(double* E, double* Ls, const double* kf, const int32_t* __restrict__ counts, int f,
                                                     const double* __restrict__ F2, int C, int P, double min_score) {
@@ -152,10 +163,10 @@ __device__ __forceinline__ void st_pose_pairs_lines(double* E, double* Ls, const
             const int view = (set == 0 || set == 3) ? u : v;
             const double* Fm = F2 + (set < 2 ? u * C + v : v * C + u) * 9;
             const double* k = kf + (view * P + p) * 51 + joint * 3;
-            double a, b, c, nrm;
-            epi_line(Fm, k[0], k[1], (set & 1) != 0, a, b, c, nrm);
-            double* L = Ls + (((vl * 4 + set) * P + p) * 17 + joint) * 4;
-            L[0] = a; L[1] = b; L[2] = c; L[3] = nrm;
+            double a, b, c0, sc, nrm;
+            epi_line(Fm, k[0], k[1], (set & 1) != 0, a, b, c0, sc, nrm);
+            double* L = Ls + (((vl * 4 + set) * P + p) * 17 + joint) * 5;
+            L[0] = a; L[1] = b; L[2] = c0; L[3] = sc; L[4] = nrm;
         }
         __syncthreads();
         for (int it = tid; it < 2 * 2 * P * P; it += NT) {
@@ -173,16 +184,16 @@ __device__ __forceinline__ void st_pose_pairs_lines(double* E, double* Ls, const
             nb = nb < 0 ? 0 : (nb > P ? P : nb);
             if (pi >= na || pj >= nb) continue;
             const int qi = va * P + pi, qj = vb * P + pj;
-            const double* L1 = Ls + ((vl * 4 + (dir ? 2 : 0)) * P + pi) * 68;    // lines of the first pose's joints under F
-            const double* L2 = Ls + ((vl * 4 + (dir ? 3 : 1)) * P + pj) * 68;    // lines of the second pose's joints under F^T
+            const double* L1 = Ls + ((vl * 4 + (dir ? 2 : 0)) * P + pi) * 85;    // lines of the first pose's joints under F
+            const double* L2 = Ls + ((vl * 4 + (dir ? 3 : 1)) * P + pj) * 85;    // lines of the second pose's joints under F^T
             const double* k1 = kf + qi * 51, * k2 = kf + qj * 51;
             double total = 0.0;
             int cnt = 0;
             for (int j = 0; j < 17; ++j) {
                 if (!(k1[j * 3 + 2] * k2[j * 3 + 2] > min_score)) continue;
-                const double d1 = epi_dist(L1[j * 4], L1[j * 4 + 1], L1[j * 4 + 2], L1[j * 4 + 3], k2[j * 3], k2[j * 3 + 1]);
-                const double d2 = epi_dist(L2[j * 4], L2[j * 4 + 1], L2[j * 4 + 2], L2[j * 4 + 3], k1[j * 3], k1[j * 3 + 1]);
-                total = total + 0.5 * (d1 + d2);
+                const double d1 = epi_dist(L1[j * 5], L1[j * 5 + 1], L1[j * 5 + 2], L1[j * 5 + 3], L1[j * 5 + 4], k2[j * 3], k2[j * 3 + 1]);
+                const double d2 = epi_dist(L2[j * 5], L2[j * 5 + 1], L2[j * 5 + 2], L2[j * 5 + 3], L2[j * 5 + 4], k1[j * 3], k1[j * 3 + 1]);
+                total = fma(0.5, d1 + d2, total);
                 ++cnt;
             }
             E[qi * N + qj] = cnt ? total / cnt : __longlong_as_double(0x7ff8000000000000LL);
@@ -417,7 +428,8 @@ __device__ __forceinline__ void assign_chain(int lane, int nl, int b, int f, con
             int32_t tmp[64];
             for (int c = 0; c < C; ++c)
                 for (int p = 0; p < cnt[c]; ++p, ++node)
-                    if (lab[node] == k && m < 64) tmp[m++] = (f * C + c) * P + p;
+                    if (lab[node] == k) { if (m < 64) tmp[m] = (f * C + c) * P + p; ++m; }
+            if (m > 64) { if (ovf) atomicOr(ovf, 1); m = 64; }   // (a cluster of more than 64 poses: cut, and said so, as in the ballot form)
             if (m >= 2) {
                 if (ovf && m > V) atomicOr(ovf, 1);
                 if (created < K) {

@@ -636,8 +636,7 @@ def fmats_from_projections(Pmats: torch.Tensor) -> torch.Tensor:
     return F2
 
 
-def st_affinity(kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, want_D=False, min_score=0.1):
-    """AS-7/8/9.  -> (W (B,NS,NS) f64, D | None, group_counts (B,C+1) i32)."""
+def _st_affinity(name, kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, want_D, min_score, form=()):
     F, Cn, P = kps17.shape[:3]
     B, T = track_joints.shape[:2]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -651,15 +650,24 @@ def st_affinity(kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, wan
     W = torch.empty((B, NS, NS), dtype=torch.float64, device=kps17.device)
     D = torch.empty((B, NS, NS), dtype=torch.float64, device=kps17.device) if want_D else None
     gc = torch.empty((B, Cn + 1), dtype=torch.int32, device=kps17.device)
-    check(_cabi.load().mvmc_st_affinity(_p(kps17), _p(counts), _p(frame_idx), _p(track_joints), _p(n_tracks), _p(Pmats),
-                                        _p(F2), B, Cn, P, T, float(min_score), _p(W), _p(D), _p(gc), _stream()),
-          "mvmc_st_affinity")
+    check(getattr(_cabi.load(), name)(_p(kps17), _p(counts), _p(frame_idx), _p(track_joints), _p(n_tracks), _p(Pmats), _p(F2), B, Cn, P,
+                                      T, float(min_score), *form, _p(W), _p(D), _p(gc), _stream()), name)
     return W, D, gc
 
 
-def track_assign(labels_sp, ncl_sp, labels_st, ncl_st, counts, frame_idx, n_tracks, track_params, p_max, k_max, v_max, overflow=None):
-    """TK-1 first half -> members (B,T+K,V), cold (B,T+K), init (B,T+K,68), status (B,T), n_new (B).
-    overflow (B) i32 in/out: bit 0 set where a cluster or member did not fit (k_max new clusters, v_max views)."""
+def st_affinity(kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, want_D=False, min_score=0.1):
+    """AS-7/8/9.  -> (W (B,NS,NS) f64, D | None, group_counts (B,C+1) i32)."""
+    return _st_affinity("mvmc_st_affinity", kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, want_D, min_score)
+
+
+def debug_st_affinity_wg(kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, nt_threads, pair_form, want_D=False, min_score=0.1):
+    """Diagnostic: st_affinity's arguments and results from the form the chain kernels run -- one workgroup of nt_threads (256 | 512)
+    per chain, the 2-D / 2-D block computed in place (pair_form 0), made ahead per pose pair (1) or by line tables (2)."""
+    return _st_affinity("mvmc_debug_st_affinity_wg", kps17, counts, frame_idx, track_joints, n_tracks, Pmats, F2, want_D, min_score,
+                        form=(int(nt_threads), int(pair_form)))
+
+
+def _track_assign_outputs(labels_sp, labels_st, counts, track_params, p_max, k_max, v_max):
     B, T = track_params.shape[:2]
     Cn = counts.shape[1]
     dev_ = track_params.device
@@ -672,22 +680,57 @@ def track_assign(labels_sp, ncl_sp, labels_st, ncl_st, counts, frame_idx, n_trac
     init = torch.empty((B, NP, 68), dtype=torch.float64, device=dev_)
     status = torch.empty((B, T), dtype=torch.int32, device=dev_)
     n_new = torch.empty((B,), dtype=torch.int32, device=dev_)
+    return B, T, Cn, mem, cold, init, status, n_new
+
+
+def track_assign(labels_sp, ncl_sp, labels_st, ncl_st, counts, frame_idx, n_tracks, track_params, p_max, k_max, v_max, overflow=None):
+    """TK-1 first half -> members (B,T+K,V), cold (B,T+K), init (B,T+K,68), status (B,T), n_new (B).
+    overflow (B) i32 in/out: bit 0 set where a cluster or member did not fit (k_max new clusters, v_max views)."""
+    B, T, Cn, mem, cold, init, status, n_new = _track_assign_outputs(labels_sp, labels_st, counts, track_params, p_max, k_max, v_max)
     check(_cabi.load().mvmc_track_assign(_p(labels_sp), _p(ncl_sp), _p(labels_st), _p(ncl_st), _p(counts), _p(frame_idx),
                                          _p(n_tracks), _p(track_params), B, Cn, p_max, T, k_max, v_max, _p(mem), _p(cold),
                                          _p(init), _p(status), _p(n_new), _p(overflow), _stream()), "mvmc_track_assign")
     return mem, cold, init, status, n_new
 
 
-def track_commit(status, n_new, ik_params, ik_joints, track_params, track_joints, meta, n_tracks, next_id, n_dead,
-                 k_max, n_inits=3, slot_src=None, overflow=None):
-    """TK-1 second half: updates the tracklet table tensors in place (overflow bit 1: a new tracklet did not fit t_max slots)."""
+def debug_track_assign_wave(labels_sp, ncl_sp, labels_st, ncl_st, counts, frame_idx, n_tracks, track_params, p_max, k_max, v_max,
+                            overflow=None, want_counts=False):
+    """Diagnostic: track_assign's arguments and results from the 64-lane ballot form the chain kernels run (one wave per chain).
+    want_counts: -> also n_members (B,T+K) i32, and rows of members are then valid in [0, count) only (no -1 padding)."""
+    B, T, Cn, mem, cold, init, status, n_new = _track_assign_outputs(labels_sp, labels_st, counts, track_params, p_max, k_max, v_max)
+    n_mem = torch.empty((B, T + k_max), dtype=torch.int32, device=mem.device) if want_counts else None
+    check(_cabi.load().mvmc_debug_track_wave(0, _p(labels_sp), _p(ncl_sp), _p(labels_st), _p(ncl_st), _p(counts), _p(frame_idx),
+                                             _p(n_tracks), _p(track_params), B, Cn, p_max, T, k_max, v_max, _p(mem), _p(n_mem),
+                                             _p(cold), _p(init), _p(status), _p(n_new), None, None, 0, None, None, None, None, None,
+                                             _p(overflow), _stream()), "mvmc_debug_track_wave")
+    return (mem, cold, init, status, n_new, n_mem) if want_counts else (mem, cold, init, status, n_new)
+
+
+def _track_commit_req(ik_params, ik_joints, track_params, meta, k_max):
     B, T = track_params.shape[:2]
     _req(ik_params, torch.float64, "ik_params", (B, T + k_max, 68))
     _req(ik_joints, torch.float64, "ik_joints", (B, T + k_max, 18, 3))
     _req(meta, torch.int32, "meta", (B, T, 4))
+    return B, T
+
+
+def track_commit(status, n_new, ik_params, ik_joints, track_params, track_joints, meta, n_tracks, next_id, n_dead,
+                 k_max, n_inits=3, slot_src=None, overflow=None):
+    """TK-1 second half: updates the tracklet table tensors in place (overflow bit 1: a new tracklet did not fit t_max slots)."""
+    B, T = _track_commit_req(ik_params, ik_joints, track_params, meta, k_max)
     check(_cabi.load().mvmc_track_commit(_p(status), _p(n_new), _p(ik_params), _p(ik_joints), B, T, k_max, n_inits,
                                          _p(track_params), _p(track_joints), _p(meta), _p(n_tracks), _p(next_id),
                                          _p(n_dead), _p(slot_src), _p(overflow), _stream()), "mvmc_track_commit")
+
+
+def debug_track_commit_wave(status, n_new, ik_params, ik_joints, track_params, track_joints, meta, n_tracks, next_id, n_dead,
+                            k_max, n_inits=3, slot_src=None, overflow=None):
+    """Diagnostic: track_commit from the multi-lane form the chain kernels run (one 64-lane wave per chain)."""
+    B, T = _track_commit_req(ik_params, ik_joints, track_params, meta, k_max)
+    check(_cabi.load().mvmc_debug_track_wave(1, None, None, None, None, None, None, _p(n_tracks), _p(track_params), B, 0, 0, T, k_max,
+                                             0, None, None, None, None, _p(status), _p(n_new), _p(ik_params), _p(ik_joints), n_inits,
+                                             _p(track_joints), _p(meta), _p(next_id), _p(n_dead), _p(slot_src), _p(overflow),
+                                             _stream()), "mvmc_debug_track_wave")
 
 
 def rig_start(obs: torch.Tensor, rig_of: torch.Tensor, Pmats: torch.Tensor, min_score=0.1):

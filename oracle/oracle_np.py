@@ -406,11 +406,13 @@ def fundamental_from_projections(P1, P2):
     return F
 
 
-def epipolar_error(P1, kps1, sc1, P2, kps2, sc2, min_score=0.05, invalid=np.nan):
-    """calc_epipolar_error, mv_math_util.py:80-115."""
+def epipolar_error(P1, kps1, sc1, P2, kps2, sc2, min_score=0.05, invalid=np.nan, F=None):
+    """calc_epipolar_error, mv_math_util.py:80-115.  F: the pair's fundamental matrix where the caller has it (default: made here,
+    as the reference does)."""
     if len(kps1) == 0:
         return invalid
-    F = fundamental_from_projections(P1, P2)
+    if F is None:
+        F = fundamental_from_projections(P1, P2)
     l12 = epilines(F, kps1, 1)
     l21 = epilines(F, kps2, 2)
     valid = (np.asarray(sc1).ravel() * np.asarray(sc2).ravel()) > min_score
@@ -452,10 +454,12 @@ def spatial_time_affinity(D):
     return D, S
 
 
-def spatial_time_distance(track_joints, views_kps, Ps):
+def spatial_time_distance(track_joints, views_kps, Ps, min_score=0.1, Fs=None):
     """Distance matrix of match_spatial_time, motion_capture.py:651-740.
     track_joints: list of (18,3); views_kps: per view list of (17,3); Ps: per view (3,4).
-    Node order = tracklets, then 2-D poses by view.  Returns (D with NaN, dim_groups)."""
+    Node order = tracklets, then 2-D poses by view.  Returns (D with NaN, dim_groups).
+    min_score: the joint-score threshold (the reference's constant 0.1); Fs (C,C,3,3) or None: fundamental matrices to use in place
+    of fundamental_from_projections(Ps[i], Ps[j])."""
     T = len(track_joints)
     cam_of = [-1] * T
     nodes = [('3d', j) for j in track_joints]
@@ -479,13 +483,13 @@ def spatial_time_distance(track_joints, views_kps, Ps):
             if ki == '2d' and kj == '2d':
                 a, b = nodes[i][1], nodes[j][1]
                 D[i, j] = epipolar_error(Ps[cam_of[i]], a[:, :2], a[:, 2], Ps[cam_of[j]], b[:, :2], b[:, 2],
-                                         0.1, np.nan)
+                                         min_score, np.nan, None if Fs is None else Fs[cam_of[i]][cam_of[j]])
             elif ki == '2d' and kj == '3d':
                 a = nodes[i][1]
-                D[i, j] = reprojection_error(nodes[j][1], a[:, :2], a[:, 2], Ps[cam_of[i]], 0.1, np.nan)
+                D[i, j] = reprojection_error(nodes[j][1], a[:, :2], a[:, 2], Ps[cam_of[i]], min_score, np.nan)
             elif ki == '3d' and kj == '2d':
                 b = nodes[j][1]
-                D[i, j] = reprojection_error(nodes[i][1], b[:, :2], b[:, 2], Ps[cam_of[j]], 0.1, np.nan)
+                D[i, j] = reprojection_error(nodes[i][1], b[:, :2], b[:, 2], Ps[cam_of[j]], min_score, np.nan)
             else:
                 D[i, j] = np.nan
     return D, dim_groups
