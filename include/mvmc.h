@@ -642,6 +642,33 @@ int mvmc_smooth_window_robust(const mvmcSkeleton* skel_host, const double* kps17
                               double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
                               double* work, long long work_doubles, int loss, double loss_px, mvmcStream_t stream);
 
+/* ---- foot contacts of the trajectory smoother (smoothing.py: contacts=; restated in tests/smooth_contact_np.py).  Per identity and
+ * foot f = 0 (skeleton joint MVMC_SMOOTH_FOOT_L), 1 (MVMC_SMOOTH_FOOT_R) a label c[t][f] per row; a run is a maximal stretch of
+ * consecutive rows with c != 0 of one foot, and every run has one anchor a (metres).  The term
+ *   E_contact = 1/2 contact_weight sum_{t, f: c != 0} |X_f(x_t) - a_run(t, f)|^2      (contact_weight in px^2 / m^2)
+ * belongs to one row for fixed anchors: it joins that row's block alone, outside the robust loss, and the step, the sweep and the
+ * covariance entry read the blocks as they are.  Over the anchors it is minimised in closed form: the mean of X_f over the run.
+ * mvmc_smooth_blocks_contact is mvmc_smooth_blocks_robust with the term: cmask (N, 2) i32 and anchors (N, 2, 3) f64 per row (an anchor
+ * is read only where the mask is not 0), contact_weight finite and >= 0.  A row whose mask is (0, 0) gets the blocks of
+ * mvmc_smooth_blocks_robust bit for bit; a row with a mask but no selected view gets the term alone.
+ * mvmc_smooth_contact_anchors, ONE launch, one workgroup of two waves per identity, one wave per foot (csrc/mvmc_smooth_contact.hip):
+ * joints (N, 18, 3) f64 the FK joints of the rows, id_lo (n_ids + 1) i32.  detect != 0: the labels are made here -- row t of foot f is
+ * a contact when its speed, |p[t+1] - p[t-1]| / 2 inside the identity and |p[t+1] - p[t]| at its first and |p[t] - p[t-1]| at its last
+ * row (metres per frame), is < speed and, with use_ground != 0, ground[0..2] . p - ground[3] < height (ground: 4 doubles on the HOST,
+ * the plane's normal and offset; not read otherwise); then the runs shorter than min_run rows are dropped.  detect == 0: cmask is read as given and not changed.  anchors out: the run's mean (summed in row order)
+ * on every row of the run, NaN on every other row.  ctl (n_ids, 4) i32, mvmc_smooth_step's control words: ctl[id][0] is set to 0 (the
+ * identity runs again) when either foot has a run, and is not touched otherwise.  An identity's numbers depend on nothing else in
+ * the launch; there is no limit on the rows of an identity. ---- */
+#define MVMC_SMOOTH_FOOT_L 3
+#define MVMC_SMOOTH_FOOT_R 6
+int mvmc_smooth_blocks_contact(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                               const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of, const int32_t* ctl,
+                               int n_frames, double* blk, int loss, double loss_px, const int32_t* cmask, const double* anchors,
+                               double contact_weight, mvmcStream_t stream);
+int mvmc_smooth_contact_anchors(const double* joints, const int32_t* id_lo, int n_ids, int n_frames, int detect, double speed,
+                                int min_run, int use_ground, const double* ground, double height, int32_t* cmask, double* anchors,
+                                int32_t* ctl, mvmcStream_t stream);
+
 /* ---- re-linking of the records of one person (multiview_motion_capture_amd/relinking.py).  No counterpart in the reference.  Per
  * sequence, its records in (first frame, track id) order are the nodes; record a may be followed by record b when 1 <= gap =
  * first(b) - last(a) <= max_gap, at the cost mean_k |last_joints(a)[k] + v gap - first_joints(b)[k]| (metres; v = the mean of a's end

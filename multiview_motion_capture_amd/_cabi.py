@@ -27,6 +27,7 @@ SMOOTH_K, SMOOTH_BLOCK_DOUBLES, SMOOTH_WORK_DOUBLES, SMOOTH_INFO_DOUBLES, SMOOTH
 SMOOTH_COV_INFO_DOUBLES, SMOOTH_JOINTS = 8, 18
 SMOOTH_WIN_MAX, SMOOTH_WIN_RING, SMOOTH_WIN_ITEM_INTS, SMOOTH_WIN_INFO_DOUBLES = 32, 66, 8, 16
 SMOOTH_LOSS_NONE, SMOOTH_LOSS_HUBER, SMOOTH_LOSS_CAUCHY = 0, 1, 2                                     # MVMC_SMOOTH_LOSS_*
+SMOOTH_FOOT_L, SMOOTH_FOOT_R = 3, 6                                                                   # MVMC_SMOOTH_FOOT_*: the ankles
 RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
 RIG_TILE, RIG_MAX_CAMS, RIG_MAX_ITER, RIG_CAM_DOUBLES, RIG_INFO_DOUBLES = 64, 8, 24, 21, 64
 LENS_DOUBLES, LENS_PINHOLE, LENS_BROWN, LENS_FISHEYE, LENS_MAX_ITER, LENS_FISHEYE_MAX_THETA = 16, 0, 1, 2, 12, 1.5
@@ -43,6 +44,7 @@ SYMBOLS = (
     "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_cov", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
     "mvmc_smooth_blocks_robust", "mvmc_smooth_obs_weights", "mvmc_smooth_window_robust",
+    "mvmc_smooth_blocks_contact", "mvmc_smooth_contact_anchors",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
     "mvmc_rig_accumulate_robust", "mvmc_rig_step_robust", "mvmc_rig_weights",
     "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
@@ -165,6 +167,8 @@ def load():
         "mvmc_smooth_obs_weights": [SK, vp, i32, i32, vp, vp, vp, vp, i32, i32, f64, vp, vp],
         "mvmc_smooth_window_robust": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, f64, f64, f64, f64, f64,
                                       f64, f64, vp, vp, C.c_longlong, i32, f64, vp],
+        "mvmc_smooth_blocks_contact": [SK, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, f64, vp, vp, f64, vp],
+        "mvmc_smooth_contact_anchors": [vp, vp, i32, i32, i32, f64, i32, i32, C.POINTER(C.c_double), f64, vp, vp, vp, vp],
         "mvmc_relink_work_words": [i32],
         "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
         "mvmc_rig_part_doubles": [i32],

@@ -119,11 +119,21 @@ __device__ __forceinline__ void sm_rho_w(double e2, double delta, double& rho, d
 // LOSS = MVMC_SMOOTH_LOSS_NONE is the arithmetic without a loss, operation for operation (loss_px is not read).  With a loss the pair's
 // rho and w are taken in registers inside the view loop: W_k and t_k carry w s^2, E = sum s^2 rho; the score stays outside the loss, and
 // a pair whose score is 0 contributes nothing whatever its residual.  The reductions and the LDS are the same for every LOSS.
-template <int LOSS>
+// CONTACT (default false: none of the three last arguments is read, the code is the one without the parameter): the foot-contact term
+// of the row, 1/2 wc |X_K - a|^2 for foot f = 0 (K = MVMC_SMOOTH_FOOT_L), 1 (MVMC_SMOOTH_FOOT_R) when cmask[f] != 0, a = anchors + 3 f
+// (include/mvmc.h: mvmc_smooth_blocks_contact).  It is quadratic in X_K, so it joins the observed joint's own W_k (+ wc I), t_k
+// (+ wc (X_K - a)) after the views' reduction, in the lane that owns them, and E (left, then right); it stays outside the loss.  A
+// row whose mask is (0, 0) runs the code without the term, operation for operation; a row with a mask and no view runs the whole row
+// with an empty view loop instead of the no-data return.
+template <int LOSS, bool CONTACT = false>
 __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, const double* __restrict__ kps17,
                                              const double* __restrict__ Prig, int C, int Pmax, const int32_t* __restrict__ members,
-                                             const double* __restrict__ x, double* __restrict__ out, double loss_px) {
+                                             const double* __restrict__ x, double* __restrict__ out, double loss_px,
+                                             const int32_t* __restrict__ cmask = nullptr, const double* __restrict__ anchors = nullptr,
+                                             double wc = 0.0) {
     const int lane = threadIdx.x & 63;
+    bool on[2] = {false, false};
+    if constexpr (CONTACT) { on[0] = uni((int)cmask[0]) != 0; on[1] = uni((int)cmask[1]) != 0; }
     if (lane == 0) {
         int n = 0;
         for (int c = 0; c < C; ++c) {
@@ -134,7 +144,7 @@ __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, co
     }
     MVMC_WAVE_SYNC();
     const int nv = uni(L.nv);
-    if (nv == 0) {   // no data: the prior alone places the frame
+    if (nv == 0 && !(on[0] || on[1])) {   // no data: the prior alone places the frame
         for (int i = lane; i < SM_BLK; i += 64) out[i] = 0.0;
         return;
     }
@@ -178,11 +188,24 @@ __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, co
         o[7] += ct * (du[1] * gu + dv[1] * gv);
         o[8] += ct * (du[2] * gu + dv[2] * gv);
     }
-    const double E = LOSS == MVMC_SMOOTH_LOSS_NONE ? 0.5 * wave_sum(f2) : wave_sum(f2);   // 1/2 sum (s e)^2, or sum s^2 rho
+    double E = LOSS == MVMC_SMOOTH_LOSS_NONE ? 0.5 * wave_sum(f2) : wave_sum(f2);   // 1/2 sum (s e)^2, or sum s^2 rho
 #pragma unroll
     for (int e = 0; e < 9; ++e) {
         o[e] += xor_lane<16>(o[e]);
         o[e] += xor_lane<32>(o[e]);
+    }
+    if constexpr (CONTACT) {
+        for (int f = 0; f < 2; ++f) {   // left, then right
+            if (!on[f]) continue;
+            const int K = f == 0 ? MVMC_SMOOTH_FOOT_L : MVMC_SMOOTH_FOOT_R;
+            const double* a = anchors + 3 * f;
+            const double c0 = L.pos[3 * K] - a[0], c1 = L.pos[3 * K + 1] - a[1], c2 = L.pos[3 * K + 2] - a[2];
+            E += 0.5 * wc * (c0 * c0 + c1 * c1 + c2 * c2);   // (every lane: E stays wave-uniform)
+            if (lane < NOBS && kIkSkel[lane] == K) {         // the lane of the ankle's observed-joint slot
+                o[0] += wc; o[3] += wc; o[5] += wc;
+                o[6] += wc * c0; o[7] += wc * c1; o[8] += wc * c2;
+            }
+        }
     }
     if (lane < NOBS) {
 #pragma unroll

@@ -436,10 +436,12 @@ def smooth_loss_args(loss, loss_px, what: str):
 
 def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,
                   id_of: torch.Tensor, ctl: torch.Tensor, blk: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None, *,
-                  loss: Optional[str] = None, loss_px: Optional[float] = None) -> None:
+                  loss: Optional[str] = None, loss_px: Optional[float] = None, cmask: Optional[torch.Tensor] = None,
+                  anchors: Optional[torch.Tensor] = None, contact_weight: Optional[float] = None) -> None:
     """The data blocks of the trajectory smoother at x (include/mvmc.h: mvmc_smooth_blocks), one wave per row, into blk (2,N,820).
     loss "huber" / "cauchy" with loss_px > 0 (pixels): the blocks of the reweighted model, J^T W J, J^T W r and sum s^2 rho
-    (mvmc_smooth_blocks_robust); loss=None is the plain entry."""
+    (mvmc_smooth_blocks_robust); loss=None is the plain entry.  cmask (N,2) i32 with anchors (N,2,3) f64 and contact_weight >= 0:
+    the blocks with the foot-contact term of the labelled rows (mvmc_smooth_blocks_contact), with or without a loss."""
     sk = skeleton if skeleton is not None else make_skeleton()
     F, Cn, P = kps17.shape[:3]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -451,6 +453,16 @@ def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor
     _req(members, torch.int32, "members", (N, Cn))
     _req(ctl, torch.int32, "ctl", (None, 4))
     _req(blk, torch.float64, "blk", (2, N, _cabi.SMOOTH_BLOCK_DOUBLES))
+    if cmask is not None or anchors is not None or contact_weight is not None:
+        if cmask is None or anchors is None or contact_weight is None:
+            raise ValueError("smooth_blocks: cmask, anchors and contact_weight go together")
+        _req(cmask, torch.int32, "cmask", (N, 2))
+        _req(anchors, torch.float64, "anchors", (N, 2, 3))
+        code, px = smooth_loss_args(loss, loss_px, "smooth_blocks")
+        check(_cabi.load().mvmc_smooth_blocks_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
+                                                      _p(ctl), N, _p(blk), code, px, _p(cmask), _p(anchors), float(contact_weight),
+                                                      _stream()), "mvmc_smooth_blocks_contact")
+        return
     if loss is None:
         check(_cabi.load().mvmc_smooth_blocks(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of), _p(ctl),
                                               N, _p(blk), _stream()), "mvmc_smooth_blocks")
@@ -458,6 +470,27 @@ def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor
     code, px = smooth_loss_args(loss, loss_px, "smooth_blocks")
     check(_cabi.load().mvmc_smooth_blocks_robust(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
                                                  _p(ctl), N, _p(blk), code, px, _stream()), "mvmc_smooth_blocks_robust")
+
+
+def smooth_contact_anchors(joints: torch.Tensor, id_lo: torch.Tensor, cmask: torch.Tensor, anchors: torch.Tensor, ctl: torch.Tensor,
+                           detect: bool, speed: float, min_run: int, ground=None, height: float = 0.0) -> None:
+    """The foot-contact labels and anchors of every identity from its FK joints (include/mvmc.h: mvmc_smooth_contact_anchors), one
+    launch.  joints (N,18,3), id_lo (n_ids + 1,) i32; cmask (N,2) i32 is written when ``detect`` (speed in m / frame, runs of at
+    least min_run rows, ground = (normal (3,), offset) with ``height`` or None) and read as given otherwise; anchors (N,2,3) f64 out,
+    NaN off the runs; ctl (n_ids,4) i32: the stop word of an identity with a run is cleared."""
+    N = joints.shape[0]
+    n_ids = id_lo.shape[0] - 1
+    _req(joints, torch.float64, "joints", (N, 18, 3))
+    _req(id_lo, torch.int32, "id_lo", (n_ids + 1,))
+    _req(cmask, torch.int32, "cmask", (N, 2))
+    _req(anchors, torch.float64, "anchors", (N, 2, 3))
+    _req(ctl, torch.int32, "ctl", (n_ids, 4))
+    g = None
+    if ground is not None:
+        g = (C.c_double * 4)(*[float(v) for v in ground[0]], float(ground[1]))
+    check(_cabi.load().mvmc_smooth_contact_anchors(_p(joints), _p(id_lo), n_ids, N, int(bool(detect)), float(speed), int(min_run),
+                                                   int(g is not None), g, float(height), _p(cmask), _p(anchors), _p(ctl), _stream()),
+          "mvmc_smooth_contact_anchors")
 
 
 def smooth_obs_weights(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,

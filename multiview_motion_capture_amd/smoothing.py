@@ -28,9 +28,15 @@ pair's Jacobian rows and residual by sqrt(w), w = 1 or delta / e (Huber), 1 / (1
 least squares without a second-order term; the Levenberg-Marquardt rules, the sweep and the prior are untouched, and the view gate of
 the selection still comes first.  It is for the keypoint the gate cannot see: one limb exchanged, one joint put on the neighbour.
 
+contacts="auto" or given labels (default None: nothing of it runs) adds foot contacts: per run of consecutive rows on which an ankle
+is labelled as planted, 1/2 contact_weight |ankle(x_t) - a|^2 with one anchor a per run, minimised over x and the anchors in
+alternation: further rounds of the same solve, the anchors (and with "auto" the labels) re-made between them by one launch.  It is
+for the foot that slides under a retargeted character; smooth_sequences' docstring has the model and what it is not.
+
 Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; with a loss mvmc_smooth_blocks_robust and
-mvmc_smooth_obs_weights; selection: mvmc_body_observe), the optional per-frame covariance csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov);
-NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py, tests/smooth_robust_np.py.
+mvmc_smooth_obs_weights; with contacts mvmc_smooth_blocks_contact and csrc/mvmc_smooth_contact.hip: mvmc_smooth_contact_anchors;
+selection: mvmc_body_observe), the optional per-frame covariance csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov);
+NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py, tests/smooth_robust_np.py, tests/smooth_contact_np.py.
 Sequences with the same number of cameras share every launch, each with its own rig.
 """
 from __future__ import annotations
@@ -60,6 +66,12 @@ MAX_WORK_BYTES = 1 << 30
 _BLOCK, _WORK = 820, 3940   # include/mvmc.h: doubles per row
 _JOINTS, _K, _COV_INFO = 18, 39, 8   # include/mvmc.h: skeleton joints, MVMC_SMOOTH_K, MVMC_SMOOTH_COV_INFO_DOUBLES
 _OBS = 16                            # observed joints of a view (the IK's observation rows): mvmc_smooth_obs_weights' last axis
+# Foot contacts (contacts=): tools/smooth_contact_probe.py on planted walks with ground truth (profiles/smooth_contact_probe.json)
+CONTACT_WEIGHT = 1e6       # px^2 / m^2, the root prior's unit
+CONTACT_SPEED = 0.01       # m / frame: an ankle slower than this is planted (contacts="auto")
+CONTACT_MIN_FRAMES = 3     # a detected run shorter than this is dropped
+CONTACT_HEIGHT = 0.15      # m over the ground plane, when one is given
+_FEET = (3, 6)             # include/mvmc.h: MVMC_SMOOTH_FOOT_L, MVMC_SMOOTH_FOOT_R (the two ankles of the 18-joint skeleton)
 
 
 def stage1_columns() -> np.ndarray:
@@ -169,6 +181,66 @@ def check_loss(who: str, loss, loss_px) -> float:
     return float(loss_px)
 
 
+def _number(v) -> bool:
+    return not isinstance(v, (str, bytes, bool)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def _check_contact_args(contacts, contact_weight, contact_speed, contact_min_frames, contact_rounds, ground, contact_height):
+    """The scalar foot-contact arguments (host only) -> (auto, weight, speed, min_frames, rounds, ground or None, height)."""
+    who = "smooth_sequences"
+    auto = isinstance(contacts, str)
+    if auto and contacts != "auto":
+        raise ValueError(f"{who}: contacts must be None, \"auto\" or per sequence a list of label arrays, got {contacts!r}")
+    if not auto and not isinstance(contacts, (list, tuple)):
+        raise ValueError(f"{who}: contacts must be None, \"auto\" or per sequence a list of label arrays, got {type(contacts).__name__}")
+    if not _number(contact_weight) or not math.isfinite(contact_weight) or contact_weight < 0:
+        raise ValueError(f"{who}: contact_weight must be a finite number >= 0, got {contact_weight!r}")
+    if not _number(contact_speed) or not math.isfinite(contact_speed):
+        raise ValueError(f"{who}: contact_speed must be a finite number, got {contact_speed!r}")
+    if not _number(contact_height) or not math.isfinite(contact_height):
+        raise ValueError(f"{who}: contact_height must be a finite number, got {contact_height!r}")
+    for name, v in (("contact_min_frames", contact_min_frames), ("contact_rounds", contact_rounds)):
+        if not _number(v) or int(v) != v or int(v) < 1:
+            raise ValueError(f"{who}: {name} must be an integer >= 1, got {v!r}")
+    g = None
+    if ground is not None:
+        if not auto:
+            raise ValueError(f"{who}: ground gates the detection of contacts=\"auto\"; given labels are taken as they are")
+        try:
+            normal, off = ground
+            normal = np.array(normal, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: ground must be (normal (3,), offset)") from None
+        if normal.shape != (3,) or not np.all(np.isfinite(normal)) or not _number(off) or not math.isfinite(off):
+            raise ValueError(f"{who}: ground must be (normal (3,), offset) of finite numbers")
+        g = (normal, float(off))
+    return auto, float(contact_weight), float(contact_speed), int(contact_min_frames), int(contact_rounds), g, float(contact_height)
+
+
+def _check_contact_labels(contacts, recs):
+    """Given labels against the checked records (host only) -> per sequence, per record None or an (m, 2) int32 array over f0..f1."""
+    who = "smooth_sequences"
+    if len(contacts) != len(recs):
+        raise ValueError(f"{who}: contacts has {len(contacts)} entries for {len(recs)} sequences")
+    out = []
+    for s, (cs, rs) in enumerate(zip(contacts, recs)):
+        if not isinstance(cs, (list, tuple)) or len(cs) != len(rs):
+            raise ValueError(f"{who}: contacts[{s}] must be a list aligned with the sequence's {len(rs)} records")
+        row = []
+        for j, (c, r) in enumerate(zip(cs, rs)):
+            if c is None:
+                row.append(None)
+                continue
+            a = np.asarray(c)
+            m = int(r[0][-1] - r[0][0] + 1)
+            if a.dtype != np.bool_ or a.shape != (m, 2):
+                raise ValueError(f"{who}: contacts[{s}][{j}] must be None or a bool array ({m}, 2) over the record's frames f0..f1 "
+                                 f"(columns left, right), got {a.dtype} {a.shape}")
+            row.append(a.astype(np.int32))
+        out.append(row)
+    return out
+
+
 def _check(sequences, tracklets_per_sequence):
     return check_records(sequences, tracklets_per_sequence, "smooth_sequences", increasing=True, finite=True,
                          cameras=(1, MAX_VIEWS, f"sequence {{s}}: {{C}} cameras, at most {MAX_VIEWS}"))
@@ -178,7 +250,9 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                      root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
                      fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0",
                      timings: Optional[dict] = None, covariance: Optional[str] = None, noise_px: Optional[float] = None,
-                     loss: Optional[str] = None, loss_px: float = LOSS_PX) -> List[list]:
+                     loss: Optional[str] = None, loss_px: float = LOSS_PX, contacts=None, contact_weight: float = CONTACT_WEIGHT,
+                     contact_speed: float = CONTACT_SPEED, contact_min_frames: int = CONTACT_MIN_FRAMES, contact_rounds: int = 1,
+                     ground=None, contact_height: float = CONTACT_HEIGHT) -> List[list]:
     """Smooth every identity of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows
     track_sequences and fit_sequences take -- from its MvTracklet records (fit_sequences, track_sequences, run_main_batched,
     MvTracker.update_4d, LivePool).  Returns, per sequence, NEW records in the input order (the inputs are not touched): the same
@@ -211,27 +285,56 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     one-frame records are all NaN.  It tells which keypoints of which camera were voted down.  timings gets a "weights" part.
     With covariance="joints" the launch inverts J^T W J + the prior at the final weights, and smooth_edof and smooth_nres are defined
     as above on the weighted blocks; the ESTIMATED smooth_noise_px is then biased low, because rho <= 1/2 e^2 shrinks E_data while
-    smooth_nres still counts every residual: under a loss noise_px= is the honest choice."""
+    smooth_nres still counts every residual: under a loss noise_px= is the honest choice.
+    contacts="auto" or per sequence a list aligned with its records, each item None or a bool array (m, 2) over the record's frames
+    f0..f1, columns left / right ankle (default None: nothing below is computed or set, the launches and the bits are those of a
+    call without the argument): a planted foot stays where it is.  A run is a maximal stretch of consecutive rows on which one foot
+    is labelled; every run has one anchor a, and E gains E_contact = 1/2 contact_weight sum |ankle(x_t) - a|^2 over the labelled
+    (row, foot) pairs (contact_weight in px^2 / m^2, the root prior's unit; outside the robust loss).  The anchors are unknowns too
+    and are minimised in closed form (the run's mean ankle).  Round 0 is the solve without contacts, launch for launch; then
+    contact_rounds times: FK, one launch (mvmc_smooth_contact_anchors) that sets every run's anchor -- and in the first round of
+    "auto" the labels: the ankle's central-difference speed on round 0's joints (one-sided at the record's ends) < contact_speed
+    m / frame and, with ground=(normal (3,), offset), normal . ankle - offset < contact_height; runs shorter than
+    contact_min_frames are dropped, there is no hysteresis --, and the same Levenberg-Marquardt loop on the blocks with the term
+    (mvmc_smooth_blocks_contact), max_iter trials again.  The joint energy over (x, anchors) never increases from round 1 on.  An
+    identity without a labelled row is not solved again: its result is that of contacts=None bit for bit.  Every record gets, rows
+    as ``poses``: ``smooth_contact`` (n, 2) bool; ``smooth_contact_anchor`` (n, 2, 3) m, NaN where there is no contact;
+    ``smooth_contact_cost`` [E_contact at the first anchors, at the end]; ``smooth_round_trials`` the trials of round 0 and of every
+    later round, ``smooth_trials`` all of them in order; ``smooth_cost`` = E_data, E_prior at round 0's start and at the last round's
+    end, E_data WITHOUT the contact part: the device sums the row costs with it, and the host subtracts E_contact computed from
+    the returned joints and anchors (so the last digits of that E_data carry the rounding of a difference).  A one-frame record:
+    all False / NaN / zeros.  covariance="joints" takes its blocks with the final labels and anchors: the covariance is conditional
+    on them, and the E_data behind an estimated smooth_noise_px includes E_contact.  timings gets a "contacts" part (FK, the
+    anchors launch and the host's share); "blocks" and "solve" hold every round's.  What this is not: the 18-joint skeleton has no
+    toes, so an ankle that pivots during push-off is held too rigidly if it is labelled; the anchor is not forced onto a floor
+    plane; contact_speed is per frame, so it depends on the frame rate.  LiveSmoother has no contacts: a fixed-lag window does not
+    know a run's future."""
     t_start = time.perf_counter()
     w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
     noise_px = _check_covariance(covariance, noise_px)
     loss_px = check_loss("smooth_sequences", loss, loss_px)
     rob = dict(loss=loss, loss_px=loss_px) if loss is not None else {}     # loss=None: the calls without the arguments
+    if contacts is not None:
+        auto, wc, c_speed, c_min, c_rounds, c_ground, c_height = _check_contact_args(contacts, contact_weight, contact_speed,
+                                                                                    contact_min_frames, contact_rounds, ground, contact_height)
     if no_sequences(sequences, tracklets_per_sequence, "smooth_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence)
+    given = _check_contact_labels(contacts, recs) if contacts is not None and not auto else None
     import torch
 
     from . import device as dev
     d = torch.device(device)
     T = dev.uploader(d)
     lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records") + (("covariance",) if covariance else ())
-                        + (("weights",) if loss is not None else ()))
+                        + (("weights",) if loss is not None else ()) + (("contacts",) if contacts is not None else ()))
     tm["prepare"] = time.perf_counter() - t_start
     out: List[list] = [[None] * len(r) for r in recs]
     per_row = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
     if covariance:
         per_row += 8 * (_JOINTS * 6 + _K)
+    if contacts is not None:
+        per_row += 4 * 2 + 8 * 6 + 8 * _JOINTS * 3     # labels, anchors and the FK joints of the rounds
     for lay in plan_groups(shapes, 1):
         if not any(recs[i] for i in lay.seq_ids):
             continue
@@ -258,7 +361,7 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
             nvf[rows] = nv_h[rec_lo[a]:rec_lo[a + 1]]
             traj.append((a, x0, filled, mem, nvf, int(sel.rig_of[rec_lo[a]])))
         t0 = lap("prepare", t0)
-        res, obs_w = {}, {}
+        res, obs_w, con = {}, {}, {}
         cap = max(1, int(max_work_bytes) // (per_row + (8 * _OBS * C if loss is not None else 0)))   # (the weights: (C, 16) per row)
         at = 0
         while at < len(traj):
@@ -291,6 +394,32 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 t0 = lap("blocks", t0)
                 dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info, work)
                 t0 = lap("solve", t0)
+            ckw = {}
+            if contacts is not None:
+                cm_h = np.zeros((N, 2), np.int32)
+                if given is not None:
+                    for s, p in enumerate(part):
+                        g = given[items[p[0]][0]][items[p[0]][1]]
+                        if g is not None:
+                            cm_h[id_lo[s]:id_lo[s + 1]] = g
+                cmask = T(cm_h)
+                anch = torch.empty((N, 2, 3), dtype=torch.float64, device=d)
+                ckw = dict(cmask=cmask, anchors=anch, contact_weight=wc)
+                infos, first = [info], None
+                t0 = lap("prepare", t0)
+                for rnd in range(c_rounds):
+                    jn_d = dev.fk(x)
+                    dev.smooth_contact_anchors(jn_d, id_lo_d, cmask, anch, ctl, auto and rnd == 0, c_speed, c_min, c_ground, c_height)
+                    if rnd == 0:
+                        first = (jn_d.cpu().numpy(), cmask.cpu().numpy(), anch.cpu().numpy())
+                    info_r = torch.zeros((len(part), 32), dtype=torch.float64, device=d)   # (a stopped identity's row stays 0)
+                    infos.append(info_r)
+                    t0 = lap("contacts", t0)
+                    for phase in range(int(max_iter) + 1):
+                        dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x if phase == 0 else xt, id_of_d, ctl, blk, **rob, **ckw)
+                        t0 = lap("blocks", t0)
+                        dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info_r, work)
+                        t0 = lap("solve", t0)
             cov = None
             if covariance:
                 # the blocks AT x (the loop's last blocks are the last trial's, which may have been rejected) into buffer 0, steered
@@ -300,7 +429,7 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 jcov = torch.empty((N, _JOINTS, 6), dtype=torch.float64, device=d)
                 pvar = torch.empty((N, _K), dtype=torch.float64, device=d)
                 cinfo = torch.empty((len(part), _COV_INFO), dtype=torch.float64, device=d)
-                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x, id_of_d, ctl_x, blk, **rob)
+                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x, id_of_d, ctl_x, blk, **rob, **ckw)
                 dev.smooth_cov(x, blk[0], id_lo_d, w, COV_MU, k17, Pm_d, rig_d, mem_d, work, jcov, pvar, cinfo)
                 t0 = lap("covariance", t0)
                 cov = (jcov.cpu().numpy(), pvar.cpu().numpy(), cinfo.cpu().numpy())
@@ -310,6 +439,17 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 wts_h = wts.cpu().numpy()
             jn = dev.fk(x).cpu().numpy()
             xs, inf = x.cpu().numpy(), info.cpu().numpy()
+            if contacts is not None:
+                t0 = lap("records", t0)
+                infs = [inf] + [i.cpu().numpy() for i in infos[1:]]
+                anc_h = anch.cpu().numpy()
+                inf = []
+                for s in range(len(part)):
+                    sl = slice(id_lo[s], id_lo[s + 1])
+                    inf_s, con[part[s][0]] = _contact_result([i[s] for i in infs], first[0][sl], first[1][sl], first[2][sl], jn[sl],
+                                                             anc_h[sl], wc)
+                    inf.append(inf_s)
+                t0 = lap("contacts", t0)
             for s, p in enumerate(part):
                 sl = slice(id_lo[s], id_lo[s + 1])
                 res[p[0]] = (xs[sl], jn[sl], inf[s]) + ((cov[0][sl], cov[1][sl], cov[2][s]) if cov else ())
@@ -322,6 +462,8 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
             _covariance_fields(out, items, traj, res, fill_gaps, noise_px)
         if loss is not None:
             _weight_fields(out, items, traj, obs_w, fill_gaps, C)
+        if contacts is not None:
+            _contact_fields(out, items, traj, con, fill_gaps, c_rounds)
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
@@ -388,6 +530,45 @@ def _covariance_fields(out, items, traj, res, fill_gaps, noise_px):
         t.smooth_cov_status = status
 
 
+def _contact_energy(joints, mask, anchors, wc) -> float:
+    """E_contact = 1/2 wc sum over the labelled (row, foot) pairs of |ankle - anchor|^2: joints (m,18,3), mask (m,2), anchors (m,2,3)."""
+    d = np.where(mask[..., None] != 0, joints[:, _FEET] - anchors, 0.0)
+    return 0.5 * wc * float(np.sum(d * d))
+
+
+def _contact_result(infs, joints1, mask, anchors1, joints, anchors, wc):
+    """One identity after its rounds: infs its info row of round 0 and of every later round, joints1 / anchors1 the first round's FK
+    joints and anchors, mask (m,2) the labels, joints / anchors the returned joints and the last round's anchors -> (the info row
+    _records reads, of the whole call: E_data without the contact part, every round's trials in order; (labels, anchors,
+    [E_contact first, end], trials per round))."""
+    live = bool(mask.any())
+    n_r = [int(i[4]) for i in infs] if live else [int(infs[0][4])] + [0] * (len(infs) - 1)
+    trials = np.concatenate([i[8:8 + n] for i, n in zip(infs, n_r)])
+    cost = np.zeros(2)
+    end = infs[0][2:4]
+    if live:
+        cost[:] = _contact_energy(joints1, mask, anchors1, wc), _contact_energy(joints, mask, anchors, wc)
+        end = np.array([infs[-1][2] - cost[1], infs[-1][3]])
+    inf = np.concatenate([infs[0][0:2], end, [float(sum(n_r)), 0.0, 0.0, 0.0], trials])
+    return inf, (mask != 0, anchors, cost, n_r)
+
+
+def _contact_fields(out, items, traj, con, fill_gaps, rounds):
+    """The smooth_contact* attributes and smooth_round_trials of the group's records (smooth_sequences' docstring)."""
+    tr = {p[0]: p for p in traj}
+    for a, (i, j) in enumerate(items):
+        t = out[i][j]
+        if a in tr:
+            filled = tr[a][2]
+            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
+            mask, anchors, cost, n_r = con[a]
+            t.smooth_contact, t.smooth_contact_anchor = mask[idx].copy(), anchors[idx].copy()
+            t.smooth_contact_cost, t.smooth_round_trials = cost, list(n_r)
+        else:   # one frame: nothing was solved
+            t.smooth_contact, t.smooth_contact_anchor = np.zeros((1, 2), bool), np.full((1, 2, 3), np.nan)
+            t.smooth_contact_cost, t.smooth_round_trials = np.zeros(2), [0] * (1 + rounds)
+
+
 def _weight_fields(out, items, traj, obs_w, fill_gaps, C):
     """smooth_obs_weight (n, C, 16) of the group's records, rows as poses; a one-frame record has nothing solved: NaN."""
     tr = {p[0]: p for p in traj}
@@ -404,8 +585,18 @@ def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calib
                      root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC, max_iter: int = 10,
                      fill_gaps: bool = True, max_work_bytes: int = MAX_WORK_BYTES, device="cuda:0", timings: Optional[dict] = None,
                      covariance: Optional[str] = None, noise_px: Optional[float] = None, loss: Optional[str] = None,
-                     loss_px: float = LOSS_PX) -> list:
-    """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records."""
+                     loss_px: float = LOSS_PX, contacts=None, contact_weight: float = CONTACT_WEIGHT,
+                     contact_speed: float = CONTACT_SPEED, contact_min_frames: int = CONTACT_MIN_FRAMES, contact_rounds: int = 1,
+                     ground=None, contact_height: float = CONTACT_HEIGHT) -> list:
+    """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records.
+    contacts: None, "auto", or a list aligned with ``tracklets`` (None or a bool array (m, 2) per record)."""
+    if contacts is not None:
+        return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel,
+                                ang_acc=ang_acc, max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device,
+                                timings=timings, covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px,
+                                contacts=contacts if isinstance(contacts, str) else [contacts], contact_weight=contact_weight,
+                                contact_speed=contact_speed, contact_min_frames=contact_min_frames, contact_rounds=contact_rounds,
+                                ground=ground, contact_height=contact_height)[0]
     return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel, ang_acc=ang_acc,
                             max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings,
                             covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px)[0]

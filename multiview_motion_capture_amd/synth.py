@@ -96,9 +96,40 @@ def scene_walk(n_frames: int, n_people: int, seed: int, segment: int = 0, kappa:
     return home_root[None] + y[..., :3], home_ang[None] + y[..., 3:].reshape(n_frames, n_people, 18, 3)
 
 
+def planted_walk(n_frames: int, n_people: int, seed: int, stance: int = 8, side_lens=None, start=None):
+    """A walk with planted feet, the ground truth for foot skate: -> root (n_frames, P, 3), angles (n_frames, P, 18, 3), contact
+    (n_frames, P, 2) bool (columns: left ankle = skeleton joint 3, right ankle = joint 6).  The angles are scene_walk(seed)'s
+    (segment 0: the mean-reverting walk around a home pose); the root is not drawn but PLACED, frame by frame, where the stance
+    ankle stays exactly where it is.  The stance foot changes every ``stance`` frames: on the frame of the change the root still
+    follows the old stance ankle, the other ankle's position on that frame becomes the new anchor, and both feet are labelled (a
+    double support); from the next frame on the root follows the new one.  So one foot is down on every frame, and an ankle does
+    not move between two consecutive frames on which it is labelled (to the rounding of one FK: ~1e-16 m).  Everybody starts on
+    the left foot, at ``start`` (P, 3) (default: scene_walk's first roots).  side_lens (11,) or (P, 11): the bone lengths the FK is
+    taken with (default: the skeleton's reference lengths).  Nothing puts the anchors on a common floor: the swing ankle is
+    wherever the angles put it when its turn comes."""
+    if int(stance) != stance or stance < 2:
+        raise ValueError("planted_walk: stance must be an integer >= 2")
+    root_s, ang = scene_walk(n_frames, n_people, seed)
+    lens = np.asarray(skeleton_arrays()[1] if side_lens is None else side_lens, np.float64) * np.ones((n_people, 11))
+    rel = batched_fk(np.zeros((n_frames, n_people, 3)), ang, np.broadcast_to(lens, (n_frames, n_people, 11)))[:, :, [3, 6]]
+    root = np.empty((n_frames, n_people, 3))
+    contact = np.zeros((n_frames, n_people, 2), dtype=bool)
+    foot = 0
+    anchor = (root_s[0] if start is None else np.asarray(start, np.float64) * np.ones((n_people, 3))) + rel[0, :, foot]
+    for t in range(n_frames):
+        root[t] = anchor - rel[t, :, foot]
+        contact[t, :, foot] = True
+        if t > 0 and t % int(stance) == 0:      # the change: the other ankle, where it is now, carries on
+            foot = 1 - foot
+            anchor = root[t] + rel[t, :, foot]
+            contact[t, :, foot] = True
+    return root, ang, contact
+
+
 def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: int = 0, dtype=np.float32,
              drop=0.05, pix_sigma=2.0, shuffle=True, frame_seed=None, occlusion=0.0, spurious=0.0, walk=None, segment: int = 0):
-    """-> dict(kps25 (F,C,P,25,3), counts (F,C) int32, K, Rt, P, gt_joints (F,P,18,3), gt_order (F,C,P)).
+    """-> dict(kps25 (F,C,P,25,3), counts (F,C) int32, K, Rt, P, gt_joints (F,P,18,3), gt_order (F,C,P)); walk="planted":
+    gt_contact (F,P,2) bool too.
 
     occlusion: probability that a person is missed entirely by a view in a frame (the view's list gets shorter: ragged counts,
     tracklets seen by one view or none, deaths and re-births); spurious: probability that such a freed slot holds a false
@@ -116,6 +147,9 @@ def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: i
     is ignored), bone lengths come from ``seed``, and this call returns segment ``segment`` of it (frames [segment n_frames,
     (segment + 1) n_frames)); noise, scores, drops and shuffles of a segment come from (seed, 1, segment).  The same seed on every rank
     with segment = rank cuts one sequence into contiguous shards: what the tracklet stitch has identities to carry across.
+    walk="planted": the scene walk's angles, bone lengths and noise streams with the roots of planted_walk(seed) -- one foot of
+    every person is planted on every frame, the stance foot changes every 8 frames --, and gt_contact (F,P,2) in the output: the
+    ground truth of foot skate (segment 0 only).
     walk=None (default): the random walk above, bit for bit the output of earlier versions."""
     K, Rt, Pm = make_cameras(n_views, np.random.default_rng(seed))
     F, C, Pn = n_frames, n_views, n_people
@@ -125,8 +159,15 @@ def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: i
         lens = side * np.random.default_rng([seed, 4]).uniform(0.9, 1.1, size=(Pn, 1)) * np.ones((Pn, 11))
         frame_seed = [seed, 5, int(segment)]
         rng = np.random.default_rng(frame_seed + [1])
+    elif walk == "planted":
+        if segment != 0:
+            raise ValueError("generate: walk='planted' has one segment")
+        lens = side * np.random.default_rng([seed, 4]).uniform(0.9, 1.1, size=(Pn, 1)) * np.ones((Pn, 11))
+        root, ang, gt_contact = planted_walk(F, Pn, seed, side_lens=lens)
+        frame_seed = [seed, 5, 0]
+        rng = np.random.default_rng(frame_seed + [1])
     elif walk is not None:
-        raise ValueError("generate: walk is None (random walk, restarted every chain_len frames) or 'scene'")
+        raise ValueError("generate: walk is None (random walk, restarted every chain_len frames), 'scene' or 'planted'")
     else:
         rng = np.random.default_rng([seed if frame_seed is None else frame_seed, 1])
         L = chain_len if chain_len > 0 else F
@@ -184,5 +225,8 @@ def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: i
         counts = keep.sum(axis=-1).astype(np.int32)
         kps[np.arange(Pn)[None, None, :] >= counts[..., None]] = 0.0
         order = np.where(np.arange(Pn)[None, None, :] >= counts[..., None], -1, order)
-    return dict(kps25=np.ascontiguousarray(kps.astype(dtype)), counts=counts, K=K, Rt=Rt, P=Pm,
-                gt_joints=joints, gt_order=order.astype(np.int32))
+    out = dict(kps25=np.ascontiguousarray(kps.astype(dtype)), counts=counts, K=K, Rt=Rt, P=Pm,
+               gt_joints=joints, gt_order=order.astype(np.int32))
+    if walk == "planted":
+        out["gt_contact"] = gt_contact
+    return out
