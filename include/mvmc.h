@@ -244,7 +244,9 @@ int mvmc_track_commit(const int32_t* status, const int32_t* n_new, const double*
  *           [0,8) i32 {identities that start in this shard, pairs matched at its inner chain boundaries, error word (bit 0: a chain
  *                 with more than id_cap ids, bit 1: an assignment did not terminate), void word (bit i = void_words[i] != 0), 0 ...}
  *           lmatch (n_chains_cap, t_max) i32: slot of the previous chain's last frame matched to slot s of this chain's first (-1;
- *                 the shard's first chain: -1, its boundary belongs to the gathered pass)
+ *                 the shard's first chain: -1, its boundary belongs to the gathered pass).  A live tracklet with a non-finite joint
+ *                 is left out of the assignment: it matches nobody (-1) and its identity starts anew; the others are assigned
+ *                 optimally among themselves
  *           lgid   (n_chains_cap, id_cap) i32: shard-local identity of (chain, local id), numbered in chain order; -1 = no such id */
 #define MVMC_BOUND_WORDS 56
 #define MVMC_ROW_WORDS 128
@@ -254,7 +256,9 @@ long long mvmc_pack_work_words(int n_frames, int chain_len, int id_cap);        
 /* Packs mvmc_chain_run's per-frame outputs (out_params (F,t_tables,68), out_joints (F,t_tables,18,3), out_meta (F,t_tables,4),
  * out_n_tracks (F)) and next_id (n_chains) into `message` (mvmc_pack_message_words words), then stitches the shard's own chain
  * boundaries (chain b-1 | b: optimal assignment -- Kuhn-Munkres -- of the last frame's tracklets to the first frame's on the mean
- * joint distance, pairs farther than max_dist metres dropped) and numbers its identities locally (the `local` section).
+ * joint distance, pairs farther than max_dist metres dropped; tracklets with a non-finite joint take no part) and numbers its
+ * identities locally (the `local` section).  n_frames = 0 (an empty shard) writes the header and an empty local section only; the
+ * table pointers may then be NULL.
  *   t_tables  slots per frame of the tables; t_max <= 16 slots of the message: the SAME on every rank (a rank whose repair tier
  *             widened its tables still packs t_max slots; every frame's live tracklets must fit: more are cut and show as an
  *             overflow of rows wanted in no header -- callers pass t_max >= the widest table any rank can have)
@@ -275,8 +279,8 @@ int mvmc_pack_tracks(const double* out_params, const double* out_joints, const i
  *   gid    (n_chains_total_cap, id_cap) i32 out: global identity of (chain, local id), -1 where the chain has fewer identities
  *   match  (n_chains_total_cap, t_max) i32 out: slot of the previous chain's last frame matched to slot s of this chain's first, -1
  *   info   (4) i32 out: {chains, global identities, error word, pairs}; error word bit 0 = a message overflowed or a chain has more
- *          than id_cap ids, bit 1 = an assignment did not terminate (cannot happen with finite costs; a tracklet with a non-finite
- *          joint is given a cost beyond any max_dist, i.e. it matches nobody), bit 2 = some shard's void word is set (its compute
+ *          than id_cap ids, bit 1 = an assignment did not terminate (cannot happen: the costs are finite, a tracklet with a
+ *          non-finite joint is left out of the assignment -- it matches nobody and starts a new identity), bit 2 = some shard's void word is set (its compute
  *          step was void).  Non-zero = the result is void
  *   work   mvmc_stitch_work_words i32 device workspace;  n_chains_total_cap >= world * n_chains_cap; id_cap as packed */
 long long mvmc_stitch_work_words(int world, int t_max, int id_cap);

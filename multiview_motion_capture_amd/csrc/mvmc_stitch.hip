@@ -19,7 +19,6 @@ namespace {
 
 constexpr int ST_T = 16;        // max tracklet slots per frame (t_max <= 16)
 constexpr int ST_HDR = 8;       // header words
-constexpr double MVMC_STITCH_NO_MATCH = 1e30;
 
 constexpr int ST_LOCAL_HDR = 8; // words in front of the local section: {local roots, matched pairs, error word, void word, 0...}
 
@@ -114,7 +113,7 @@ pack_kernel(const double* __restrict__ params, const double* __restrict__ joints
 }
 
 // Optimal assignment of n rows to m >= n columns (Kuhn-Munkres with potentials, O(n^2 m)); col_of[i] = column of row i.
-// Costs must be finite (the caller replaces non-finite entries by a large constant): with a NaN row no column is ever selected and
+// Costs must be finite (the caller leaves tracklets with a non-finite joint out): with a NaN row no column is ever selected and
 // the augmenting loop would never end.  Every loop is bounded regardless (an augmenting path visits a column at most once, and the
 // back-trace has at most m links); false = the bound was hit, col_of is then not a valid assignment.
 template <typename Mat>
@@ -164,12 +163,25 @@ struct BoundScratch {
     double cost[ST_T][ST_T];
     int ip[ST_T], in[ST_T];
 };
+// the 54 float32 words of one tracklet's joints: no NaN, no infinity (exponent bits not all set).  No early exit: the loads do not
+// depend on each other and go out together.
+__device__ inline bool joints_finite(const uint32_t* __restrict__ j) {
+    uint32_t bad = 0u;
+#pragma unroll
+    for (int k = 0; k < 54; ++k) bad |= (uint32_t)((j[k] & 0x7f800000u) == 0x7f800000u);
+    return bad == 0u;
+}
 __device__ inline int match_boundary_wave(const uint32_t* __restrict__ pv, const uint32_t* __restrict__ nx, int T, int IC,
                                           double max_dist, BoundScratch& B, int32_t* __restrict__ match_row,
                                           int32_t* __restrict__ link) {
     const int lane = threadIdx.x & 63;
-    const bool lp = lane < T && (int32_t)pv[(size_t)lane * MVMC_BOUND_WORDS] >= 0;
-    const bool ln = lane < T && (int32_t)nx[(size_t)lane * MVMC_BOUND_WORDS] >= 0;
+    bool lp = lane < T && (int32_t)pv[(size_t)lane * MVMC_BOUND_WORDS] >= 0;
+    bool ln = lane < T && (int32_t)nx[(size_t)lane * MVMC_BOUND_WORDS] >= 0;
+    // a live tracklet with a non-finite joint is left out of the assignment: it matches nobody and its identity becomes a new root.
+    // (A large cost in its place would swallow the healthy pairs' costs in every sum it enters, and the assignment of the OTHERS
+    // would no longer be optimal.)  So every cost below is finite.
+    if (lp) lp = joints_finite(pv + (size_t)lane * MVMC_BOUND_WORDS + 1);
+    if (ln) ln = joints_finite(nx + (size_t)lane * MVMC_BOUND_WORDS + 1);
     const unsigned long long mp = __builtin_amdgcn_ballot_w64(lp), mn = __builtin_amdgcn_ballot_w64(ln);
     const int np = __popcll(mp), nn = __popcll(mn);
     if (lp) B.ip[__popcll(mp & ((1ull << lane) - 1ull))] = lane;
@@ -189,8 +201,7 @@ __device__ inline int match_boundary_wave(const uint32_t* __restrict__ pv, const
             const double dz = (double)__uint_as_float(a[3 * k + 2]) - (double)__uint_as_float(b[3 * k + 2]);
             sum += sqrt(dx * dx + dy * dy + dz * dz);
         }
-        // a tracklet with a non-finite joint matches nobody: a cost beyond any max_dist, and finite for the assignment
-        const double c = isfinite(sum) ? sum / 18.0 : MVMC_STITCH_NO_MATCH;
+        const double c = sum / 18.0;
         if (swap) B.cost[j][i] = c; else B.cost[i][j] = c;
     }
     __syncthreads();
@@ -417,7 +428,9 @@ extern "C" int mvmc_pack_tracks(const double* out_params, const double* out_join
                                 const int32_t* out_n_tracks, const int32_t* next_id, int n_frames, int chain_len, int t_tables,
                                 int t_max, int n_chains_cap, int row_cap, int id_cap, double max_dist, const uint32_t* void_words,
                                 int n_void_words, int32_t* work, void* message, mvmcStream_t stream) {
-    if (!out_params || !out_joints || !out_meta || !out_n_tracks || !next_id || !work || !message) return MVMC_ERR_ARG;
+    // (an empty shard has no tables: tensors of zero elements have null pointers, and nothing is read from them)
+    if (!work || !message) return MVMC_ERR_ARG;
+    if (n_frames > 0 && (!out_params || !out_joints || !out_meta || !out_n_tracks || !next_id)) return MVMC_ERR_ARG;
     if (n_frames < 0 || chain_len <= 0 || n_frames % chain_len || t_max <= 0 || t_max > ST_T || t_tables <= 0 || row_cap < 0)
         return MVMC_ERR_ARG;
     if (id_cap <= 0 || id_cap > 64 || n_void_words < 0 || n_void_words > 32 || (n_void_words && !void_words)) return MVMC_ERR_ARG;

@@ -79,23 +79,62 @@ def pack_np(params, joints, meta, n_tracks, next_id, chain_len, b_cap, row_cap, 
                 lgid[b, l] = n_roots
                 n_roots += 1
     vw = 0
-    if void_words is not None:
+    if void_words is not None and F > 0:      # (a shard without a frame has run no compute step: its message carries no void word)
         for i, w in enumerate(np.asarray(void_words).ravel()):
             vw |= (1 << i) if w else 0
-    lh[:4] = [n_roots, pairs, err, vw]
+    lh[:4] = [n_roots, pairs, err, int(np.array([vw], np.uint32).view(np.int32)[0])]      # (bit 31 of the void word: the sign bit)
     return msg
 
 
+def boundary_costs(joints_prev, joints_next):
+    """(n,18,3), (m,18,3) float32 -> (n,m) float64: the mean joint distance of every pair."""
+    a = np.asarray(joints_prev).astype(np.float64)[:, None]
+    b = np.asarray(joints_next).astype(np.float64)[None]
+    return np.sqrt(((a - b) ** 2).sum(axis=-1)).sum(axis=-1) / 18.0
+
+
+def finite_tracklets(joints):
+    """(n,18,3) -> indices of the tracklets without a non-finite coordinate."""
+    j = np.asarray(joints)
+    return np.nonzero(np.isfinite(j.reshape(len(j), 54)).all(axis=1))[0]
+
+
 def match_boundary(joints_prev, joints_next, max_dist):
-    """joints_* (n,18,3) float32 of the live tracklets -> list of (i_prev, i_next)."""
-    if len(joints_prev) == 0 or len(joints_next) == 0:
+    """joints_* (n,18,3) float32 of the live tracklets -> list of (i_prev, i_next).  A tracklet with a non-finite joint is left out of
+    the assignment (it stays live, matches nobody, its identity becomes a new root): a sentinel cost in its place -- 1e30 was the rule
+    once -- swallows the metre-sized costs of the healthy pairs in every sum it enters, and the solver can then no longer tell a good
+    pairing of the healthy tracklets from a bad one."""
+    fp, fn = finite_tracklets(joints_prev), finite_tracklets(joints_next)
+    if len(fp) == 0 or len(fn) == 0:
         return []
-    a = joints_prev.astype(np.float64)[:, None]
-    b = joints_next.astype(np.float64)[None]
-    cost = np.sqrt(((a - b) ** 2).sum(axis=-1)).sum(axis=-1) / 18.0
-    cost = np.where(np.isfinite(cost), cost, 1e30)      # a tracklet with a non-finite joint matches nobody (SciPy would raise)
+    cost = boundary_costs(np.asarray(joints_prev)[fp], np.asarray(joints_next)[fn])
     r, c = linear_sum_assignment(cost)
-    return [(int(i), int(j)) for i, j in zip(r, c) if cost[i, j] <= max_dist]
+    return [(int(fp[i]), int(fn[j])) for i, j in zip(r, c) if cost[i, j] <= max_dist]
+
+
+def match_boundary_brute(joints_prev, joints_next, max_dist):
+    """The assignment by enumeration, independent of SciPy and of any sentinel: every injection of the smaller side's finite tracklets
+    into the larger side's -> (minimum total cost, the pairs (i_prev, i_next) of one minimiser that are within max_dist).  For at most
+    7 finite tracklets a side (7! = 5040 injections)."""
+    import itertools
+    fp, fn = finite_tracklets(joints_prev), finite_tracklets(joints_next)
+    if len(fp) == 0 or len(fn) == 0:
+        return 0.0, []
+    if max(len(fp), len(fn)) > 7:
+        raise ValueError("match_boundary_brute: more than 7 finite tracklets on a side")
+    cost = boundary_costs(np.asarray(joints_prev)[fp], np.asarray(joints_next)[fn])
+    swap = len(fp) > len(fn)
+    c = cost.T if swap else cost                       # rows = the smaller side
+    best, best_cols = None, None
+    for cols in itertools.permutations(range(c.shape[1]), c.shape[0]):
+        tot = float(sum(c[i, j] for i, j in enumerate(cols)))
+        if best is None or tot < best:
+            best, best_cols = tot, cols
+    pairs = []
+    for i, j in enumerate(best_cols):
+        if c[i, j] <= max_dist:
+            pairs.append((int(fp[j]), int(fn[i])) if swap else (int(fp[i]), int(fn[j])))
+    return best, sorted(pairs)
 
 
 def stitch_np(messages, b_cap, t_max, row_cap, max_dist=0.5, id_cap=16):
@@ -118,7 +157,7 @@ def stitch_np(messages, b_cap, t_max, row_cap, max_dist=0.5, id_cap=16):
         if h[0] > 0 and m.size >= o_l + LOCAL_HDR:
             flag |= int(m[o_l + 2]) | (4 if m[o_l + 3] else 0)
         bounds = m[o_b:o_r].reshape(b_cap, 2, T, BOUND_WORDS)
-        for b in range(int(h[0])):
+        for b in range(min(int(h[0]), b_cap)):      # (a header that claims more chains than the message holds is flagged above)
             ids = bounds[b, :, :, 0]
             jo = bounds[b, :, :, 1:55].copy().view(np.float32).reshape(2, T, 18, 3)
             chains.append((int(m[HDR + b]), ids[0].copy(), jo[0], ids[1].copy(), jo[1]))
