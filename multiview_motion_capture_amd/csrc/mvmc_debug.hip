@@ -2,6 +2,7 @@
 // solver kernels on caller-supplied data so that tests can check them in isolation.
 #include "mvmc_common.h"
 #include "mvmc_eigh_tri.h"
+#include "mvmc_tri_w1.h"
 
 namespace {
 constexpr int NMAXE = 50, LDE = 51;
@@ -85,7 +86,63 @@ debug_trstep_kernel(const double* __restrict__ Bin, const double* __restrict__ r
     if (cyc_out && tid < 3) cyc_out[(size_t)b * 4 + tid] = (double)prof[tid];
     if (cyc_out && tid == 3) cyc_out[(size_t)b * 4 + 3] = (double)t_tri;
 }
+
+// eightri::tridiag_krylov_w1<N, DPP> + pack_reflectors on caller-given matrices, one wave per problem: everything the IK's model step
+// reads afterwards.  vec: six rows of 64 per problem (d, e, tau, v0 from LDS -- zeroed first, so the entries the routine leaves alone
+// compare -- then the per-lane scv, tauv); ret: {return value, ksteps}; pk: the (N - 2) / 2 packed reflector rows of every lane.
+template <int N, bool DPP>
+__global__ void __launch_bounds__(64)
+debug_tridiag_w1_kernel(const double* __restrict__ Ain, const double* __restrict__ gin, const int32_t* __restrict__ nact,
+                        double* __restrict__ vec, double* __restrict__ out4, int32_t* __restrict__ ret, double* __restrict__ pk_out) {
+    __shared__ double sv[4 * 64];
+    __shared__ __attribute__((aligned(16))) double xb[2 * 64];
+    __shared__ double o4[4];
+    const int b = blockIdx.x, lane = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sv[i * 64 + lane] = 0.0;
+    xb[lane] = 0.0; xb[64 + lane] = 0.0;
+    if (lane < 4) o4[lane] = 0.0;
+    __syncthreads();
+    const int n = min(max((int)nact[b], 2), N);
+    double a[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) a[i] = lane < N ? Ain[((size_t)b * N + i) * N + lane] : 0.0;
+    const double gj = lane < N ? gin[(size_t)b * N + lane] : 0.0;
+    double scv, tauv;
+    int ksteps;
+    const int kk = eightri::tridiag_krylov_w1<N, DPP>(a, gj, n, sv, sv + 64, sv + 128, sv + 192, xb, xb + 64, o4, scv, tauv, ksteps);
+    double pk[(N - 2) / 2];
+    eightri::pack_reflectors<N>(a, pk);
+    __syncthreads();
+    double* v = vec + (size_t)b * 6 * 64;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i * 64 + lane] = sv[i * 64 + lane];
+    v[4 * 64 + lane] = scv; v[5 * 64 + lane] = tauv;
+    if (lane < 4) out4[(size_t)b * 4 + lane] = o4[lane];
+    if (lane == 0) { ret[b * 2] = kk; ret[b * 2 + 1] = ksteps; }
+#pragma unroll
+    for (int z = 0; z < (N - 2) / 2; ++z) pk_out[((size_t)b * ((N - 2) / 2) + z) * 64 + lane] = pk[z];
+}
 }  // namespace
+
+// Not part of include/mvmc.h (tests/test_gpu_tridiag_dpp.py calls it by name): the single-wave tridiagonalisation with its row operands
+// by DPP (dpp != 0, the shipped form) or as LDS broadcasts, on n_problems symmetric N x N matrices A (row-major; zero beyond the
+// active size n_active[b]) and gradients g.  N = 30, 40 or 50; device pointers; vec (n_problems, 6, 64), out4 (n_problems, 4),
+// ret (n_problems, 2) int32, pk (n_problems, (N - 2) / 2, 64).
+extern "C" int mvmc_debug_tridiag_w1(const double* A, const double* g, const int32_t* n_active, int n_problems, int N, int dpp,
+                                     double* vec, double* out4, int32_t* ret, double* pk, mvmcStream_t stream) {
+    if (!A || !g || !n_active || !vec || !out4 || !ret || !pk || (N != 30 && N != 40 && N != 50)) return MVMC_ERR_ARG;
+    if (n_problems <= 0) return n_problems == 0 ? MVMC_OK : MVMC_ERR_ARG;
+#define MVMC_DBG_TRI(NN, D)                                                                                                          \
+    hipLaunchKernelGGL((debug_tridiag_w1_kernel<NN, D>), dim3(n_problems), dim3(64), 0, (hipStream_t)stream, A, g, n_active, vec, out4, \
+                       ret, pk)
+    if (N == 30) { if (dpp) MVMC_DBG_TRI(30, true); else MVMC_DBG_TRI(30, false); }
+    else if (N == 40) { if (dpp) MVMC_DBG_TRI(40, true); else MVMC_DBG_TRI(40, false); }
+    else { if (dpp) MVMC_DBG_TRI(50, true); else MVMC_DBG_TRI(50, false); }
+#undef MVMC_DBG_TRI
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
+}
 
 extern "C" int mvmc_debug_eigh(const double* A, const double* g, int n_problems, int n, double* lam, double* Vt,
                                int32_t* k0, double* phase_cycles, mvmcStream_t stream) {

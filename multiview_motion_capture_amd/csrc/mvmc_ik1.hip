@@ -439,7 +439,9 @@ __device__ __noinline__ void ik1_model_step(Ik1Shared& S, const Ik1Tables& T, in
     if (lane == 0) { S.sc[0] = gg; S.sc[1] = ginf; }
     if (DBG) hh[MVMC_IK_DBG_G + lane] = on ? gj : 0.0;
     M1STAMP(4)
-    if (ginf < gtol || !budget_left) { *mode_out = 0; return; }
+    // (budget_left is wave-uniform but arrives in a vector register; as a scalar the test is a scalar branch, and the tridiagonalisation's
+    // DPP row operands are read with no execution-mask region around them: tools/isa_exec_dpp.py)
+    if (ginf < gtol || !uni((int)budget_left)) { *mode_out = 0; return; }
     double scv, tauv;
     int ksteps;
     const int kk = uni(eightri::tridiag_krylov_w1<N>(a, gj, na, S.sv + SV_D, S.sv + SV_E, S.sv + SV_TAU, S.sv + SV_V0, S.tmp, S.tmp + 64,
@@ -655,7 +657,9 @@ __device__ __noinline__ void ik1_model_step_r(Ik1Shared& S, const Ik1Tables& T, 
     MVMC_WAVE_SYNC();
     if (lane == 0) { S.sc[0] = gg; S.sc[1] = ginf; }
     M1STAMP(4)
-    if (ginf < gtol || !budget_left) { *mode_out = 0; return; }
+    // (budget_left is wave-uniform but arrives in a vector register; as a scalar the test is a scalar branch, and the tridiagonalisation's
+    // DPP row operands are read with no execution-mask region around them: tools/isa_exec_dpp.py)
+    if (ginf < gtol || !uni((int)budget_left)) { *mode_out = 0; return; }
     double scv, tauv;
     int ksteps;
     const int kk = uni(eightri::tridiag_krylov_w1<N>(a, gj, na, S.sv + SV_D, S.sv + SV_E, S.sv + SV_TAU, S.sv + SV_V0, S.tmp, S.tmp + 64,

@@ -1,8 +1,9 @@
 // The Krylov tridiagonalisation of mvmc_eigh_tri.h on ONE wave (mvmc_ik1.hip: one wave per solve, no workgroup
 // barriers).  Lane l owns column l of the symmetric matrix and keeps all N rows in registers: a[i] = M[i][l].
 // Per step: the reflector of row k (one wave reduction), then p = tau M v and the rank-2 update with the row-side
-// values v_i, w_i read back from LDS as broadcasts (two values per ds_read_b128) -- three FMAs per live row and
-// lane and no cross-lane VALU traffic in the inner loops.  Rows <= k are dead (never read again; their diagonal
+// values v_i, w_i taken as DPP row broadcasts from registers that hold them replicated per row of 16 lanes (one
+// ds_read_b64 per 16 rows; DPP = false: read back from LDS as broadcasts, two values per ds_read_b128) -- three
+// multiply-adds per live row and lane.  Rows <= k are dead (never read again; their diagonal
 // entry survives because v vanishes there) and are skipped in chunks.  The Householder vectors STAY IN THE MATRIX
 // REGISTERS: row k is dead after step k and is left untouched from then on (w is forced to zero on the lanes <= k, which
 // only ever fed dead entries), so v_k = {1 at lane k+1, a[k] * sc_k beyond} can be re-formed from a[k] and the scalar
@@ -19,6 +20,55 @@ namespace eightri {
 #define MVMC_ROWS50(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) \
     X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32) X(33) X(34) X(35) X(36) X(37)  \
     X(38) X(39) X(40) X(41) X(42) X(43) X(44) X(45) X(46) X(47) X(48) X(49)
+
+// ---- row operands by DPP: acc += x_i * t with x_i = x of lane i, for a compile-time row i ----
+// X[r] holds x of lane 16 r + (lane & 15) -- every row of 16 lanes carries the sixteen values of row group r -- and the fused
+// v_fmac_f64_dpp takes lane i % 16 of the reading lane's own row of 16 (row_newbcast): one instruction where the LDS form has a
+// broadcast read and an FMA; same operands, same operation, same rounding.  It issues at the plain v_fmac_f64's rate within 3 - 6 %
+// (tools/dpp_f64_rate.hip, profiles/r07_dpp_f64_rate.txt; FMAs fed by ds_read_b128 broadcasts: half of it, the CU's LDS pipe being shared
+// by all its waves).  A disabled source lane returns no data: the execution mask is all ones wherever these run (one wave per solve,
+// wave-uniform control flow only).  Ten rows (one chunk) per statement; the compiler does not look into it for hazards: s_nop 1 in
+// front covers a VALU write (a copy) of a DPP source just before it, the closing s_nop a DPP or lane read of a result just behind.
+#define MVMC_DPP_ROWS10(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+#define MVMC_DPP_TAIL " row_mask:0xf bank_mask:0xf\n\t"
+// p0 += a[C + j] * v_{C + j} (j even), p1 += ... (j odd), in row order
+template <int N, int C>
+__device__ __forceinline__ void dpp_product10(double& p0, double& p1, const double (&a)[N], const double (&V)[(N + 15) / 16]) {
+#define MVMC_A(j) , "v"(a[C + j])
+#define MVMC_V(j) , "v"(V[(C + j) / 16])
+#define MVMC_I(j) , "n"((C + j) % 16)
+    // operands: 0, 1 the sums; 2 .. 11 the matrix rows; 12 .. 21 each row's group register; 22 .. 31 each row's lane in the group
+    asm volatile("s_nop 1\n\t"
+                 "v_fmac_f64_dpp %0, %12, %2 row_newbcast:%22" MVMC_DPP_TAIL "v_fmac_f64_dpp %1, %13, %3 row_newbcast:%23" MVMC_DPP_TAIL
+                 "v_fmac_f64_dpp %0, %14, %4 row_newbcast:%24" MVMC_DPP_TAIL "v_fmac_f64_dpp %1, %15, %5 row_newbcast:%25" MVMC_DPP_TAIL
+                 "v_fmac_f64_dpp %0, %16, %6 row_newbcast:%26" MVMC_DPP_TAIL "v_fmac_f64_dpp %1, %17, %7 row_newbcast:%27" MVMC_DPP_TAIL
+                 "v_fmac_f64_dpp %0, %18, %8 row_newbcast:%28" MVMC_DPP_TAIL "v_fmac_f64_dpp %1, %19, %9 row_newbcast:%29" MVMC_DPP_TAIL
+                 "v_fmac_f64_dpp %0, %20, %10 row_newbcast:%30" MVMC_DPP_TAIL "v_fmac_f64_dpp %1, %21, %11 row_newbcast:%31" MVMC_DPP_TAIL
+                 "s_nop 0"
+                 : "+v"(p0), "+v"(p1)
+                 : "v"(a[C]) MVMC_A(1) MVMC_A(2) MVMC_A(3) MVMC_A(4) MVMC_A(5) MVMC_A(6) MVMC_A(7) MVMC_A(8) MVMC_A(9)
+                   MVMC_DPP_ROWS10(MVMC_V) MVMC_DPP_ROWS10(MVMC_I));
+}
+// a[C + j] = fma(-w_{C + j}, vj, fma(-v_{C + j}, wj, a[C + j])): the ten inner FMAs, then the ten outer ones
+template <int N, int C>
+__device__ __forceinline__ void dpp_rank2_10(double (&a)[N], const double (&V)[(N + 15) / 16], const double (&W)[(N + 15) / 16], double vj, double wj) {
+#define MVMC_U(j) "v_fmac_f64_dpp %" #j ", -%1" #j ", %40 row_newbcast:%3" #j MVMC_DPP_TAIL
+#define MVMC_W(j) "v_fmac_f64_dpp %" #j ", -%2" #j ", %41 row_newbcast:%3" #j MVMC_DPP_TAIL
+#define MVMC_AO(j) , "+v"(a[C + j])
+#define MVMC_WG(j) , "v"(W[(C + j) / 16])
+    // operands: 0 .. 9 the matrix rows; 10 .. 19 / 20 .. 29 each row's group register of v / w; 30 .. 39 its lane in the group; 40 wj, 41 vj
+    asm volatile("s_nop 1\n\t" MVMC_DPP_ROWS10(MVMC_U) MVMC_DPP_ROWS10(MVMC_W) "s_nop 0"
+                 : "+v"(a[C]) MVMC_AO(1) MVMC_AO(2) MVMC_AO(3) MVMC_AO(4) MVMC_AO(5) MVMC_AO(6) MVMC_AO(7) MVMC_AO(8) MVMC_AO(9)
+                 : "v"(V[C / 16]) MVMC_V(1) MVMC_V(2) MVMC_V(3) MVMC_V(4) MVMC_V(5) MVMC_V(6) MVMC_V(7) MVMC_V(8) MVMC_V(9)
+                   MVMC_DPP_ROWS10(MVMC_WG) MVMC_DPP_ROWS10(MVMC_I), "v"(wj), "v"(vj));
+#undef MVMC_U
+#undef MVMC_W
+#undef MVMC_AO
+#undef MVMC_WG
+#undef MVMC_A
+#undef MVMC_V
+#undef MVMC_I
+}
 
 // a[k] for a wave-uniform k (register arrays need static indices)
 template <int N>
@@ -40,7 +90,9 @@ __device__ __forceinline__ double row_of(const double (&a)[N], int k) {
 // tau[0..kk-1) valid; d[kk] is the first diagonal entry of the null block), n if no sub-diagonal collapses, and -1 if
 // one collapses in front of a block that is not null -- the tridiagonalisation is then complete (all n rows) and
 // meant for tri_eigh_w1.
-template <int N>
+// DPP = false keeps the row operands as LDS broadcasts: the same operations in the same order, bit for bit (the A/B partner, and the
+// reference of tests/test_gpu_tridiag_dpp.py).  All 64 lanes must be active at the call in either form.
+template <int N, bool DPP = true>
 __device__ __forceinline__ int tridiag_krylov_w1(double (&a)[N], double gj, int n, double* d, double* e, double* tau, double* v0,
                                                  double* vb, double* pb, double* out4, double& scv, double& tauv, int& ksteps,
                                                  long long* tprof = nullptr) {
@@ -77,18 +129,21 @@ __device__ __forceinline__ int tridiag_krylov_w1(double (&a)[N], double gj, int 
     // of that chain.  Bit-identical, but the preloaded operands (40 registers in the 40-row model) and the second set of step scalars do
     // not fit: 63 - 73 scratch stores in the model functions, IK 34.5 -> 84 M cycles per chain; without the preload the 50-row model
     // still spills (36 stores) and nothing is hidden.  Dropped.
-    // Batch sizes: what a step waits for is the LDS round trip of the row-side broadcasts (> 100 cycles each; the FMAs of a row are 4 - 8),
-    // so the 40-row model takes as many rows per round trip as its registers hold.  Tried and dropped: a software pipeline over 5-row
-    // chunks with two or three chunks of operands in flight (loads of chunk c + 2 in front of the FMAs of chunk c) -- more round trips
-    // and branches than it hides, IK 37.9 -> 40.1 M cycles per chain, and the 50-row model spilled v_j / w_j.
+    // Row operands (DPP form): a step makes ONE LDS round trip for v and one for w -- (N + 15) / 16 ds_read_b64 each, lane l reading
+    // element 16 r + (l & 15) -- where the LDS form makes one per batch of broadcasts, and holds 2 (N + 15) / 16 operand registers where
+    // that one holds a batch's 2 HB + HB (which is what the batch sizes below bound).  The chunks of CH rows remain as the unit of the
+    // wave-uniform skip of dead rows.  Measured on the chain kernel, config 4, against the LDS form (bit-identical; same box, interleaved,
+    // profiles/r07_tridiag_dpp_ab.txt): 551 k -> 572 k frames/s, IK 36.2 -> 34.3 M cycles per chain; per launch the LDS-busy cycles
+    // (SQ_LDS_IDX_ACTIVE) 6.58 G -> 5.06 G, the cycles waves wait on LDS (SQ_WAIT_INST_LDS) 1.58 G -> 0.93 G, LDS instructions
+    // 1.38 G -> 1.01 G, VALU instructions 7.92 G -> 7.96 G (profiles/r07_tridiag_dpp_counters.txt).
+    // LDS form only -- batch sizes: what a step waits for is the LDS round trip of the row-side broadcasts (> 100 cycles each), so the
+    // 40-row model takes as many rows per round trip as its registers hold (HB pairs of rows per batch of the update, CHB rows per round
+    // trip of the product, MVMC_TRI_PB pairs per batch inside one where the 128-register build has no room for ten operands).
 #ifdef MVMC_TRI_HB
     constexpr int HB = MVMC_TRI_HB;
 #else
-    constexpr int HB = N <= 40 ? 5 : 3;   // pairs of rows per batch of the rank-2 update
+    constexpr int HB = N <= 40 ? 5 : 3;
 #endif
-    // (CHB: rows per round trip of the product.  Twenty for the 40-row model measured best while a wave's latency was the limit; with the
-    // chip's VALU and LDS pipes as the limit -- two launches in flight, every slot taken -- the ten dead rows a 20-row chunk drags along on
-    // average cost more than the round trip they save: 454.0 k -> 456.1 k frames/s, bit-identical)
 #ifdef MVMC_TRI_CHB
     constexpr int CH = 10, CHB = MVMC_TRI_CHB;
 #else
@@ -101,31 +156,49 @@ __device__ __forceinline__ int tridiag_krylov_w1(double (&a)[N], double gj, int 
 #else
 #define TRSTAMP(k)
 #endif
-    auto rank2 = [&](int k, double vj, double wj) {
+    constexpr int NG = (N + 15) / 16;   // row groups of 16
+    static_assert(!DPP || CH == 10, "dpp_product10 / dpp_rank2_10 take one chunk");
+    // X[r] <- x[16 r + (lane & 15)] (x: 64 doubles of LDS)
+    auto replicated = [&](const double* x, double (&X)[NG]) {
 #pragma unroll
-        for (int c = 0; c < N; c += CH)
-            if (c + CH - 1 > k) {
-                // two batches of loads per chunk (6 + 4 rows): ten 16-byte broadcasts in flight at once would push the
-                // N = 50 instance over its register budget
+        for (int r = 0; r < NG; ++r) X[r] = x[16 * r + (lane & 15)];
+    };
+    // (the live chunks of a step, each behind its wave-uniform test; C is a template argument of the chunk's statement)
+#define MVMC_TRI_CHUNKS(k, F) MVMC_TRI_CHUNK(k, F, 0) MVMC_TRI_CHUNK(k, F, 10) MVMC_TRI_CHUNK(k, F, 20) MVMC_TRI_CHUNK(k, F, 30) MVMC_TRI_CHUNK(k, F, 40)
+#define MVMC_TRI_CHUNK(k, F, C) if constexpr (C < N) { if (C + CH - 1 > k) { F(C); } }
+    auto rank2 = [&](int k, double vj, double wj, const double (&V)[NG]) {
+        if constexpr (DPP) {
+            double W[NG];
+            replicated(pb, W);
+#define MVMC_TRI_UPD(C) dpp_rank2_10<N, C>(a, V, W, vj, wj)
+            MVMC_TRI_CHUNKS(k, MVMC_TRI_UPD)
+#undef MVMC_TRI_UPD
+        } else {
 #pragma unroll
-                for (int h0 = 0; h0 < CH / 2; h0 += HB) {
-                    double2 v2[HB], w2[HB];
+            for (int c = 0; c < N; c += CH)
+                if (c + CH - 1 > k) {
+                    // two batches of loads per chunk (6 + 4 rows): ten 16-byte broadcasts in flight at once would push the
+                    // N = 50 instance over its register budget
 #pragma unroll
-                    for (int u = 0; u < HB; ++u)
-                        if (h0 + u < CH / 2) {
-                            v2[u] = *reinterpret_cast<const double2*>(&vb[c + 2 * (h0 + u)]);
-                            w2[u] = *reinterpret_cast<const double2*>(&pb[c + 2 * (h0 + u)]);
-                        }
+                    for (int h0 = 0; h0 < CH / 2; h0 += HB) {
+                        double2 v2[HB], w2[HB];
 #pragma unroll
-                    for (int u = 0; u < HB; ++u)
-                        if (h0 + u < CH / 2) {
-                            const int i = c + 2 * (h0 + u);
-                            a[i] = fma(-w2[u].x, vj, fma(-v2[u].x, wj, a[i]));
-                            a[i + 1] = fma(-w2[u].y, vj, fma(-v2[u].y, wj, a[i + 1]));
-                        }
-                    __builtin_amdgcn_sched_barrier(0);
+                        for (int u = 0; u < HB; ++u)
+                            if (h0 + u < CH / 2) {
+                                v2[u] = *reinterpret_cast<const double2*>(&vb[c + 2 * (h0 + u)]);
+                                w2[u] = *reinterpret_cast<const double2*>(&pb[c + 2 * (h0 + u)]);
+                            }
+#pragma unroll
+                        for (int u = 0; u < HB; ++u)
+                            if (h0 + u < CH / 2) {
+                                const int i = c + 2 * (h0 + u);
+                                a[i] = fma(-w2[u].x, vj, fma(-v2[u].x, wj, a[i]));
+                                a[i + 1] = fma(-w2[u].y, vj, fma(-v2[u].y, wj, a[i + 1]));
+                            }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
-            }
+        }
         MVMC_WAVE_SYNC();  // vb / pb are rewritten by the next step
         TRSTAMP(6)   // rank-2 update
     };
@@ -134,31 +207,39 @@ __device__ __forceinline__ int tridiag_krylov_w1(double (&a)[N], double gj, int 
         vb[lane] = vj;
         MVMC_WAVE_SYNC();
         double p0 = 0.0, p1 = 0.0;
-        // (the product takes CHB rows per LDS round trip)
+        double V[NG];
+        if constexpr (DPP) {
+            replicated(vb, V);
+#define MVMC_TRI_PROD(C) dpp_product10<N, C>(p0, p1, a, V)
+            MVMC_TRI_CHUNKS(k, MVMC_TRI_PROD)
+#undef MVMC_TRI_PROD
+        } else {
+            // (the product takes CHB rows per LDS round trip)
 #pragma unroll
-        for (int c = 0; c < N; c += CHB)
-            if (c + CHB - 1 > k) {
+            for (int c = 0; c < N; c += CHB)
+                if (c + CHB - 1 > k) {
 #ifdef MVMC_TRI_PB   // (pairs of rows per batch of loads inside a chunk: the 128-register build has no room for a chunk's ten operands at once)
-                constexpr int PB = MVMC_TRI_PB;
+                    constexpr int PB = MVMC_TRI_PB;
 #pragma unroll
-                for (int u0 = 0; u0 < CHB / 2; u0 += PB) {
-                    double2 v2[PB];
+                    for (int u0 = 0; u0 < CHB / 2; u0 += PB) {
+                        double2 v2[PB];
 #pragma unroll
-                    for (int u = 0; u < PB; ++u)
-                        if (u0 + u < CHB / 2) v2[u] = *reinterpret_cast<const double2*>(&vb[c + 2 * (u0 + u)]);
+                        for (int u = 0; u < PB; ++u)
+                            if (u0 + u < CHB / 2) v2[u] = *reinterpret_cast<const double2*>(&vb[c + 2 * (u0 + u)]);
 #pragma unroll
-                    for (int u = 0; u < PB; ++u)
-                        if (u0 + u < CHB / 2) { p0 += a[c + 2 * (u0 + u)] * v2[u].x; p1 += a[c + 2 * (u0 + u) + 1] * v2[u].y; }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                        for (int u = 0; u < PB; ++u)
+                            if (u0 + u < CHB / 2) { p0 += a[c + 2 * (u0 + u)] * v2[u].x; p1 += a[c + 2 * (u0 + u) + 1] * v2[u].y; }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
 #else
-                double2 v2[CHB / 2];
+                    double2 v2[CHB / 2];
 #pragma unroll
-                for (int u = 0; u < CHB / 2; ++u) v2[u] = *reinterpret_cast<const double2*>(&vb[c + 2 * u]);
+                    for (int u = 0; u < CHB / 2; ++u) v2[u] = *reinterpret_cast<const double2*>(&vb[c + 2 * u]);
 #pragma unroll
-                for (int u = 0; u < CHB / 2; ++u) { p0 += a[c + 2 * u] * v2[u].x; p1 += a[c + 2 * u + 1] * v2[u].y; }
+                    for (int u = 0; u < CHB / 2; ++u) { p0 += a[c + 2 * u] * v2[u].x; p1 += a[c + 2 * u + 1] * v2[u].y; }
 #endif
-            }
+                }
+        }
         TRSTAMP(3)   // v broadcast + matrix-vector product
         const double p = tk * (p0 + p1);
         const double h = 0.5 * tk * wave_sum_dpp(p * vj);
@@ -166,8 +247,10 @@ __device__ __forceinline__ int tridiag_krylov_w1(double (&a)[N], double gj, int 
         pb[lane] = wj;
         MVMC_WAVE_SYNC();
         TRSTAMP(4)   // h reduction, w, w broadcast
-        rank2(k, vj, wj);
+        rank2(k, vj, wj, V);
     };
+#undef MVMC_TRI_CHUNKS
+#undef MVMC_TRI_CHUNK
     double anorm;
     {
         double cs = 0.0;
