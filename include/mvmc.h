@@ -618,6 +618,35 @@ int mvmc_smooth_window(const mvmcSkeleton* skel_host, const double* kps17, int n
                        double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
                        double* work, long long work_doubles, mvmcStream_t stream);
 
+/* The per-joint covariance of the rows a tick emits (csrc/mvmc_smooth_window_cov.hip; live_smoothing.py: covariance="joints"): ONE
+ * launch after mvmc_smooth_window[_robust], one 256-lane workgroup per item, that only READS the state above (rows, members, count, the
+ * keypoint ring, Pmats).  An item (MVMC_SMOOTH_COV_ITEM_INTS i32): {slot, rig, emit_row, work_row}; emit_row counts from the
+ * identity's first row.  With n = count[slot] rows the window is the one mvmc_smooth_window solved: the last m = min(window, n) rows
+ * free, the h = min(2, n - m) rows before them frozen.  A_w = the free rows' data blocks at their values (with a loss the weighted ones)
+ * + the exact Hessian of every prior term that touches a free row, the history held fixed: the matrix the window's LM step factors.
+ * The launch factors A_w + mu diag A_w with the smoothers' sweep (mu as mvmc_smooth_cov takes it: without history A_w alone is
+ * singular, and at mu = 0 its last pivot is a rounding residue of either sign, so status 1 is not guaranteed there) and runs
+ * mvmc_smooth_cov's backward recursion from the last free row down to the emitted one, e = emit_row - (n - m): Sigma_ee is the
+ * covariance of the emitted row CONDITIONAL on the frozen history (and on the rig, the lengths and the view selection).  From it:
+ *   jcov (n_items, 18, 6), pvar (n_items, MVMC_SMOOTH_K) f64 out: as mvmc_smooth_cov's, of the emitted row alone, unit variance;
+ *   cinfo (n_items, MVMC_SMOOTH_COV_INFO_DOUBLES) f64 out: {status, E_data of the free rows, n_res, edof, m, e, 0, 0}.  full != 0: the
+ *        recursion goes on down to free row 0 and n_res, edof = sum_t tr(Sigma_tt H_t) are those of all free rows (mvmc_smooth_cov's
+ *        definitions); full == 0: it stops at row e, n_res and edof are NaN, jcov and pvar have the same bits.
+ *        status 0: solved.  1: a pivot of the factor is not positive and finite, NaN outputs.  2: n < 2, nothing was solved, NaN.
+ *        6: the item is malformed (slot or rig out of range, n < 1, emit_row not a free row, work_row < 0 or work_row + window >
+ *        n_items * window), NaN outputs; it is never followed out of bounds and its neighbours are not touched.
+ * loss, loss_px: MVMC_SMOOTH_LOSS_* and its scale under mvmc_smooth_window_robust's rule (MVMC_SMOOTH_LOSS_NONE: loss_px is not read).
+ * work: at least mvmc_smooth_window_cov_work_doubles(n_items, window) doubles, overwritten.  Every sum runs in a fixed order inside the
+ * item's own workgroup: the same bits alone, among other items and from run to run.  Argument errors return before any HIP call;
+ * nothing is allocated or synchronised inside. */
+#define MVMC_SMOOTH_COV_ITEM_INTS 4
+long long mvmc_smooth_window_cov_work_doubles(int n_items, int window);   /* -1: bad arguments */
+int mvmc_smooth_window_cov(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats, int n_rigs,
+                           const int32_t* items, int n_items, const double* rows, const int32_t* members, const int32_t* count,
+                           int n_slots, int window, double root_vel, double root_acc, double ang_vel, double ang_acc, double mu,
+                           int full, int loss, double loss_px, double* work, long long work_doubles, double* jcov, double* pvar,
+                           double* cinfo, mvmcStream_t stream);
+
 /* ---- a robust loss on the smoothers' keypoint residuals (restated in tests/smooth_robust_np.py).  For one (selected view, observed
  * joint) pair of a row: score s, plain pixel residual (ru, rv) = proj(X_k) - obs, e^2 = ru^2 + rv^2, delta = loss_px > 0 (pixels),
  *   MVMC_SMOOTH_LOSS_HUBER   rho = 1/2 e^2, w = 1 for e <= delta; otherwise rho = delta (e - 1/2 delta), w = delta / e

@@ -26,6 +26,7 @@ BODY_INFO_DOUBLES, BODY_WORK_DOUBLES = 16, 270
 SMOOTH_K, SMOOTH_BLOCK_DOUBLES, SMOOTH_WORK_DOUBLES, SMOOTH_INFO_DOUBLES, SMOOTH_MAX_VIEWS = 39, 820, 3940, 32, 64
 SMOOTH_COV_INFO_DOUBLES, SMOOTH_JOINTS = 8, 18
 SMOOTH_WIN_MAX, SMOOTH_WIN_RING, SMOOTH_WIN_ITEM_INTS, SMOOTH_WIN_INFO_DOUBLES = 32, 66, 8, 16
+SMOOTH_COV_ITEM_INTS = 4                                                                          # MVMC_SMOOTH_COV_ITEM_INTS
 SMOOTH_LOSS_NONE, SMOOTH_LOSS_HUBER, SMOOTH_LOSS_CAUCHY = 0, 1, 2                                     # MVMC_SMOOTH_LOSS_*
 SMOOTH_FOOT_L, SMOOTH_FOOT_R = 3, 6                                                                   # MVMC_SMOOTH_FOOT_*: the ankles
 RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
@@ -45,6 +46,7 @@ SYMBOLS = (
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_cov", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
     "mvmc_smooth_blocks_robust", "mvmc_smooth_obs_weights", "mvmc_smooth_window_robust",
     "mvmc_smooth_blocks_contact", "mvmc_smooth_contact_anchors",
+    "mvmc_smooth_window_cov_work_doubles", "mvmc_smooth_window_cov",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
     "mvmc_rig_accumulate_robust", "mvmc_rig_step_robust", "mvmc_rig_weights",
     "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
@@ -169,6 +171,9 @@ def load():
                                       f64, f64, vp, vp, C.c_longlong, i32, f64, vp],
         "mvmc_smooth_blocks_contact": [SK, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, f64, vp, vp, f64, vp],
         "mvmc_smooth_contact_anchors": [vp, vp, i32, i32, i32, f64, i32, i32, C.POINTER(C.c_double), f64, vp, vp, vp, vp],
+        "mvmc_smooth_window_cov_work_doubles": [i32, i32],
+        "mvmc_smooth_window_cov": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i32, i32, f64, vp,
+                                   C.c_longlong, vp, vp, vp, vp],
         "mvmc_relink_work_words": [i32],
         "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
         "mvmc_rig_part_doubles": [i32],
@@ -190,7 +195,8 @@ def load():
         "mvmc_pair_refit": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
-                "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong,
+                "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong,
+                "mvmc_smooth_window_cov_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong,
                 "mvmc_rig_part_doubles": C.c_longlong, "mvmc_rig_red_doubles": C.c_longlong,
                 "mvmc_rig_part_doubles_intr": C.c_longlong, "mvmc_rig_red_doubles_intr": C.c_longlong}
     # A build of another revision loaded through MVMC_LIB_PATH for a same-box A/B comparison (tools/lib_diff.py, tools/*_ab.sh) may

@@ -1,0 +1,157 @@
+// Per-joint covariance of the pose a live session emits (multiview_motion_capture_amd/live_smoothing.py: covariance="joints";
+// restated in tests/live_smooth_cov_np.py): ONE launch per tick after mvmc_smooth_window[_robust], one 256-lane workgroup per item =
+// one identity that emits a row this tick.  The launch only reads the device-resident state (rows, members, count, the keypoint ring,
+// Pmats).  With n rows the window is the window kernel's: the last m = min(W, n) rows free, the h = min(2, n - m) rows before them
+// frozen.  A_w = the free rows' data blocks at their final values (sm_row_block<LOSS>: the weighted ones under a loss) + the exact
+// Hessian of every prior term whose stencil touches a free row, the history held fixed: the matrix the window's LM step factors.  The
+// launch inverts A_w + mu diag A_w (A_w alone is singular, csrc/mvmc_smooth_cov.hip) and keeps Sigma_ee of the emitted free row e: the
+// covariance CONDITIONAL on the frozen history, the rig, the lengths and the view selection -- what the fixed-lag solve itself assumes.
+//   copy       the h + m rows from the ring into the item's workspace (the ring wraps; the sweep and the prior's stencils index
+//              rows linearly);
+//   blocks     the m free rows' blocks at them, a row per wave at a time on the four waves (the window kernel's eval_blocks);
+//   factor     sm_sweep (mvmc_smooth_sweep.h, unchanged) with h and nw: the history enters the diagonal's coefficients only;
+//   recursion  mvmc_smooth_cov_rec.h (shared with csrc/mvmc_smooth_cov.hip, whose head comment describes the phases and the wave
+//              assignment: products on all four waves, the three right-solves on waves 0-2, the row's FK / D_K / residual count on
+//              wave 3) from row m - 1 down to e; with full != 0 down to row 0, accumulating edof = sum_t tr(Sigma_tt H_t) and n_res
+//              over all free rows.  Only row e does the D Sigma D^T products and writes.
+// The recursion below row e is only needed for edof: a caller who knows the noise scale passes full = 0 and pays lag + 1 of m rows.
+// LDS: the blocks phase (four SmBlkLds, one per wave, 143,760 bytes) and the factor + recursion phase (ScLds, 138,808 bytes) do not
+// overlap in time and share a union, as SwLds does in csrc/mvmc_smooth_window.hip; 143,760 of the 163,840 bytes a workgroup may
+// have on gfx950, so one workgroup per CU: a tick has at most a few dozen items and the launch is latency bound, not occupancy bound.
+// Workspace per item: (MVMC_SMOOTH_WIN_MAX + 2) x 68 doubles for the rows, and per window row a block (SM_BLK) and a factor row (SM_WORK).
+// Every sum runs in a fixed order inside the identity's own lanes, no atomics: an identity's numbers depend on nothing else in the
+// launch.  A malformed item gets status 6 and NaN outputs and is never followed out of bounds.
+#define MVMC_DEVICE_ONLY
+#include "mvmc_common.h"
+#include "mvmc_track.hip"
+#include "mvmc_ik1.hip"
+#undef MVMC_DEVICE_ONLY
+
+namespace {
+
+#include "mvmc_smooth_row.h"
+#include "mvmc_smooth_sweep.h"
+#include "mvmc_smooth_cov_rec.h"
+
+constexpr int WC_MAXW = MVMC_SMOOTH_WIN_MAX;
+constexpr int WC_RING = MVMC_SMOOTH_WIN_RING;
+constexpr int WC_ITEM = MVMC_SMOOTH_COV_ITEM_INTS;
+constexpr int WC_X = (WC_MAXW + 2) * 68;                  // the item's rows: history + window
+
+union WcLds {
+    SmBlkLds blk[4];          // the blocks phase: one row block per wave
+    ScLds sc;                 // the sweep and the recursion (the phases do not overlap in time)
+};
+static_assert(sizeof(WcLds) <= 160 * 1024, "LDS of one workgroup");
+
+template <int LOSS>
+__global__ void __launch_bounds__(SM_THREADS) smooth_window_cov_kernel(
+    Ik1Tables T, const double* __restrict__ kps17, const double* __restrict__ Pmats, int C, int Pmax, int n_rigs,
+    const int32_t* __restrict__ items, const double* __restrict__ rows, const int32_t* __restrict__ members,
+    const int32_t* __restrict__ count, int n_slots, int W, double root_vel, double root_acc, double ang_vel, double ang_acc, double mu,
+    int full, double* __restrict__ work, int work_rows, double* __restrict__ jcov, double* __restrict__ pvar, double* __restrict__ cinfo,
+    double loss_px) {
+    __shared__ WcLds LL;
+    const int tid = threadIdx.x, wave = tid >> 6, it = blockIdx.x;
+    const int32_t* im = items + (size_t)it * WC_ITEM;
+    const int slot = uni((int)im[0]), rig = uni((int)im[1]), emit = uni((int)im[2]), row_lo = uni((int)im[3]);
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+    double* ci = cinfo + (size_t)it * SC_INFO;
+    double* jc = jcov + (size_t)it * (SC_J * 6);
+    double* pv = pvar + (size_t)it * SK;
+    // NaN outputs and the status word {status, E_data, n_res, edof, m, e, 0, 0} of an item that is not solved
+    auto unsolved = [&](double status, double Ed, double mm, double ee) {
+        for (int i = tid; i < SC_J * 6; i += SM_THREADS) jc[i] = qnan;
+        if (tid < SK) pv[tid] = qnan;
+        if (tid < SC_INFO) ci[tid] = tid == 0 ? status : tid == 1 ? Ed : tid < 4 ? qnan : tid == 4 ? mm : tid == 5 ? ee : 0.0;
+    };
+    // (a malformed item is never followed out of bounds: status 6; the checks are the window kernel's)
+    if (slot < 0 || slot >= n_slots || rig < 0 || rig >= n_rigs || row_lo < 0 || row_lo > work_rows - W) {
+        unsolved(6.0, qnan, 0.0, 0.0);
+        return;
+    }
+    const int n = uni((int)count[slot * 2]);
+    if (n < 1) {
+        unsolved(6.0, qnan, 0.0, 0.0);
+        return;
+    }
+    const int m = n < W ? n : W, h = (n - m) < 2 ? (n - m) : 2, nw = h + m, lo = n - nw;
+    if (emit < n - m || emit >= n) {                          // the emitted row must be a free row
+        unsolved(6.0, qnan, 0.0, 0.0);
+        return;
+    }
+    const int e = emit - (n - m);                             // its index among the free rows
+    if (n < 2) {   // one row: nothing was solved
+        unsolved(2.0, 0.0, (double)m, (double)e);
+        return;
+    }
+    const double* ring = rows + (size_t)slot * WC_RING * 68;
+    const int32_t* mring = members + (size_t)slot * WC_RING * C;
+    double* x = work + (size_t)it * WC_X;
+    double* bk = work + (size_t)gridDim.x * WC_X + (size_t)row_lo * SM_BLK;                                  // this item's W blocks
+    double* wk = work + (size_t)gridDim.x * WC_X + (size_t)work_rows * SM_BLK + (size_t)row_lo * SM_WORK;    // and W factor rows
+    // ---- the h + m rows out of the ring ----
+    for (int i = tid; i < nw * 68; i += SM_THREADS) {
+        const int t = i / 68, c = i - t * 68;
+        x[i] = ring[((lo + t) % WC_RING) * 68 + c];
+    }
+    __syncthreads();
+    // ---- the row blocks of the free rows at them: a row per wave at a time ----
+    const double* Prig = Pmats + (size_t)rig * C * 12;
+    for (int r = wave; r < m; r += 4)
+        sm_row_block<LOSS>(T, LL.blk[wave], kps17, Prig, C, Pmax, mring + (size_t)((lo + h + r) % WC_RING) * C, x + (size_t)(h + r) * 68,
+                           bk + (size_t)r * SM_BLK, loss_px);
+    __syncthreads();   // (the LDS changes hands: blocks -> sweep; the blocks are complete)
+    ScLds& S = LL.sc;
+    SmSweepLds& L = S.sw;
+    sm_sweep_tables(L, T, root_vel, root_acc, ang_vel, ang_acc);
+    const double Ed = sm_data_energy(L, bk, SM_BLK, m);
+    const SmStep st = sm_sweep(L, bk, SM_BLK, wk, SM_WORK, x, m, h, nw, mu);
+    if (uni(st.fail)) {   // a pivot of the factor is not positive and finite: no covariance
+        unsolved(1.0, Ed, (double)m, (double)e);
+        return;
+    }
+    __syncthreads();   // the factor in the workspace is read-only from here on
+    double e_acc = 0.0;
+    int n_acc = 0;
+    sc_recursion(S, T, x + (size_t)h * 68, bk, wk, m, full ? 0 : e, e, kps17, C,
+                 [&](int r) { return mring + (size_t)((lo + h + r) % WC_RING) * C; }, jc, pv, e_acc, n_acc);
+    double edof = qnan, nres = qnan;
+    if (full) {
+        edof = sm_wg_sum(L.red, e_acc);
+        nres = 2.0 * sm_wg_sum(L.red, (double)n_acc);
+    }
+    if (tid < SC_INFO) ci[tid] = tid == 0 ? 0.0 : tid == 1 ? Ed : tid == 2 ? nres : tid == 3 ? edof : tid == 4 ? (double)m : tid == 5 ? (double)e : 0.0;
+}
+
+}  // namespace
+
+extern "C" long long mvmc_smooth_window_cov_work_doubles(int n_items, int window) {
+    if (n_items < 0 || window < 2 || window > WC_MAXW) return -1;
+    return (long long)n_items * (WC_X + (long long)window * (SM_BLK + SM_WORK));
+}
+
+extern "C" int mvmc_smooth_window_cov(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                      int n_rigs, const int32_t* items, int n_items, const double* rows, const int32_t* members,
+                                      const int32_t* count, int n_slots, int window, double root_vel, double root_acc, double ang_vel,
+                                      double ang_acc, double mu, int full, int loss, double loss_px, double* work, long long work_doubles,
+                                      double* jcov, double* pvar, double* cinfo, mvmcStream_t stream) {
+    if (!skel_host || n_items < 0 || n_slots < 0 || n_rigs < 1 || n_views <= 0 || n_views > MVMC_SMOOTH_MAX_VIEWS || p_max <= 0)
+        return MVMC_ERR_ARG;
+    if (window < 2 || window > WC_MAXW) return MVMC_ERR_ARG;
+    if (!(root_vel >= 0.0) || !(root_acc >= 0.0) || !(ang_vel >= 0.0) || !(ang_acc >= 0.0) || !(mu >= 0.0)) return MVMC_ERR_ARG;
+    if (!sm_loss_ok(loss, loss_px)) return MVMC_ERR_ARG;
+    if (n_items == 0) return MVMC_OK;
+    if (!kps17 || !Pmats || !items || !rows || !members || !count || !work || !jcov || !pvar || !cinfo) return MVMC_ERR_ARG;
+    if (work_doubles < mvmc_smooth_window_cov_work_doubles(n_items, window)) return MVMC_ERR_ARG;
+    Ik1Tables T;
+    if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
+    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_HUBER>
+                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_CAUCHY>
+                                                    : smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(n_items), dim3(SM_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, n_rigs, items, rows,
+                       members, count, n_slots, window, root_vel, root_acc, ang_vel, ang_acc, mu, full != 0 ? 1 : 0, work, n_items * window, jcov, pvar,
+                       cinfo, loss_px);
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
+}

@@ -607,6 +607,46 @@ def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor,
     return info
 
 
+def smooth_window_cov_work(n_items: int, window: int, dev) -> torch.Tensor:
+    """Workspace of mvmc_smooth_window_cov for ``n_items`` emitted rows of one tick (include/mvmc.h:
+    mvmc_smooth_window_cov_work_doubles)."""
+    need = int(_cabi.load().mvmc_smooth_window_cov_work_doubles(int(n_items), int(window)))
+    if need < 0:
+        raise ValueError(f"smooth_window_cov: no workspace for {n_items} items of window {window}")
+    return stream_buffer("smooth_window_cov", max(need, 1), (), dev)
+
+
+def smooth_window_cov(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, rows: torch.Tensor, members: torch.Tensor,
+                      count: torch.Tensor, window: int, weights, mu: float, full: bool, skeleton: Optional[MvmcSkeleton] = None, *,
+                      loss: Optional[str] = None, loss_px: Optional[float] = None):
+    """The covariance of the rows a tick emits, conditional on the frozen history (include/mvmc.h: mvmc_smooth_window_cov), one launch
+    after smooth_window that only reads the state.  items (n,4) i32 {slot, rig, emit_row, work_row}; kps17, Pmats, rows, members,
+    count, window, weights and the loss as smooth_window takes them; mu the damping of the inverted A_w + mu diag A_w; full: the
+    recursion covers every free row and cinfo carries n_res and edof (else NaN).  -> jcov (n,18,6), pvar (n,39), cinfo (n,8), unit
+    variance."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    n = items.shape[0]
+    _req(items, torch.int32, "items", (n, _cabi.SMOOTH_COV_ITEM_INTS))
+    n_slots = rows.shape[0]
+    _req(rows, torch.float64, "rows", (n_slots, _cabi.SMOOTH_WIN_RING, 68))
+    _req(members, torch.int32, "members", (n_slots, _cabi.SMOOTH_WIN_RING, Cn))
+    _req(count, torch.int32, "count", (n_slots, 2))
+    rv, ra, av, aa = (float(w) for w in weights)
+    code, px = smooth_loss_args(loss, loss_px, "smooth_window_cov")
+    jcov = torch.empty((n, _cabi.SMOOTH_JOINTS, 6), dtype=torch.float64, device=rows.device)
+    pvar = torch.empty((n, _cabi.SMOOTH_K), dtype=torch.float64, device=rows.device)
+    cinfo = torch.empty((n, _cabi.SMOOTH_COV_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
+    work = smooth_window_cov_work(n, window, rows.device)
+    check(_cabi.load().mvmc_smooth_window_cov(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(rows),
+                                              _p(members), _p(count), n_slots, int(window), rv, ra, av, aa, float(mu), int(bool(full)),
+                                              code, px, _p(work), int(work.numel()), _p(jcov), _p(pvar), _p(cinfo), _stream()),
+          "mvmc_smooth_window_cov")
+    return jcov, pvar, cinfo
+
+
 def ik_solve_fd(kps17: torch.Tensor, Pmats: torch.Tensor, members: torch.Tensor, init_params: Optional[torch.Tensor] = None,
                 cold: Optional[torch.Tensor] = None, max_nfev_cold=50, max_nfev_warm=5, stage_mask=3,
                 skeleton: Optional[MvmcSkeleton] = None):

@@ -24,9 +24,25 @@ loss="huber" / "cauchy" at loss_px pixels puts smoothing.py's robust loss on the
 mvmc_smooth_window_robust (the same state, workspace and outputs; ``solved``'s cost holds the robust E_data).  loss=None is the plain
 launch, bit for bit.  The live path sets no weights attribute: which keypoints were voted down is the offline smoother's
 ``smooth_obs_weight``.
+
+covariance="joints" (default None: no extra launch, no new argument to any entry, the same bits) adds ONE launch per tick after the
+window's, mvmc_smooth_window_cov (csrc/mvmc_smooth_window_cov.hip; restated in tests/live_smooth_cov_np.py), for every row the tick
+emits; its outputs join the tick's one read-back.  At the end of a tick A_w is the matrix the window's LM step factors at the rows'
+final values: the free rows' data blocks (with a loss the weighted ones) + the exact Hessian of every prior term that touches a free
+row, the history held fixed.  Sigma = (A_w + smoothing.COV_MU diag A_w)^-1, and the emitted row e gets Sigma_ee: per skeleton joint
+C_K = D_K Sigma_ee D_K^T and the 39 diagonal entries, scaled by noise_px^2.  This is the covariance CONDITIONAL on the frozen history
+(and on the rig, the lengths, the held joints and the view selection) -- what the fixed-lag solve itself assumes.  Conditioning can
+only lower a variance, so on the window's rows it is a lower bound on what the offline smoother (smoothing.py: covariance="joints")
+would report; the offline smoother of the complete record also sees the frames after the window, which pushes the other way.  The gap
+is measured, not promised (tools/live_smooth_cov_probe.py, INTEGRATION.md section C.5: within half a percent at unit variance for lag
+8 in a window of 24, on either side).  noise_px given: the recursion stops at the emitted row (lag + 1 of
+the window's rows) and edof / nres are not computed (NaN / 0).  noise_px=None: it is estimated per tick and identity over the window's
+free rows, sqrt(2 E_data / (n_res - edof)), NaN when that is not positive.  Under a loss the ESTIMATED noise_px is biased low, because
+rho <= 1/2 e^2 shrinks E_data while n_res still counts every residual: under a loss noise_px= is the honest choice.
 """
 from __future__ import annotations
 
+import math
 import time
 from typing import Dict, List, Optional, Sequence
 
@@ -34,7 +50,7 @@ import numpy as np
 
 from .body_fit import MAX_DIST, MIN_SCORE
 from .sequences import frame_buckets, new_record, pose_slot, pose_tuples
-from .smoothing import ANG_ACC, ANG_VEL, LM_FTOL, LM_MU0, LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, check_loss, unwrap_euler_many
+from .smoothing import ANG_ACC, ANG_VEL, COV_MU, LM_FTOL, LM_MU0, LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, check_loss, unwrap_euler_many
 from .tracker import T_WIDE
 
 WINDOW_MAX = 32     # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
@@ -59,15 +75,46 @@ def check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc) 
     return w
 
 
+def check_covariance(covariance, noise_px) -> Optional[float]:
+    """LiveSmoother's covariance arguments (host only; smoothing._check_covariance's rules) -> noise_px as a float, or None."""
+    if covariance is not None and not (isinstance(covariance, str) and covariance == "joints"):
+        raise ValueError(f"LiveSmoother: covariance must be None or \"joints\", got {covariance!r}")
+    if noise_px is None:
+        return None
+    if covariance is None:
+        raise ValueError("LiveSmoother: noise_px without covariance=\"joints\" has nothing to scale")
+    if isinstance(noise_px, (str, bytes, bool)) or not isinstance(noise_px, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(noise_px) or not noise_px > 0:
+        raise ValueError(f"LiveSmoother: noise_px must be None or a finite number > 0, got {noise_px!r}")
+    return float(noise_px)
+
+
+def cov_entry(jc6, pv, ci, noise_px: Optional[float]) -> dict:
+    """One emitted row's unit-variance device outputs (jcov (18,6), pvar (39,), cinfo (8,)) -> its TickOutput.cov entry."""
+    status, e_data, n_res, edof = int(ci[0]), float(ci[1]), float(ci[2]), float(ci[3])
+    if noise_px is not None:
+        s = noise_px
+    else:
+        s = math.sqrt(2.0 * e_data / (n_res - edof)) if status == 0 and n_res - edof > 0 else math.nan
+    jc = jc6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(18, 3, 3)
+    return dict(joint_cov=(s * s) * jc, joint_sigma=np.sqrt((s * s) * (jc[:, 0, 0] + jc[:, 1, 1] + jc[:, 2, 2])),
+                param_sigma=np.sqrt((s * s) * pv), noise_px=float(s), edof=edof,
+                nres=int(n_res) if status == 0 and math.isfinite(n_res) else 0, status=status)
+
+
 class TickOutput:
     """One session's results of one tick.  ``emitted``: [(track_id, frame_idx, PoseShapeParam, Pose (FK joints), filled, views)] for
     frame idx - lag, in the table's order; ``finished``: the records of the tracklets that died this tick; ``solved``: track_id ->
-    dict(cost [E_data, E_prior at the start, E_data, E_prior at the end], trials [1 accepted / 0 rejected], stop)."""
+    dict(cost [E_data, E_prior at the start, E_data, E_prior at the end], trials [1 accepted / 0 rejected], stop); ``cov``: empty
+    unless the smoother has covariance="joints", then track_id -> dict(joint_cov (18,3,3) m^2, joint_sigma (18,) m, param_sigma (39,),
+    noise_px, edof, nres, status 0 solved / 1 singular / 2 a one-row identity (NaN arrays)) of the emitted row, conditional on the
+    window's frozen history (the module's docstring)."""
 
     def __init__(self):
         self.emitted: list = []
         self.finished: list = []
         self.solved: Dict[int, dict] = {}
+        self.cov: Dict[int, dict] = {}
 
 
 class _Ident:
@@ -80,6 +127,7 @@ class _Ident:
         self.sel: List[Optional[np.ndarray]] = []
         self.params: List[Optional[np.ndarray]] = []   # a row's values once it is final (None before)
         self.joints: List[Optional[np.ndarray]] = []
+        self.cov: Dict[int, tuple] = {}                # row -> (joint_sigma, param_sigma, noise_px) as emitted (covariance="joints")
         self.n_final = 0
 
     @property
@@ -109,8 +157,11 @@ class LiveSmoother:
 
     def __init__(self, n_views: int, capacity: int, p_max: int = 8, window: int = 24, lag: int = 8, n_iter: int = 2,
                  root_vel: float = ROOT_VEL, root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC,
-                 device=None, skeleton=None, loss: Optional[str] = None, loss_px: float = LOSS_PX):
+                 device=None, skeleton=None, loss: Optional[str] = None, loss_px: float = LOSS_PX, covariance: Optional[str] = None,
+                 noise_px: Optional[float] = None):
         self.w = check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc)
+        self._noise_px = check_covariance(covariance, noise_px)
+        self._cov = covariance is not None
         loss_px = check_loss("LiveSmoother", loss, loss_px)
         self._rob = dict(loss=loss, loss_px=loss_px) if loss is not None else {}     # loss=None: the launch without the arguments
         if int(capacity) < 1 or not 1 <= int(n_views) <= MAX_VIEWS or int(p_max) < 1:
@@ -336,6 +387,14 @@ class LiveSmoother:
             info = dev.smooth_window(st["kps"], st["Pm"], T(np.array(items, np.int32)), newp_d, mem_d, st["rows"], st["members"],
                                      st["count"], W, self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton, **self._rob)
             parts.append(info.reshape(-1))
+        # the covariance of the emitted rows: ONE launch for all of them, none when nothing is emitted (or it is not asked for)
+        cov_of = [a for a, (key, idn, f) in enumerate(solved_of) if f - self.lag - idn.f0 >= 0] if self._cov else []
+        if cov_of:
+            citems = [[solved_of[a][1].slot, self._sessions[solved_of[a][0]].s, solved_of[a][2] - self.lag - solved_of[a][1].f0, k * W]
+                      for k, a in enumerate(cov_of)]
+            parts += [p.reshape(-1) for p in dev.smooth_window_cov(st["kps"], st["Pm"], T(np.array(citems, np.int32)), st["rows"],
+                                                                   st["members"], st["count"], W, self.w, COV_MU,
+                                                                   self._noise_px is None, self.skeleton, **self._rob)]
         Pg = [p for p in (P_fin, st["rows"].view(-1, 68).index_select(0, slot_idx(want)) if want else None) if p is not None]
         n_rows = len(want_fin) + len(want)
         if n_rows:
@@ -353,6 +412,8 @@ class LiveSmoother:
             at += n
             return a
         inf_h = take(len(items) * 16, (len(items), 16))
+        nc = len(cov_of)
+        jc_h, pv_h, ci_h = take(nc * 108, (nc, 18, 6)), take(nc * 39, (nc, 39)), take(nc * 8, (nc, 8))
         P_h = take(n_rows * 68, (n_rows, 68))
         J_h = take(n_rows * 54, (n_rows, 18, 3))
         mem_h = take(B * C, (B, C)).astype(np.int64)
@@ -383,6 +444,12 @@ class LiveSmoother:
             r = f - self.lag - idn.f0
             if r >= 0:
                 emit.append((key, idn.tid, f - self.lag, got[(id(idn), r)], bool(idn.filled[r]), int(idn.views[r])))
+        for k, a in enumerate(cov_of):
+            key, idn, f = solved_of[a]
+            if int(ci_h[k, 0]) == 6:
+                raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed covariance item")
+            c = out[key].cov[idn.tid] = cov_entry(jc_h[k], pv_h[k], ci_h[k], self._noise_px)
+            idn.cov[f - self.lag - idn.f0] = (c["joint_sigma"], c["param_sigma"], c["noise_px"])
         if emit:      # the tick's emitted poses in one pass
             ks = [e[3] for e in emit]
             for (key, tid, _, _, filled, views), pose in zip(emit, pose_tuples([e[2] for e in emit], P_h[ks], J_h[ks])):
@@ -457,11 +524,19 @@ class LiveSmoother:
         t.smooth_views = np.array(idn.views[:n], np.int32)
         t.smooth_select = np.array(idn.sel[:n], np.int32).reshape(n, self.C)
         t.smooth_final = np.arange(n) < idn.n_final
+        if self._cov:      # per row the values recorded when it was emitted; NaN on the rows that never were
+            t.smooth_joint_sigma, t.smooth_param_sigma, t.smooth_noise_px = np.full((n, 18), np.nan), np.full((n, 39), np.nan), np.full(n, np.nan)
+            for r, (js, ps, s) in idn.cov.items():
+                if r < n:
+                    t.smooth_joint_sigma[r], t.smooth_param_sigma[r], t.smooth_noise_px[r] = js, ps, s
         return t
 
     def tracklets(self, key) -> list:
         """The session's live identities as records f0..newest without holes: poses, smooth_filled, smooth_views, smooth_select,
-        smooth_final (the row has left the window).  Reads the rows that are not final back from the device."""
+        smooth_final (the row has left the window).  Reads the rows that are not final back from the device.  With covariance="joints"
+        (here, in ``finished`` and from close_session) also smooth_joint_sigma (n,18), smooth_param_sigma (n,39), smooth_noise_px (n,): per
+        row the values of TickOutput.cov when the row was emitted, NaN on the rows that never were (the last <= lag rows of a record,
+        and the rows a jump of the frame index skipped)."""
         sess = self._session(key, "tracklets")
         want = [(idn, r) for idn in sess.ids.values() for r in range(idn.n_final, idn.n)]
         P, J = self._fetch(want)
