@@ -702,6 +702,40 @@ int mvmc_smooth_contact_anchors(const double* joints, const int32_t* id_lo, int 
                                 int min_run, int use_ground, const double* ground, double height, int32_t* cmask, double* anchors,
                                 int32_t* ctl, mvmcStream_t stream);
 
+/* ---- foot contacts of the live smoother (live_smoothing.py: contacts="auto"; restated in tests/live_smooth_contact_np.py).  Two more
+ * state arrays stay on the device between ticks, per identity slot and ring position: contact (n_slots, MVMC_SMOOTH_WIN_RING, 2) i32,
+ * the row's label per foot, and anchors (n_slots, MVMC_SMOOTH_WIN_RING, 2, 3) f64, NaN without a label.
+ * mvmc_smooth_window_contact is mvmc_smooth_window_robust, still ONE launch per tick and one 256-lane workgroup per item, with:
+ *   append   the new rows get label 0 and a NaN anchor (reset: the slot's whole rings are cleared);
+ *   solve    every free row with a label adds 1/2 contact_weight |ankle_f(x_r) - anchor|^2 under its STORED label and anchor (the
+ *            term of mvmc_smooth_blocks_contact, outside the loss); history rows carry no term.  info's E_data includes it;
+ *   relabel  after the last trial, on the solved values: rows with index <= n - 1 - lag are frozen and keep label and anchor for good;
+ *            the rows after them are labelled again by mvmc_smooth_contact_anchors' rule (speed < contact_speed, one-sided at the
+ *            identity's first and newest row; with use_ground != 0 also ground[0..2] . p - ground[3] < contact_height, ground 4
+ *            doubles on the HOST); then over the window's rows, history included: a run whose first visible row is frozen keeps that
+ *            row's anchor on all its rows and is never dropped; a run without a frozen row is dropped when shorter than
+ *            contact_min_frames, else its anchor is the mean of its rows' ankles, summed in row order.
+ *   cinfo (n_items, MVMC_SMOOTH_LIVE_CONTACT_DOUBLES) f64 out: label L, R and anchor L (3), R (3) of the row n - 1 - lag (the row the
+ *            tick emits: frozen from this tick on; 0 and NaN when there is none), E_contact at the start and at the end of the tick.
+ * 0 <= lag < window, contact_min_frames >= 1, lag + 1 >= contact_min_frames, contact_weight finite >= 0, contact_speed finite (and
+ * with use_ground a finite ground and contact_height), else MVMC_ERR_ARG before any HIP call; a malformed item is skipped with stop
+ * reason 6.  mvmc_smooth_window_cov_contact is mvmc_smooth_window_cov whose free rows' blocks carry the term of the labels and anchors
+ * as they stand in the two arrays (after the tick's launch: the relabelled ones); it only reads them. ---- */
+#define MVMC_SMOOTH_LIVE_CONTACT_DOUBLES 10
+int mvmc_smooth_window_contact(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats, int n_rigs,
+                               const int32_t* items, int n_items, const double* new_params, const int32_t* new_members, int n_new,
+                               double* rows, int32_t* members, int32_t* count, int n_slots, int window, int n_iter, double root_vel,
+                               double root_acc, double ang_vel, double ang_acc, double mu0, double ftol, double xtol, double* info,
+                               double* work, long long work_doubles, int loss, double loss_px, int32_t* contact, double* anchors,
+                               int lag, double contact_weight, double contact_speed, int contact_min_frames, int use_ground,
+                               const double* ground, double contact_height, double* cinfo, mvmcStream_t stream);
+int mvmc_smooth_window_cov_contact(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                   int n_rigs, const int32_t* items, int n_items, const double* rows, const int32_t* members,
+                                   const int32_t* count, int n_slots, int window, double root_vel, double root_acc, double ang_vel,
+                                   double ang_acc, double mu, int full, int loss, double loss_px, double* work, long long work_doubles,
+                                   double* jcov, double* pvar, double* cinfo, const int32_t* contact, const double* anchors,
+                                   double contact_weight, mvmcStream_t stream);
+
 /* ---- re-linking of the records of one person (multiview_motion_capture_amd/relinking.py).  No counterpart in the reference.  Per
  * sequence, its records in (first frame, track id) order are the nodes; record a may be followed by record b when 1 <= gap =
  * first(b) - last(a) <= max_gap, at the cost mean_k |last_joints(a)[k] + v gap - first_joints(b)[k]| (metres; v = the mean of a's end

@@ -27,6 +27,7 @@ SMOOTH_K, SMOOTH_BLOCK_DOUBLES, SMOOTH_WORK_DOUBLES, SMOOTH_INFO_DOUBLES, SMOOTH
 SMOOTH_COV_INFO_DOUBLES, SMOOTH_JOINTS = 8, 18
 SMOOTH_WIN_MAX, SMOOTH_WIN_RING, SMOOTH_WIN_ITEM_INTS, SMOOTH_WIN_INFO_DOUBLES = 32, 66, 8, 16
 SMOOTH_COV_ITEM_INTS = 4                                                                          # MVMC_SMOOTH_COV_ITEM_INTS
+SMOOTH_LIVE_CONTACT_DOUBLES = 10                                                                  # MVMC_SMOOTH_LIVE_CONTACT_DOUBLES
 SMOOTH_LOSS_NONE, SMOOTH_LOSS_HUBER, SMOOTH_LOSS_CAUCHY = 0, 1, 2                                     # MVMC_SMOOTH_LOSS_*
 SMOOTH_FOOT_L, SMOOTH_FOOT_R = 3, 6                                                                   # MVMC_SMOOTH_FOOT_*: the ankles
 RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
@@ -47,6 +48,7 @@ SYMBOLS = (
     "mvmc_smooth_blocks_robust", "mvmc_smooth_obs_weights", "mvmc_smooth_window_robust",
     "mvmc_smooth_blocks_contact", "mvmc_smooth_contact_anchors",
     "mvmc_smooth_window_cov_work_doubles", "mvmc_smooth_window_cov",
+    "mvmc_smooth_window_contact", "mvmc_smooth_window_cov_contact",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
     "mvmc_rig_accumulate_robust", "mvmc_rig_step_robust", "mvmc_rig_weights",
     "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
@@ -174,6 +176,11 @@ def load():
         "mvmc_smooth_window_cov_work_doubles": [i32, i32],
         "mvmc_smooth_window_cov": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i32, i32, f64, vp,
                                    C.c_longlong, vp, vp, vp, vp],
+        "mvmc_smooth_window_contact": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32, i32, f64, f64, f64, f64, f64,
+                                       f64, f64, vp, vp, C.c_longlong, i32, f64, vp, vp, i32, f64, f64, i32, i32, C.POINTER(C.c_double),
+                                       f64, vp, vp],
+        "mvmc_smooth_window_cov_contact": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i32, i32, f64,
+                                           vp, C.c_longlong, vp, vp, vp, vp, vp, f64, vp],
         "mvmc_relink_work_words": [i32],
         "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
         "mvmc_rig_part_doubles": [i32],

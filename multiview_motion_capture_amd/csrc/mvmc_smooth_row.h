@@ -25,9 +25,10 @@ struct SmBlkLds {
 };
 
 // FK of one row on the calling wave: x the row's 68 parameters -> L.Rl, L.Rg (local and global rotations) and L.pos (joints); AXES: L.ax
-// too, the Euler axes of every joint in the global frame.  L.pos is complete on return; L.ax needs one MVMC_WAVE_SYNC more.
-template <bool AXES, class Lds>
-__device__ __forceinline__ void sm_row_fk(const Ik1Tables& T, Lds& L, const double* __restrict__ x) {
+// too, the Euler axes of every joint in the global frame.  L.pos is complete on return; L.ax needs one MVMC_WAVE_SYNC more.  Tab: the
+// tables' type -- Ik1Tables, or any struct with its parents, side_map and dirs (a copy of them in LDS).
+template <bool AXES, class Lds, class Tab>
+__device__ __forceinline__ void sm_row_fk(const Tab& T, Lds& L, const double* __restrict__ x) {
     const int lane = threadIdx.x & 63;
     if (lane < 18) {
         euler_to_rot(x + 3 + 3 * lane, &L.Rl[9 * lane]);

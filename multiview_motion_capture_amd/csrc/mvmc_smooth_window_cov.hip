@@ -21,6 +21,9 @@
 // Workspace per item: (MVMC_SMOOTH_WIN_MAX + 2) x 68 doubles for the rows, and per window row a block (SM_BLK) and a factor row (SM_WORK).
 // Every sum runs in a fixed order inside the identity's own lanes, no atomics: an identity's numbers depend on nothing else in the
 // launch.  A malformed item gets status 6 and NaN outputs and is never followed out of bounds.
+// mvmc_smooth_window_cov_contact (live_smoothing.py: covariance="joints" with contacts="auto"): the same launch reading the slots' label
+// and anchor rings as they stand after the tick; the free rows' blocks come from sm_row_block<LOSS, true>, so A_w carries wc D^T D of
+// every labelled ankle: the covariance is conditional on the labels and anchors too, as the offline smoother's is.
 #define MVMC_DEVICE_ONLY
 #include "mvmc_common.h"
 #include "mvmc_track.hip"
@@ -44,13 +47,22 @@ union WcLds {
 };
 static_assert(sizeof(WcLds) <= 160 * 1024, "LDS of one workgroup");
 
-template <int LOSS>
+// the contact arguments of smooth_window_cov_kernel<LOSS, true> (the plain instantiations take none)
+struct WcContact {
+    const int32_t* lab;   // (n_slots, WC_RING, 2)
+    const double* anc;    // (n_slots, WC_RING, 2, 3)
+    double wc;
+};
+__device__ __forceinline__ const WcContact& wc_contact(const WcContact& c) { return c; }
+
+template <int LOSS, bool CONTACT, class... CA>
 __global__ void __launch_bounds__(SM_THREADS) smooth_window_cov_kernel(
     Ik1Tables T, const double* __restrict__ kps17, const double* __restrict__ Pmats, int C, int Pmax, int n_rigs,
     const int32_t* __restrict__ items, const double* __restrict__ rows, const int32_t* __restrict__ members,
     const int32_t* __restrict__ count, int n_slots, int W, double root_vel, double root_acc, double ang_vel, double ang_acc, double mu,
     int full, double* __restrict__ work, int work_rows, double* __restrict__ jcov, double* __restrict__ pvar, double* __restrict__ cinfo,
-    double loss_px) {
+    double loss_px, CA... ca) {
+    static_assert(sizeof...(CA) == (CONTACT ? 1 : 0), "one WcContact with contacts, nothing without");
     __shared__ WcLds LL;
     const int tid = threadIdx.x, wave = tid >> 6, it = blockIdx.x;
     const int32_t* im = items + (size_t)it * WC_ITEM;
@@ -98,9 +110,18 @@ __global__ void __launch_bounds__(SM_THREADS) smooth_window_cov_kernel(
     __syncthreads();
     // ---- the row blocks of the free rows at them: a row per wave at a time ----
     const double* Prig = Pmats + (size_t)rig * C * 12;
-    for (int r = wave; r < m; r += 4)
-        sm_row_block<LOSS>(T, LL.blk[wave], kps17, Prig, C, Pmax, mring + (size_t)((lo + h + r) % WC_RING) * C, x + (size_t)(h + r) * 68,
-                           bk + (size_t)r * SM_BLK, loss_px);
+    for (int r = wave; r < m; r += 4) {
+        const int at = (lo + h + r) % WC_RING;
+        if constexpr (CONTACT) {
+            const WcContact& c = wc_contact(ca...);
+            sm_row_block<LOSS, true>(T, LL.blk[wave], kps17, Prig, C, Pmax, mring + (size_t)at * C, x + (size_t)(h + r) * 68,
+                                     bk + (size_t)r * SM_BLK, loss_px, c.lab + ((size_t)slot * WC_RING + at) * 2,
+                                     c.anc + ((size_t)slot * WC_RING + at) * 6, c.wc);
+        } else {
+            sm_row_block<LOSS>(T, LL.blk[wave], kps17, Prig, C, Pmax, mring + (size_t)at * C, x + (size_t)(h + r) * 68,
+                               bk + (size_t)r * SM_BLK, loss_px);
+        }
+    }
     __syncthreads();   // (the LDS changes hands: blocks -> sweep; the blocks are complete)
     ScLds& S = LL.sc;
     SmSweepLds& L = S.sw;
@@ -131,11 +152,12 @@ extern "C" long long mvmc_smooth_window_cov_work_doubles(int n_items, int window
     return (long long)n_items * (WC_X + (long long)window * (SM_BLK + SM_WORK));
 }
 
-extern "C" int mvmc_smooth_window_cov(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+static int wc_launch(bool with_contact, const int32_t* contact, const double* anchors, double contact_weight, const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
                                       int n_rigs, const int32_t* items, int n_items, const double* rows, const int32_t* members,
                                       const int32_t* count, int n_slots, int window, double root_vel, double root_acc, double ang_vel,
                                       double ang_acc, double mu, int full, int loss, double loss_px, double* work, long long work_doubles,
                                       double* jcov, double* pvar, double* cinfo, mvmcStream_t stream) {
+    if (with_contact && !(contact_weight >= 0.0 && contact_weight <= 1.7976931348623157e308)) return MVMC_ERR_ARG;   // (NaN fails both)
     if (!skel_host || n_items < 0 || n_slots < 0 || n_rigs < 1 || n_views <= 0 || n_views > MVMC_SMOOTH_MAX_VIEWS || p_max <= 0)
         return MVMC_ERR_ARG;
     if (window < 2 || window > WC_MAXW) return MVMC_ERR_ARG;
@@ -143,15 +165,49 @@ extern "C" int mvmc_smooth_window_cov(const mvmcSkeleton* skel_host, const doubl
     if (!sm_loss_ok(loss, loss_px)) return MVMC_ERR_ARG;
     if (n_items == 0) return MVMC_OK;
     if (!kps17 || !Pmats || !items || !rows || !members || !count || !work || !jcov || !pvar || !cinfo) return MVMC_ERR_ARG;
+    if (with_contact && (!contact || !anchors)) return MVMC_ERR_ARG;
     if (work_doubles < mvmc_smooth_window_cov_work_doubles(n_items, window)) return MVMC_ERR_ARG;
     Ik1Tables T;
     if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
-    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_HUBER>
-                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_CAUCHY>
-                                                    : smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_NONE>;
+    if (with_contact) {
+        const WcContact ca{contact, anchors, contact_weight};
+        auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_HUBER, true, WcContact>
+                      : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_CAUCHY, true, WcContact>
+                                                        : smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_NONE, true, WcContact>;
+        hipLaunchKernelGGL(kernel, dim3(n_items), dim3(SM_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, n_rigs, items,
+                           rows, members, count, n_slots, window, root_vel, root_acc, ang_vel, ang_acc, mu, full != 0 ? 1 : 0, work,
+                           n_items * window, jcov, pvar, cinfo, loss_px, ca);
+        MVMC_CHECK_LAUNCH();
+        return MVMC_OK;
+    }
+    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_HUBER, false>
+                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_CAUCHY, false>
+                                                    : smooth_window_cov_kernel<MVMC_SMOOTH_LOSS_NONE, false>;
     hipLaunchKernelGGL(kernel, dim3(n_items), dim3(SM_THREADS), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, n_rigs, items, rows,
                        members, count, n_slots, window, root_vel, root_acc, ang_vel, ang_acc, mu, full != 0 ? 1 : 0, work, n_items * window, jcov, pvar,
                        cinfo, loss_px);
     MVMC_CHECK_LAUNCH();
     return MVMC_OK;
+}
+
+extern "C" int mvmc_smooth_window_cov(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                      int n_rigs, const int32_t* items, int n_items, const double* rows, const int32_t* members,
+                                      const int32_t* count, int n_slots, int window, double root_vel, double root_acc, double ang_vel,
+                                      double ang_acc, double mu, int full, int loss, double loss_px, double* work, long long work_doubles,
+                                      double* jcov, double* pvar, double* cinfo, mvmcStream_t stream) {
+    return wc_launch(false, nullptr, nullptr, 0.0, skel_host, kps17, n_views, p_max, Pmats, n_rigs, items, n_items, rows, members, count,
+                     n_slots, window, root_vel, root_acc, ang_vel, ang_acc, mu, full, loss, loss_px, work, work_doubles, jcov, pvar, cinfo,
+                     stream);
+}
+
+extern "C" int mvmc_smooth_window_cov_contact(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max,
+                                              const double* Pmats, int n_rigs, const int32_t* items, int n_items, const double* rows,
+                                              const int32_t* members, const int32_t* count, int n_slots, int window, double root_vel,
+                                              double root_acc, double ang_vel, double ang_acc, double mu, int full, int loss,
+                                              double loss_px, double* work, long long work_doubles, double* jcov, double* pvar,
+                                              double* cinfo, const int32_t* contact, const double* anchors, double contact_weight,
+                                              mvmcStream_t stream) {
+    return wc_launch(true, contact, anchors, contact_weight, skel_host, kps17, n_views, p_max, Pmats, n_rigs, items, n_items, rows, members,
+                     count, n_slots, window, root_vel, root_acc, ang_vel, ang_acc, mu, full, loss, loss_px, work, work_doubles, jcov, pvar,
+                     cinfo, stream);
 }

@@ -572,11 +572,14 @@ def smooth_window_work(n_items: int, window: int, dev) -> torch.Tensor:
 def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, new_params: torch.Tensor, new_members: torch.Tensor,
                   rows: torch.Tensor, members: torch.Tensor, count: torch.Tensor, window: int, n_iter: int, weights, mu0: float,
                   ftol: float, xtol: float, skeleton: Optional[MvmcSkeleton] = None, *, loss: Optional[str] = None,
-                  loss_px: Optional[float] = None) -> torch.Tensor:
+                  loss_px: Optional[float] = None, contact: Optional[dict] = None):
     """One tick of the live smoother for every item (include/mvmc.h: mvmc_smooth_window), one launch.  kps17 (F,C,P,17,3) the
     sessions' keypoint ring; Pmats (R,C,3,4); items (n,8) i32; new_params (B,68), new_members (B,C) the tick's data rows; rows
     (n_slots,66,68), members (n_slots,66,C), count (n_slots,2) the identities' device state, updated in place.  -> info (n,16).
-    loss "huber" / "cauchy" with loss_px > 0: the same launch on the robust data term (mvmc_smooth_window_robust)."""
+    loss "huber" / "cauchy" with loss_px > 0: the same launch on the robust data term (mvmc_smooth_window_robust).
+    contact = dict(labels (n_slots,66,2) i32, anchors (n_slots,66,2,3) f64 -- state, updated in place --, lag, weight, speed,
+    min_frames, ground (normal (3,), offset) or None, height): the launch with foot contacts (mvmc_smooth_window_contact), with or
+    without a loss -> (info (n,16), cinfo (n,10))."""
     sk = skeleton if skeleton is not None else make_skeleton()
     F, Cn, P = kps17.shape[:3]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -593,6 +596,22 @@ def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor,
     rv, ra, av, aa = (float(w) for w in weights)
     info = torch.empty((n, _cabi.SMOOTH_WIN_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
     work = smooth_window_work(n, window, rows.device)
+    if contact is not None:
+        _req(contact["labels"], torch.int32, "contact labels", (n_slots, _cabi.SMOOTH_WIN_RING, 2))
+        _req(contact["anchors"], torch.float64, "contact anchors", (n_slots, _cabi.SMOOTH_WIN_RING, 2, 3))
+        code, px = smooth_loss_args(loss, loss_px, "smooth_window")
+        g = None
+        if contact["ground"] is not None:
+            g = (C.c_double * 4)(*[float(v) for v in contact["ground"][0]], float(contact["ground"][1]))
+        cinfo = torch.empty((n, _cabi.SMOOTH_LIVE_CONTACT_DOUBLES), dtype=torch.float64, device=rows.device)
+        check(_cabi.load().mvmc_smooth_window_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n,
+                                                      _p(new_params), _p(new_members), B, _p(rows), _p(members), _p(count), n_slots,
+                                                      int(window), int(n_iter), rv, ra, av, aa, float(mu0), float(ftol), float(xtol),
+                                                      _p(info), _p(work), int(work.numel()), code, px, _p(contact["labels"]),
+                                                      _p(contact["anchors"]), int(contact["lag"]), float(contact["weight"]),
+                                                      float(contact["speed"]), int(contact["min_frames"]), int(g is not None), g,
+                                                      float(contact["height"]), _p(cinfo), _stream()), "mvmc_smooth_window_contact")
+        return info, cinfo
     if loss is None:
         check(_cabi.load().mvmc_smooth_window(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(new_params),
                                               _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window), int(n_iter), rv, ra,
@@ -618,12 +637,13 @@ def smooth_window_cov_work(n_items: int, window: int, dev) -> torch.Tensor:
 
 def smooth_window_cov(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, rows: torch.Tensor, members: torch.Tensor,
                       count: torch.Tensor, window: int, weights, mu: float, full: bool, skeleton: Optional[MvmcSkeleton] = None, *,
-                      loss: Optional[str] = None, loss_px: Optional[float] = None):
+                      loss: Optional[str] = None, loss_px: Optional[float] = None, contact: Optional[dict] = None):
     """The covariance of the rows a tick emits, conditional on the frozen history (include/mvmc.h: mvmc_smooth_window_cov), one launch
     after smooth_window that only reads the state.  items (n,4) i32 {slot, rig, emit_row, work_row}; kps17, Pmats, rows, members,
     count, window, weights and the loss as smooth_window takes them; mu the damping of the inverted A_w + mu diag A_w; full: the
     recursion covers every free row and cinfo carries n_res and edof (else NaN).  -> jcov (n,18,6), pvar (n,39), cinfo (n,8), unit
-    variance."""
+    variance.  contact = smooth_window's dict (labels, anchors, weight are read): the free rows' blocks carry the foot-contact term of
+    the labels and anchors as they stand (mvmc_smooth_window_cov_contact)."""
     sk = skeleton if skeleton is not None else make_skeleton()
     F, Cn, P = kps17.shape[:3]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -640,6 +660,15 @@ def smooth_window_cov(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Ten
     pvar = torch.empty((n, _cabi.SMOOTH_K), dtype=torch.float64, device=rows.device)
     cinfo = torch.empty((n, _cabi.SMOOTH_COV_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
     work = smooth_window_cov_work(n, window, rows.device)
+    if contact is not None:
+        _req(contact["labels"], torch.int32, "contact labels", (n_slots, _cabi.SMOOTH_WIN_RING, 2))
+        _req(contact["anchors"], torch.float64, "contact anchors", (n_slots, _cabi.SMOOTH_WIN_RING, 2, 3))
+        check(_cabi.load().mvmc_smooth_window_cov_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n,
+                                                          _p(rows), _p(members), _p(count), n_slots, int(window), rv, ra, av, aa,
+                                                          float(mu), int(bool(full)), code, px, _p(work), int(work.numel()), _p(jcov),
+                                                          _p(pvar), _p(cinfo), _p(contact["labels"]), _p(contact["anchors"]),
+                                                          float(contact["weight"]), _stream()), "mvmc_smooth_window_cov_contact")
+        return jcov, pvar, cinfo
     check(_cabi.load().mvmc_smooth_window_cov(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(rows),
                                               _p(members), _p(count), n_slots, int(window), rv, ra, av, aa, float(mu), int(bool(full)),
                                               code, px, _p(work), int(work.numel()), _p(jcov), _p(pvar), _p(cinfo), _stream()),

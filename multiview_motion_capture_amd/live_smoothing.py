@@ -39,6 +39,25 @@ is measured, not promised (tools/live_smooth_cov_probe.py, INTEGRATION.md sectio
 the window's rows) and edof / nres are not computed (NaN / 0).  noise_px=None: it is estimated per tick and identity over the window's
 free rows, sqrt(2 E_data / (n_res - edof)), NaN when that is not positive.  Under a loss the ESTIMATED noise_px is biased low, because
 rho <= 1/2 e^2 shrinks E_data while n_res still counts every residual: under a loss noise_px= is the honest choice.
+
+contacts="auto" (default None: the launches, their arguments, the state and the bits are the ones without it) adds smoothing.py's foot
+contacts with causal, committed anchors; the tick's one launch is then mvmc_smooth_window_contact (restated in
+tests/live_smooth_contact_np.py, which is the definition).  Per identity and foot (0 left ankle, 1 right) every row has a label and an
+anchor (3 doubles, NaN without a label), kept beside the row in two more device tensors.  During a tick every free row with a label
+adds 1/2 contact_weight |ankle(x_r) - anchor|^2 under its STORED label and anchor (outside the loss); rows appended by the tick have
+none yet, history rows carry no term.  At the end of the tick, on the solved values: rows with index <= n - 1 - lag -- the emitted row
+and everything older, also rows a jump of the frame index carried past the emit position -- are frozen and keep label and anchor for
+good; the rows after them are labelled again (smoothing.py's rule: the ankle's central-difference speed < contact_speed, one-sided at the
+identity's first and newest row; with ground=(normal, offset) also its height < contact_height); a run of labelled rows whose first
+row in the window is frozen keeps that row's anchor and is never dropped; a run without a frozen row is dropped when shorter than
+contact_min_frames, else its anchor is the mean of its rows' solved ankles.  Consequences: a run's anchor moves from tick to tick until
+the tick that emits its first row and is constant from then on, so every emitted row of one stance carries one anchor and was solved
+and emitted under its final label; a committed run may end up shorter than contact_min_frames (its tentative tail can be un-labelled
+later); a row's label exists one tick after the row does, so with lag = 0 a row is emitted before it can be labelled; lag + 1 >=
+contact_min_frames is required, or no run could reach its length before it freezes.  ``solved``'s cost counts the contact part in
+E_data, as the device's row costs do (the offline smoother subtracts it; here contact_cost gives it).  covariance="joints" with
+contacts is mvmc_smooth_window_cov_contact: A_w carries the contact term of the labels and anchors as they stand after the tick, the
+covariance is conditional on them as the offline one is.  Measured: tools/live_smooth_contact_probe.py, INTEGRATION.md section C.5.
 """
 from __future__ import annotations
 
@@ -50,7 +69,8 @@ import numpy as np
 
 from .body_fit import MAX_DIST, MIN_SCORE
 from .sequences import frame_buckets, new_record, pose_slot, pose_tuples
-from .smoothing import ANG_ACC, ANG_VEL, COV_MU, LM_FTOL, LM_MU0, LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, check_loss, unwrap_euler_many
+from .smoothing import (ANG_ACC, ANG_VEL, CONTACT_HEIGHT, CONTACT_MIN_FRAMES, CONTACT_SPEED, CONTACT_WEIGHT, COV_MU, LM_FTOL, LM_MU0,
+                        LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, _check_contact_args, check_loss, unwrap_euler_many)
 from .tracker import T_WIDE
 
 WINDOW_MAX = 32     # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
@@ -89,6 +109,23 @@ def check_covariance(covariance, noise_px) -> Optional[float]:
     return float(noise_px)
 
 
+def check_contacts(contacts, contact_weight, contact_speed, contact_min_frames, ground, contact_height, lag) -> Optional[dict]:
+    """LiveSmoother's foot-contact arguments (host only; smoothing._check_contact_args' rules) -> None, or the launch's dict."""
+    if contacts is None:
+        return None
+    if not (isinstance(contacts, str) and contacts == "auto"):
+        raise ValueError(f"LiveSmoother: contacts must be None or \"auto\", got {contacts if isinstance(contacts, (str, bool)) else type(contacts).__name__!r}")
+    try:
+        _, wc, speed, min_frames, _, g, height = _check_contact_args("auto", contact_weight, contact_speed, contact_min_frames, 1, ground,
+                                                                     contact_height)
+    except ValueError as e:
+        raise ValueError(str(e).replace("smooth_sequences", "LiveSmoother")) from None
+    if int(lag) + 1 < min_frames:
+        raise ValueError(f"LiveSmoother: lag + 1 >= contact_min_frames required (lag {int(lag)}, contact_min_frames {min_frames}): a run "
+                         "could not reach its length before it freezes")
+    return dict(lag=int(lag), weight=wc, speed=speed, min_frames=min_frames, ground=g, height=height)
+
+
 def cov_entry(jc6, pv, ci, noise_px: Optional[float]) -> dict:
     """One emitted row's unit-variance device outputs (jcov (18,6), pvar (39,), cinfo (8,)) -> its TickOutput.cov entry."""
     status, e_data, n_res, edof = int(ci[0]), float(ci[1]), float(ci[2]), float(ci[3])
@@ -108,13 +145,16 @@ class TickOutput:
     dict(cost [E_data, E_prior at the start, E_data, E_prior at the end], trials [1 accepted / 0 rejected], stop); ``cov``: empty
     unless the smoother has covariance="joints", then track_id -> dict(joint_cov (18,3,3) m^2, joint_sigma (18,) m, param_sigma (39,),
     noise_px, edof, nres, status 0 solved / 1 singular / 2 a one-row identity (NaN arrays)) of the emitted row, conditional on the
-    window's frozen history (the module's docstring)."""
+    window's frozen history (the module's docstring); ``contact``: empty unless the smoother has contacts="auto", then track_id ->
+    dict(contact (2,) bool, anchor (2,3) m, NaN without a label) of the emitted row, and every ``solved`` entry has contact_cost =
+    [E_contact at the start, at the end] of the tick -- its cost's E_data INCLUDES the contact part, as the device's row costs do."""
 
     def __init__(self):
         self.emitted: list = []
         self.finished: list = []
         self.solved: Dict[int, dict] = {}
         self.cov: Dict[int, dict] = {}
+        self.contact: Dict[int, dict] = {}
 
 
 class _Ident:
@@ -128,6 +168,7 @@ class _Ident:
         self.params: List[Optional[np.ndarray]] = []   # a row's values once it is final (None before)
         self.joints: List[Optional[np.ndarray]] = []
         self.cov: Dict[int, tuple] = {}                # row -> (joint_sigma, param_sigma, noise_px) as emitted (covariance="joints")
+        self.contact: Dict[int, tuple] = {}            # row -> (labels (2,) bool, anchors (2,3)) once it is final (contacts="auto")
         self.n_final = 0
 
     @property
@@ -158,8 +199,11 @@ class LiveSmoother:
     def __init__(self, n_views: int, capacity: int, p_max: int = 8, window: int = 24, lag: int = 8, n_iter: int = 2,
                  root_vel: float = ROOT_VEL, root_acc: float = ROOT_ACC, ang_vel: float = ANG_VEL, ang_acc: float = ANG_ACC,
                  device=None, skeleton=None, loss: Optional[str] = None, loss_px: float = LOSS_PX, covariance: Optional[str] = None,
-                 noise_px: Optional[float] = None):
+                 noise_px: Optional[float] = None, contacts: Optional[str] = None, contact_weight: float = CONTACT_WEIGHT,
+                 contact_speed: float = CONTACT_SPEED, contact_min_frames: int = CONTACT_MIN_FRAMES, ground=None,
+                 contact_height: float = CONTACT_HEIGHT):
         self.w = check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc)
+        self._ct = check_contacts(contacts, contact_weight, contact_speed, contact_min_frames, ground, contact_height, lag)
         self._noise_px = check_covariance(covariance, noise_px)
         self._cov = covariance is not None
         loss_px = check_loss("LiveSmoother", loss, loss_px)
@@ -234,23 +278,35 @@ class LiveSmoother:
                 rows=torch.zeros((n_slots, RING, 68), dtype=torch.float64, device=d),
                 members=torch.full((n_slots, RING, self.C), -1, dtype=torch.int32, device=d),
                 count=torch.zeros((n_slots, 2), dtype=torch.int32, device=d), Pm=None)
+            if self._ct is not None:      # per row and foot a label and an anchor, beside the rows
+                self._st["clab"] = torch.zeros((n_slots, RING, 2), dtype=torch.int32, device=d)
+                self._st["canc"] = torch.full((n_slots, RING, 2, 3), math.nan, dtype=torch.float64, device=d)
         if self._Pm_dirty:
             self._st["Pm"] = torch.from_numpy(self._Pm_h.copy()).to(self._st["d"])
             self._Pm_dirty = False
         return self._st
 
     def _fetch(self, wanted):
-        """[(ident, row)] -> params (n,68), joints (n,18,3) of those rows as they stand on the device (one read-back)."""
+        """[(ident, row)] -> per row (params (68,), joints (18,3)) as they stand on the device (one read-back); with contacts also the
+        row's labels (2,) bool and anchors (2,3)."""
         import torch
 
         from . import device as dev
         if not wanted:
-            return np.zeros((0, 68)), np.zeros((0, 18, 3))
+            return []
         st = self._state()
         idx = torch.as_tensor([i.slot * RING + r % RING for i, r in wanted], dtype=torch.int64).to(st["d"])
         P = st["rows"].view(-1, 68).index_select(0, idx)
         J = dev.fk(P, self.skeleton)
-        return P.cpu().numpy(), J.cpu().numpy()
+        n = len(wanted)
+        if self._ct is None:
+            P_h, J_h = P.cpu().numpy(), J.cpu().numpy()
+            return [(P_h[k], J_h[k]) for k in range(n)]
+        host = torch.cat([P.reshape(-1), J.reshape(-1), st["clab"].view(-1, 2).index_select(0, idx).to(torch.float64).reshape(-1),
+                          st["canc"].view(-1, 6).index_select(0, idx).reshape(-1)]).cpu().numpy()
+        P_h, J_h = host[:n * 68].reshape(n, 68), host[n * 68:n * 122].reshape(n, 18, 3)
+        L_h, A_h = host[n * 122:n * 124].reshape(n, 2) != 0, host[n * 124:].reshape(n, 2, 3)
+        return [(P_h[k], J_h[k], L_h[k], A_h[k]) for k in range(n)]
 
     # -- ticks -------------------------------------------------------------------------------------------------------------------------
     def _check_table(self, key, f, inputs, meta, params, joints):
@@ -369,7 +425,11 @@ class LiveSmoother:
         st["kps"].index_copy_(0, at_d, k17)
         st["cnt"].index_copy_(0, at_d, c17)
         slot_idx = lambda wl: T(np.array([i.slot * RING + r % RING for i, r in wl], np.int64))
-        P_fin = st["rows"].view(-1, 68).index_select(0, slot_idx(want_fin)) if want_fin else None
+        i_fin = slot_idx(want_fin) if want_fin else None
+        P_fin = st["rows"].view(-1, 68).index_select(0, i_fin) if want_fin else None
+        ct = None if self._ct is None else dict(labels=st["clab"], anchors=st["canc"], **self._ct)
+        if ct is not None and want_fin:      # the finished identities' labels and anchors, gathered before the launch as their rows are
+            C_fin = (st["clab"].view(-1, 2).index_select(0, i_fin), st["canc"].view(-1, 6).index_select(0, i_fin))
         B = len(newp)
         if B:
             frame_of = np.array([p[0] for p in prob], np.int32)
@@ -384,9 +444,12 @@ class LiveSmoother:
             newp_d = torch.zeros((0, 68), dtype=torch.float64, device=d)
         parts = []
         if items:
-            info = dev.smooth_window(st["kps"], st["Pm"], T(np.array(items, np.int32)), newp_d, mem_d, st["rows"], st["members"],
-                                     st["count"], W, self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton, **self._rob)
-            parts.append(info.reshape(-1))
+            args = (st["kps"], st["Pm"], T(np.array(items, np.int32)), newp_d, mem_d, st["rows"], st["members"], st["count"], W,
+                    self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton)
+            if ct is None:
+                parts.append(dev.smooth_window(*args, **self._rob).reshape(-1))
+            else:
+                parts += [p.reshape(-1) for p in dev.smooth_window(*args, **self._rob, contact=ct)]
         # the covariance of the emitted rows: ONE launch for all of them, none when nothing is emitted (or it is not asked for)
         cov_of = [a for a, (key, idn, f) in enumerate(solved_of) if f - self.lag - idn.f0 >= 0] if self._cov else []
         if cov_of:
@@ -394,12 +457,18 @@ class LiveSmoother:
                       for k, a in enumerate(cov_of)]
             parts += [p.reshape(-1) for p in dev.smooth_window_cov(st["kps"], st["Pm"], T(np.array(citems, np.int32)), st["rows"],
                                                                    st["members"], st["count"], W, self.w, COV_MU,
-                                                                   self._noise_px is None, self.skeleton, **self._rob)]
-        Pg = [p for p in (P_fin, st["rows"].view(-1, 68).index_select(0, slot_idx(want)) if want else None) if p is not None]
+                                                                   self._noise_px is None, self.skeleton, **self._rob,
+                                                                   **({} if ct is None else dict(contact=ct)))]
+        i_want = slot_idx(want) if want else None
+        Pg = [p for p in (P_fin, st["rows"].view(-1, 68).index_select(0, i_want) if want else None) if p is not None]
         n_rows = len(want_fin) + len(want)
         if n_rows:
             Pall = torch.cat(Pg) if len(Pg) > 1 else Pg[0]
             parts += [Pall.reshape(-1), dev.fk(Pall, self.skeleton).reshape(-1)]
+            if ct is not None:      # the same rows' labels and anchors join the read-back
+                Lg = ([C_fin[0]] if want_fin else []) + ([st["clab"].view(-1, 2).index_select(0, i_want)] if want else [])
+                Ag = ([C_fin[1]] if want_fin else []) + ([st["canc"].view(-1, 6).index_select(0, i_want)] if want else [])
+                parts += [torch.cat(Lg).to(torch.float64).reshape(-1), torch.cat(Ag).reshape(-1)]
         parts += [mem_d.to(torch.float64).reshape(-1), nv_d.to(torch.float64).reshape(-1)]
         host = torch.cat(parts).cpu().numpy()      # the tick's one synchronisation
         t_launch = time.perf_counter()
@@ -412,10 +481,13 @@ class LiveSmoother:
             at += n
             return a
         inf_h = take(len(items) * 16, (len(items), 16))
+        cin_h = take(len(items) * 10, (len(items), 10)) if ct is not None and items else None
         nc = len(cov_of)
         jc_h, pv_h, ci_h = take(nc * 108, (nc, 18, 6)), take(nc * 39, (nc, 39)), take(nc * 8, (nc, 8))
         P_h = take(n_rows * 68, (n_rows, 68))
         J_h = take(n_rows * 54, (n_rows, 18, 3))
+        if ct is not None:
+            L_h, A_h = take(n_rows * 2, (n_rows, 2)) != 0, take(n_rows * 6, (n_rows, 2, 3))
         mem_h = take(B * C, (B, C)).astype(np.int64)
         nv_h = take(B, (B,)).astype(np.int64)
         sel_h = pose_slot(mem_h, self.P)
@@ -429,6 +501,8 @@ class LiveSmoother:
             for r in range(idn.n_final, keep):
                 k = got[(id(idn), r)]
                 idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
+                if ct is not None:
+                    idn.contact[r] = (L_h[k].copy(), A_h[k].copy())
             idn.n_final = keep
             out[key].finished.append(self._record(idn, keep, 3))
         emit = []
@@ -436,12 +510,18 @@ class LiveSmoother:
             for r in range(was_final[a], idn.n_final):
                 k = got[(id(idn), r)]
                 idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
+                if ct is not None:
+                    idn.contact[r] = (L_h[k].copy(), A_h[k].copy())
             if idn.n >= 2:
                 n_t = int(inf_h[a, 4])
                 if int(inf_h[a, 7]) == 6:
                     raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed item")
                 out[key].solved[idn.tid] = dict(cost=inf_h[a, :4].copy(), trials=[int(v) for v in inf_h[a, 8:8 + n_t]], stop=int(inf_h[a, 7]))
+                if ct is not None:
+                    out[key].solved[idn.tid]["contact_cost"] = cin_h[a, 8:10].copy()
             r = f - self.lag - idn.f0
+            if r >= 0 and ct is not None:
+                out[key].contact[idn.tid] = dict(contact=cin_h[a, :2] != 0, anchor=cin_h[a, 2:8].reshape(2, 3).copy())
             if r >= 0:
                 emit.append((key, idn.tid, f - self.lag, got[(id(idn), r)], bool(idn.filled[r]), int(idn.views[r])))
         for k, a in enumerate(cov_of):
@@ -516,14 +596,18 @@ class LiveSmoother:
     def _record(self, idn: _Ident, n: int, state: Optional[int] = None, live=None):
         """The identity's rows 0..n-1 as an MvTracklet-like record (save_bvh takes it); ``live``: values of the rows not final yet."""
         from .motion_capture import TrackState
-        rows = [(idn.params[r], idn.joints[r]) if idn.params[r] is not None else live[r] for r in range(n)]
-        poses = pose_tuples(idn.f0 + np.arange(n), np.array([p for p, _ in rows]), np.array([j for _, j in rows], np.float64))
+        rows = [(idn.params[r], idn.joints[r]) + (idn.contact[r] if self._ct is not None else ()) if idn.params[r] is not None else live[r]
+                for r in range(n)]
+        poses = pose_tuples(idn.f0 + np.arange(n), np.array([q[0] for q in rows]), np.array([q[1] for q in rows], np.float64))
         t = new_record(idn.tid, poses, state=TrackState(idn.state if state is None else state), hits=idn.hits,
                        time_since_update=idn.n - idn.last_data())
         t.smooth_filled = np.array(idn.filled[:n], bool)
         t.smooth_views = np.array(idn.views[:n], np.int32)
         t.smooth_select = np.array(idn.sel[:n], np.int32).reshape(n, self.C)
         t.smooth_final = np.arange(n) < idn.n_final
+        if self._ct is not None:      # the rows' stored labels and anchors as they stand
+            t.smooth_contact = np.array([q[2] for q in rows], bool).reshape(n, 2)
+            t.smooth_contact_anchor = np.array([q[3] for q in rows], np.float64).reshape(n, 2, 3)
         if self._cov:      # per row the values recorded when it was emitted; NaN on the rows that never were
             t.smooth_joint_sigma, t.smooth_param_sigma, t.smooth_noise_px = np.full((n, 18), np.nan), np.full((n, 39), np.nan), np.full(n, np.nan)
             for r, (js, ps, s) in idn.cov.items():
@@ -533,25 +617,27 @@ class LiveSmoother:
 
     def tracklets(self, key) -> list:
         """The session's live identities as records f0..newest without holes: poses, smooth_filled, smooth_views, smooth_select,
-        smooth_final (the row has left the window).  Reads the rows that are not final back from the device.  With covariance="joints"
+        smooth_final (the row has left the window).  Reads the rows that are not final back from the device.  With contacts="auto"
+        (here, in ``finished`` and from close_session) also smooth_contact (n,2) bool and smooth_contact_anchor (n,2,3), the rows'
+        stored labels and anchors as they stand (those of the last <= lag rows are still tentative).  With covariance="joints"
         (here, in ``finished`` and from close_session) also smooth_joint_sigma (n,18), smooth_param_sigma (n,39), smooth_noise_px (n,): per
         row the values of TickOutput.cov when the row was emitted, NaN on the rows that never were (the last <= lag rows of a record,
         and the rows a jump of the frame index skipped)."""
         sess = self._session(key, "tracklets")
         want = [(idn, r) for idn in sess.ids.values() for r in range(idn.n_final, idn.n)]
-        P, J = self._fetch(want)
         live = {}
-        for k, (idn, r) in enumerate(want):
-            live.setdefault(id(idn), {})[r] = (P[k], J[k])
+        for (idn, r), q in zip(want, self._fetch(want)):
+            live.setdefault(id(idn), {})[r] = q
         return [self._record(idn, idn.n, live=live.get(id(idn))) for idn in sess.ids.values()]
 
     def close_session(self, key) -> list:
         """Ends a session: every live identity is finished (rows after its last data row dropped) and its record returned."""
         sess = self._session(key, "close_session")
         want = [(idn, r) for idn in sess.ids.values() for r in range(idn.n_final, idn.last_data())]
-        P, J = self._fetch(want)
-        for k, (idn, r) in enumerate(want):
-            idn.params[r], idn.joints[r] = P[k].copy(), J[k].copy()
+        for (idn, r), q in zip(want, self._fetch(want)):
+            idn.params[r], idn.joints[r] = q[0].copy(), q[1].copy()
+            if self._ct is not None:
+                idn.contact[r] = (q[2].copy(), q[3].copy())
         done = []
         for idn in sess.ids.values():
             idn.n_final = idn.last_data()

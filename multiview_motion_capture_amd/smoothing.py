@@ -307,8 +307,9 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     on them, and the E_data behind an estimated smooth_noise_px includes E_contact.  timings gets a "contacts" part (FK, the
     anchors launch and the host's share); "blocks" and "solve" hold every round's.  What this is not: the 18-joint skeleton has no
     toes, so an ankle that pivots during push-off is held too rigidly if it is labelled; the anchor is not forced onto a floor
-    plane; contact_speed is per frame, so it depends on the frame rate.  LiveSmoother has no contacts: a fixed-lag window does not
-    know a run's future."""
+    plane; contact_speed is per frame, so it depends on the frame rate.  LiveSmoother(contacts="auto") is the live twin: a fixed-lag
+    window does not know a run's future, so there an anchor is re-estimated while its run is younger than the emitted row and frozen
+    from the tick that emits the run's first row (live_smoothing.py)."""
     t_start = time.perf_counter()
     w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
     noise_px = _check_covariance(covariance, noise_px)
