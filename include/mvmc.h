@@ -702,6 +702,28 @@ int mvmc_smooth_contact_anchors(const double* joints, const int32_t* id_lo, int 
                                 int min_run, int use_ground, const double* ground, double height, int32_t* cmask, double* anchors,
                                 int32_t* ctl, mvmcStream_t stream);
 
+/* ---- a floor under the contacts of the trajectory smoother (smoothing.py: floor=; restated in tests/smooth_floor_np.py).  Per sequence
+ * a unit floor normal n (T = I - n n^T projects into the floor), per identity ONE level h (metres along n) shared by all its runs and
+ * both feet; over the labelled (row, foot) pairs L of the contacts above
+ *   E_contact = 1/2 contact_weight sum_L |T (X_f(x_t) - a_run)|^2 + 1/2 floor_weight sum_L (n . X_f(x_t) - h)^2
+ * h is minimised in closed form too: the mean of n . X_f over L.  The stored anchor of a row is the point T mean_run + n h on the
+ * plane, so with c = X_f - a (n . c = n . X_f - h) the row's term is 1/2 wc |c|^2 + 1/2 (wf - wc)(n . c)^2.
+ * mvmc_smooth_blocks_floor is mvmc_smooth_blocks_contact with normals (n_rigs, 3) f64, read through rig_of[row], and floor_weight
+ * finite and >= 0 (else MVMC_ERR_ARG before any HIP call): the labelled row's W_K += wc I + (wf - wc) n n^T, t_K += wc c +
+ * (wf - wc)(n . c) n, E += the term, in the lane of the contact term, with no LDS and no barrier more.  A row whose sequence has a NaN
+ * normal, or whose mask is (0, 0), gets mvmc_smooth_blocks_contact's block bit for bit.
+ * mvmc_smooth_floor_anchors, ONE launch after mvmc_smooth_contact_anchors (which still makes the labels and the run means), the same
+ * two waves per identity: levels (n_ids) f64 out, h = the mean of n . ankle over L, summed in ONE fixed order -- the left foot's rows
+ * ascending, then the right foot's --, n = normals[rig_of[the identity's first row]]; every labelled row's anchor a is replaced by
+ * a - n (n . a - h).  An identity without a labelled row or with a NaN normal: level NaN, its anchors untouched.  cmask is read only.
+ * An identity's numbers depend on nothing else in the launch; there is no limit on its rows. ---- */
+int mvmc_smooth_blocks_floor(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                             const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of, const int32_t* ctl,
+                             int n_frames, double* blk, int loss, double loss_px, const int32_t* cmask, const double* anchors,
+                             double contact_weight, const double* normals, double floor_weight, mvmcStream_t stream);
+int mvmc_smooth_floor_anchors(const double* joints, const int32_t* id_lo, int n_ids, int n_frames, const int32_t* rig_of,
+                              const double* normals, const int32_t* cmask, double* anchors, double* levels, mvmcStream_t stream);
+
 /* ---- foot contacts of the live smoother (live_smoothing.py: contacts="auto"; restated in tests/live_smooth_contact_np.py).  Two more
  * state arrays stay on the device between ticks, per identity slot and ring position: contact (n_slots, MVMC_SMOOTH_WIN_RING, 2) i32,
  * the row's label per foot, and anchors (n_slots, MVMC_SMOOTH_WIN_RING, 2, 3) f64, NaN without a label.

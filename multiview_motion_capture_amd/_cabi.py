@@ -47,6 +47,7 @@ SYMBOLS = (
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_cov", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
     "mvmc_smooth_blocks_robust", "mvmc_smooth_obs_weights", "mvmc_smooth_window_robust",
     "mvmc_smooth_blocks_contact", "mvmc_smooth_contact_anchors",
+    "mvmc_smooth_blocks_floor", "mvmc_smooth_floor_anchors",
     "mvmc_smooth_window_cov_work_doubles", "mvmc_smooth_window_cov",
     "mvmc_smooth_window_contact", "mvmc_smooth_window_cov_contact",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
@@ -173,6 +174,8 @@ def load():
                                       f64, f64, vp, vp, C.c_longlong, i32, f64, vp],
         "mvmc_smooth_blocks_contact": [SK, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, f64, vp, vp, f64, vp],
         "mvmc_smooth_contact_anchors": [vp, vp, i32, i32, i32, f64, i32, i32, C.POINTER(C.c_double), f64, vp, vp, vp, vp],
+        "mvmc_smooth_blocks_floor": [SK, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, f64, vp, vp, f64, vp, f64, vp],
+        "mvmc_smooth_floor_anchors": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp],
         "mvmc_smooth_window_cov_work_doubles": [i32, i32],
         "mvmc_smooth_window_cov": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i32, i32, f64, vp,
                                    C.c_longlong, vp, vp, vp, vp],

@@ -8,7 +8,8 @@
 //           the frame into one of two block buffers (the other holds the blocks of the accepted point); with a robust loss
 //           (mvmc_smooth_blocks_robust) the blocks of the reweighted model, the same layout: J^T W J, J^T W r, sum s^2 rho; with foot
 //           contacts (mvmc_smooth_blocks_contact) the labelled rows' 1/2 wc |X_ankle - a|^2 joins the ankle's W_k, t_k and E, the same
-//           layout again (the labels and anchors come from csrc/mvmc_smooth_contact.hip between two rounds of the solve);
+//           layout again (the labels and anchors come from csrc/mvmc_smooth_contact.hip between two rounds of the solve); with a floor
+//           (mvmc_smooth_blocks_floor) that term weighs the part along the sequence's floor normal with a second weight;
 //   step    ONE 256-lane workgroup per identity: the accept / reject decision on the last trial (E summed in a fixed order), then one
 //           block-banded solve of (A + mu diag(A)) d = -g over all the identity's frames (mvmc_smooth_sweep.h, the sweep the live
 //           smoother runs too; the factor goes to the caller's workspace), and the next trial point.
@@ -57,6 +58,28 @@ __global__ void __launch_bounds__(64) smooth_blocks_contact_kernel(Ik1Tables T, 
     const int buf = 1 - uni((int)ctl[id * 4 + 1]);
     sm_row_block<LOSS, true>(T, L, kps17, Pmats + (size_t)rig_of[f] * C * 12, C, Pmax, members + (size_t)f * C, xe + (size_t)f * 68,
                              blk + ((size_t)buf * n_frames + f) * SM_BLK, loss_px, cmask + (size_t)f * 2, anchors + (size_t)f * 6, wc);
+}
+
+// The contact launch with a floor (include/mvmc.h: mvmc_smooth_blocks_floor): normals (n_rigs,3) the unit floor normal of every
+// sequence, NaN where it has none, wf = floor_weight.  Again a kernel of its own: the launches without a floor keep theirs.
+template <int LOSS>
+__global__ void __launch_bounds__(64) smooth_blocks_floor_kernel(Ik1Tables T, const double* __restrict__ kps17,
+                                                                 const double* __restrict__ Pmats, int C, int Pmax,
+                                                                 const int32_t* __restrict__ rig_of, const int32_t* __restrict__ members,
+                                                                 const double* __restrict__ xe, const int32_t* __restrict__ id_of,
+                                                                 const int32_t* __restrict__ ctl, int n_frames, double* __restrict__ blk,
+                                                                 double loss_px, const int32_t* __restrict__ cmask,
+                                                                 const double* __restrict__ anchors, double wc,
+                                                                 const double* __restrict__ normals, double wf) {
+    __shared__ SmBlkLds L;
+    const int f = blockIdx.x;
+    const int id = uni((int)id_of[f]);
+    if (uni((int)ctl[id * 4]) != 0) return;
+    const int buf = 1 - uni((int)ctl[id * 4 + 1]);
+    const int rig = uni((int)rig_of[f]);
+    sm_row_block<LOSS, true, true>(T, L, kps17, Pmats + (size_t)rig * C * 12, C, Pmax, members + (size_t)f * C, xe + (size_t)f * 68,
+                                   blk + ((size_t)buf * n_frames + f) * SM_BLK, loss_px, cmask + (size_t)f * 2, anchors + (size_t)f * 6,
+                                   wc, normals + (size_t)rig * 3, wf);
 }
 
 // ---- weights ----
@@ -210,6 +233,28 @@ extern "C" int mvmc_smooth_blocks_contact(const mvmcSkeleton* skel_host, const d
                                                     : smooth_blocks_contact_kernel<MVMC_SMOOTH_LOSS_NONE>;
     hipLaunchKernelGGL(kernel, dim3(n_frames), dim3(64), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, rig_of, members, x,
                        id_of, ctl, n_frames, blk, loss_px, cmask, anchors, contact_weight);
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
+}
+
+extern "C" int mvmc_smooth_blocks_floor(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats,
+                                        const int32_t* rig_of, const int32_t* members, const double* x, const int32_t* id_of,
+                                        const int32_t* ctl, int n_frames, double* blk, int loss, double loss_px, const int32_t* cmask,
+                                        const double* anchors, double contact_weight, const double* normals, double floor_weight,
+                                        mvmcStream_t stream) {
+    if (!skel_host || n_frames < 0 || n_views <= 0 || n_views > MVMC_SMOOTH_MAX_VIEWS || p_max <= 0) return MVMC_ERR_ARG;
+    if (!sm_loss_ok(loss, loss_px)) return MVMC_ERR_ARG;
+    if (!(contact_weight >= 0.0 && contact_weight <= 1.7976931348623157e308)) return MVMC_ERR_ARG;   // (NaN fails both)
+    if (!(floor_weight >= 0.0 && floor_weight <= 1.7976931348623157e308)) return MVMC_ERR_ARG;
+    if (n_frames == 0) return MVMC_OK;
+    if (!kps17 || !Pmats || !rig_of || !members || !x || !id_of || !ctl || !blk || !cmask || !anchors || !normals) return MVMC_ERR_ARG;
+    Ik1Tables T;
+    if (!sm_tables(skel_host, &T)) return MVMC_ERR_UNSUPPORTED;
+    auto kernel = loss == MVMC_SMOOTH_LOSS_HUBER    ? smooth_blocks_floor_kernel<MVMC_SMOOTH_LOSS_HUBER>
+                  : loss == MVMC_SMOOTH_LOSS_CAUCHY ? smooth_blocks_floor_kernel<MVMC_SMOOTH_LOSS_CAUCHY>
+                                                    : smooth_blocks_floor_kernel<MVMC_SMOOTH_LOSS_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(n_frames), dim3(64), 0, (hipStream_t)stream, T, kps17, Pmats, n_views, p_max, rig_of, members, x,
+                       id_of, ctl, n_frames, blk, loss_px, cmask, anchors, contact_weight, normals, floor_weight);
     MVMC_CHECK_LAUNCH();
     return MVMC_OK;
 }

@@ -87,7 +87,93 @@ __global__ void __launch_bounds__(SC_THREADS) smooth_contact_anchors_kernel(cons
     if (threadIdx.x == 0 && (has_run[0] | has_run[1]) != 0) ctl[id * 4] = 0;
 }
 
+// The floor of the contacts (include/mvmc.h: mvmc_smooth_floor_anchors; restated in tests/smooth_floor_np.py: level, project), after the
+// launch above: per identity the level h = the mean of n . ankle over its labelled (row, foot) pairs, and every labelled row's anchor
+// moved onto the plane n . a = h along n.  The same workgroup of two waves per identity, wave f = foot f:
+//   level    ONE running sum in the fixed order left foot's rows ascending, then the right foot's: wave 0 walks its labels in chunks of
+//            64 (a ballot, then the bits in row order with the sum in a wave-uniform register), hands sum and count over through LDS,
+//            and wave 1 carries on from them -- two barriers, any number of rows;
+//   project  a lane per labelled row of the wave's foot: a -= n (n . a - h).
+// n = normals[rig_of[first row]]; a NaN normal or no labelled row: level NaN, nothing else is written.
+__global__ void __launch_bounds__(SC_THREADS) smooth_floor_anchors_kernel(const double* __restrict__ joints,
+                                                                          const int32_t* __restrict__ id_lo,
+                                                                          const int32_t* __restrict__ rig_of,
+                                                                          const double* __restrict__ normals,
+                                                                          const int32_t* __restrict__ cmask, double* __restrict__ anchors,
+                                                                          double* __restrict__ levels) {
+    __shared__ double part_s;
+    __shared__ int part_n;
+    const int id = blockIdx.x, lane = threadIdx.x & 63, foot = uni((int)(threadIdx.x >> 6));
+    const int lo = uni((int)id_lo[id]), m = uni((int)id_lo[id + 1]) - lo;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    if (m <= 0) {   // (uniform for the workgroup: no barrier is skipped by a part of it)
+        if (threadIdx.x == 0) levels[id] = nan;
+        return;
+    }
+    const double* nr = normals + (size_t)uni((int)rig_of[lo]) * 3;
+    const double n0 = uni(nr[0]), n1 = uni(nr[1]), n2 = uni(nr[2]);
+    if (!(n0 == n0 && n1 == n1 && n2 == n2)) {
+        if (threadIdx.x == 0) levels[id] = nan;
+        return;
+    }
+    const double* p = joints + (size_t)lo * 54 + 3 * (foot == 0 ? MVMC_SMOOTH_FOOT_L : MVMC_SMOOTH_FOOT_R);   // row t: p + 54 t
+    const int32_t* cm = cmask + (size_t)lo * 2 + foot;                                                      // row t: cm[2 t]
+    double* an = anchors + ((size_t)lo * 2 + foot) * 3;                                                     // row t: an + 6 t
+    double s = 0.0;
+    int cnt = 0;
+    auto walk = [&]() {
+        for (int base = 0; base < m; base += 64) {
+            const int t = base + lane;
+            const bool on = t < m && cm[(size_t)2 * t] != 0;
+            const double q = on ? n0 * p[(size_t)54 * t] + n1 * p[(size_t)54 * t + 1] + n2 * p[(size_t)54 * t + 2] : 0.0;
+            const unsigned long long bal = __ballot(on);
+            const unsigned blo = (unsigned)uni((int)(unsigned)bal), bhi = (unsigned)uni((int)(unsigned)(bal >> 32));
+            const int c = m - base < 64 ? m - base : 64;
+            for (int i = 0; i < c; ++i) {   // wave-uniform: every lane walks the same bits and holds the same sum
+                const double r = __shfl(q, i);
+                if (((i < 32 ? blo >> i : bhi >> (i - 32)) & 1u) != 0u) { s += r; ++cnt; }
+            }
+        }
+    };
+    if (foot == 0) {
+        walk();
+        if (lane == 0) { part_s = s; part_n = cnt; }
+    }
+    __syncthreads();
+    if (foot == 1) {
+        s = part_s; cnt = part_n;
+        walk();
+        if (lane == 0) { part_s = s; part_n = cnt; }   // (wave 0 reads them after the next barrier only)
+    }
+    __syncthreads();
+    s = part_s; cnt = part_n;
+    if (cnt == 0) {
+        if (threadIdx.x == 0) levels[id] = nan;
+        return;
+    }
+    const double h = s / (double)cnt;
+    if (threadIdx.x == 0) levels[id] = h;
+    for (int t = lane; t < m; t += 64) {
+        if (cm[(size_t)2 * t] == 0) continue;
+        double* a = an + (size_t)6 * t;
+        const double e = (n0 * a[0] + n1 * a[1] + n2 * a[2]) - h;
+        a[0] -= n0 * e; a[1] -= n1 * e; a[2] -= n2 * e;
+    }
+}
+
 }  // namespace
+
+extern "C" int mvmc_smooth_floor_anchors(const double* joints, const int32_t* id_lo, int n_ids, int n_frames, const int32_t* rig_of,
+                                         const double* normals, const int32_t* cmask, double* anchors, double* levels,
+                                         mvmcStream_t stream) {
+    if (n_ids < 0 || n_frames < 0) return MVMC_ERR_ARG;
+    if (n_ids == 0) return MVMC_OK;
+    if (!joints || !id_lo || !rig_of || !normals || !cmask || !anchors || !levels) return MVMC_ERR_ARG;
+    hipLaunchKernelGGL(smooth_floor_anchors_kernel, dim3(n_ids), dim3(SC_THREADS), 0, (hipStream_t)stream, joints, id_lo, rig_of, normals,
+                       cmask, anchors, levels);
+    MVMC_CHECK_LAUNCH();
+    return MVMC_OK;
+}
 
 extern "C" int mvmc_smooth_contact_anchors(const double* joints, const int32_t* id_lo, int n_ids, int n_frames, int detect, double speed,
                                            int min_run, int use_ground, const double* ground, double height, int32_t* cmask,

@@ -126,15 +126,26 @@ __device__ __forceinline__ void sm_rho_w(double e2, double delta, double& rho, d
 // (+ wc (X_K - a)) after the views' reduction, in the lane that owns them, and E (left, then right); it stays outside the loss.  A
 // row whose mask is (0, 0) runs the code without the term, operation for operation; a row with a mask and no view runs the whole row
 // with an empty view loop instead of the no-data return.
-template <int LOSS, bool CONTACT = false>
+// FLOOR (default false: nrm and wf are not read, the code is the one without the parameter; needs CONTACT): the term is anisotropic
+// about the unit floor normal nrm (3) of the row's sequence (include/mvmc.h: mvmc_smooth_blocks_floor): with c = X_K - a,
+// W_k += wc I + (wf - wc) n n^T, t_k += wc c + (wf - wc)(n . c) n, E += 1/2 wc |c|^2 + 1/2 (wf - wc)(n . c)^2 -- the CONTACT term
+// first, operation for operation, then the rank-one part in the same lane; no LDS and no barrier more.  A NaN normal: CONTACT's row.
+template <int LOSS, bool CONTACT = false, bool FLOOR = false>
 __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, const double* __restrict__ kps17,
                                              const double* __restrict__ Prig, int C, int Pmax, const int32_t* __restrict__ members,
                                              const double* __restrict__ x, double* __restrict__ out, double loss_px,
                                              const int32_t* __restrict__ cmask = nullptr, const double* __restrict__ anchors = nullptr,
-                                             double wc = 0.0) {
+                                             double wc = 0.0, const double* __restrict__ nrm = nullptr, double wf = 0.0) {
+    static_assert(CONTACT || !FLOOR, "the floor is a form of the contact term");
     const int lane = threadIdx.x & 63;
     bool on[2] = {false, false};
     if constexpr (CONTACT) { on[0] = uni((int)cmask[0]) != 0; on[1] = uni((int)cmask[1]) != 0; }
+    bool fl = false;
+    double n0 = 0.0, n1 = 0.0, n2 = 0.0;
+    if constexpr (FLOOR) {
+        n0 = uni(nrm[0]); n1 = uni(nrm[1]); n2 = uni(nrm[2]);
+        fl = n0 == n0 && n1 == n1 && n2 == n2;
+    }
     if (lane == 0) {
         int n = 0;
         for (int c = 0; c < C; ++c) {
@@ -205,6 +216,17 @@ __device__ __forceinline__ void sm_row_block(const Ik1Tables& T, SmBlkLds& L, co
             if (lane < NOBS && kIkSkel[lane] == K) {         // the lane of the ankle's observed-joint slot
                 o[0] += wc; o[3] += wc; o[5] += wc;
                 o[6] += wc * c0; o[7] += wc * c1; o[8] += wc * c2;
+            }
+            if constexpr (FLOOR) {
+                if (fl) {   // the rank-one part along the normal
+                    const double dw = wf - wc, nc = n0 * c0 + n1 * c1 + n2 * c2;
+                    E += 0.5 * dw * (nc * nc);
+                    if (lane < NOBS && kIkSkel[lane] == K) {
+                        o[0] += dw * (n0 * n0); o[1] += dw * (n0 * n1); o[2] += dw * (n0 * n2);
+                        o[3] += dw * (n1 * n1); o[4] += dw * (n1 * n2); o[5] += dw * (n2 * n2);
+                        o[6] += dw * nc * n0; o[7] += dw * nc * n1; o[8] += dw * nc * n2;
+                    }
+                }
             }
         }
     }

@@ -437,11 +437,14 @@ def smooth_loss_args(loss, loss_px, what: str):
 def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,
                   id_of: torch.Tensor, ctl: torch.Tensor, blk: torch.Tensor, skeleton: Optional[MvmcSkeleton] = None, *,
                   loss: Optional[str] = None, loss_px: Optional[float] = None, cmask: Optional[torch.Tensor] = None,
-                  anchors: Optional[torch.Tensor] = None, contact_weight: Optional[float] = None) -> None:
+                  anchors: Optional[torch.Tensor] = None, contact_weight: Optional[float] = None,
+                  normals: Optional[torch.Tensor] = None, floor_weight: Optional[float] = None) -> None:
     """The data blocks of the trajectory smoother at x (include/mvmc.h: mvmc_smooth_blocks), one wave per row, into blk (2,N,820).
     loss "huber" / "cauchy" with loss_px > 0 (pixels): the blocks of the reweighted model, J^T W J, J^T W r and sum s^2 rho
     (mvmc_smooth_blocks_robust); loss=None is the plain entry.  cmask (N,2) i32 with anchors (N,2,3) f64 and contact_weight >= 0:
-    the blocks with the foot-contact term of the labelled rows (mvmc_smooth_blocks_contact), with or without a loss."""
+    the blocks with the foot-contact term of the labelled rows (mvmc_smooth_blocks_contact), with or without a loss.  With them,
+    normals (R,3) f64 (a unit floor normal per rig, NaN: none) and floor_weight >= 0: the term about the floor
+    (mvmc_smooth_blocks_floor)."""
     sk = skeleton if skeleton is not None else make_skeleton()
     F, Cn, P = kps17.shape[:3]
     _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
@@ -453,12 +456,20 @@ def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor
     _req(members, torch.int32, "members", (N, Cn))
     _req(ctl, torch.int32, "ctl", (None, 4))
     _req(blk, torch.float64, "blk", (2, N, _cabi.SMOOTH_BLOCK_DOUBLES))
+    if (normals is None) != (floor_weight is None) or (normals is not None and cmask is None):
+        raise ValueError("smooth_blocks: normals and floor_weight go together, with cmask, anchors and contact_weight")
     if cmask is not None or anchors is not None or contact_weight is not None:
         if cmask is None or anchors is None or contact_weight is None:
             raise ValueError("smooth_blocks: cmask, anchors and contact_weight go together")
         _req(cmask, torch.int32, "cmask", (N, 2))
         _req(anchors, torch.float64, "anchors", (N, 2, 3))
         code, px = smooth_loss_args(loss, loss_px, "smooth_blocks")
+        if normals is not None:
+            _req(normals, torch.float64, "normals", (Pmats.shape[0], 3))
+            check(_cabi.load().mvmc_smooth_blocks_floor(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
+                                                        _p(ctl), N, _p(blk), code, px, _p(cmask), _p(anchors), float(contact_weight),
+                                                        _p(normals), float(floor_weight), _stream()), "mvmc_smooth_blocks_floor")
+            return
         check(_cabi.load().mvmc_smooth_blocks_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
                                                       _p(ctl), N, _p(blk), code, px, _p(cmask), _p(anchors), float(contact_weight),
                                                       _stream()), "mvmc_smooth_blocks_contact")
@@ -491,6 +502,25 @@ def smooth_contact_anchors(joints: torch.Tensor, id_lo: torch.Tensor, cmask: tor
     check(_cabi.load().mvmc_smooth_contact_anchors(_p(joints), _p(id_lo), n_ids, N, int(bool(detect)), float(speed), int(min_run),
                                                    int(g is not None), g, float(height), _p(cmask), _p(anchors), _p(ctl), _stream()),
           "mvmc_smooth_contact_anchors")
+
+
+def smooth_floor_anchors(joints: torch.Tensor, id_lo: torch.Tensor, rig_of: torch.Tensor, normals: torch.Tensor, cmask: torch.Tensor,
+                         anchors: torch.Tensor, levels: torch.Tensor) -> None:
+    """The floor level of every identity and its anchors moved onto the floor (include/mvmc.h: mvmc_smooth_floor_anchors), one launch
+    after smooth_contact_anchors.  joints (N,18,3), id_lo (n_ids + 1,) i32, rig_of (N,) i32, normals (R,3) f64 unit or NaN, cmask
+    (N,2) i32 read; anchors (N,2,3) f64 in place, levels (n_ids,) f64 out: NaN (and the anchors untouched) for an identity without
+    a labelled row or with a NaN normal."""
+    N = joints.shape[0]
+    n_ids = id_lo.shape[0] - 1
+    _req(joints, torch.float64, "joints", (N, 18, 3))
+    _req(id_lo, torch.int32, "id_lo", (n_ids + 1,))
+    _req(rig_of, torch.int32, "rig_of", (N,))
+    _req(normals, torch.float64, "normals", (None, 3))
+    _req(cmask, torch.int32, "cmask", (N, 2))
+    _req(anchors, torch.float64, "anchors", (N, 2, 3))
+    _req(levels, torch.float64, "levels", (n_ids,))
+    check(_cabi.load().mvmc_smooth_floor_anchors(_p(joints), _p(id_lo), n_ids, N, _p(rig_of), _p(normals), _p(cmask), _p(anchors),
+                                                 _p(levels), _stream()), "mvmc_smooth_floor_anchors")
 
 
 def smooth_obs_weights(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, x: torch.Tensor,

@@ -31,12 +31,17 @@ the selection still comes first.  It is for the keypoint the gate cannot see: on
 contacts="auto" or given labels (default None: nothing of it runs) adds foot contacts: per run of consecutive rows on which an ankle
 is labelled as planted, 1/2 contact_weight |ankle(x_t) - a|^2 with one anchor a per run, minimised over x and the anchors in
 alternation: further rounds of the same solve, the anchors (and with "auto" the labels) re-made between them by one launch.  It is
-for the foot that slides under a retargeted character; smooth_sequences' docstring has the model and what it is not.
+for the foot that slides under a retargeted character; smooth_sequences' docstring has the model and what it is not.  floor= (a
+normal per sequence, with contacts) puts all the planted feet of one identity on one plane: the term weighs the part along the normal
+with floor_weight about one level per identity, a further unknown in closed form; estimate_floor() finds the normal from the records
+of a first call.
 
 Device code: csrc/mvmc_smooth.hip (include/mvmc.h: mvmc_smooth_blocks, mvmc_smooth_step; with a loss mvmc_smooth_blocks_robust and
-mvmc_smooth_obs_weights; with contacts mvmc_smooth_blocks_contact and csrc/mvmc_smooth_contact.hip: mvmc_smooth_contact_anchors;
-selection: mvmc_body_observe), the optional per-frame covariance csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov);
-NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py, tests/smooth_robust_np.py, tests/smooth_contact_np.py.
+mvmc_smooth_obs_weights; with contacts mvmc_smooth_blocks_contact and csrc/mvmc_smooth_contact.hip: mvmc_smooth_contact_anchors; with a
+floor mvmc_smooth_blocks_floor and mvmc_smooth_floor_anchors; selection: mvmc_body_observe), the optional per-frame covariance
+csrc/mvmc_smooth_cov.hip (mvmc_smooth_cov);
+NumPy restatement: tests/smooth_np.py, tests/smooth_cov_np.py, tests/smooth_robust_np.py, tests/smooth_contact_np.py,
+tests/smooth_floor_np.py.
 Sequences with the same number of cameras share every launch, each with its own rig.
 """
 from __future__ import annotations
@@ -217,6 +222,36 @@ def _check_contact_args(contacts, contact_weight, contact_speed, contact_min_fra
     return auto, float(contact_weight), float(contact_speed), int(contact_min_frames), int(contact_rounds), g, float(contact_height)
 
 
+def _check_floor(floor, floor_weight, contacts, contact_weight, n_seq):
+    """floor= and floor_weight= (host only) -> (per sequence None or the unit normal (3,), floor weight)."""
+    who = "smooth_sequences"
+    if contacts is None:
+        raise ValueError(f"{who}: floor needs contacts: it is the plane the planted feet stand on")
+    if floor_weight is None:
+        wf = float(contact_weight)
+    elif not _number(floor_weight) or not math.isfinite(floor_weight) or floor_weight < 0:
+        raise ValueError(f"{who}: floor_weight must be None or a finite number >= 0, got {floor_weight!r}")
+    else:
+        wf = float(floor_weight)
+
+    def normal(v, what):
+        try:
+            n = np.array(v, np.float64)
+        except (TypeError, ValueError):
+            n = None
+        if n is None or n.shape != (3,) or not np.all(np.isfinite(n)) or not np.linalg.norm(n) > 0:
+            raise ValueError(f"{who}: {what} must be a finite non-zero normal (3,), got {v!r}")
+        return n / np.linalg.norm(n)
+    if isinstance(floor, np.ndarray) or (isinstance(floor, (list, tuple)) and len(floor) == 3 and all(_number(v) for v in floor)):
+        n = normal(floor, "floor")
+        return [n.copy() for _ in range(n_seq)], wf
+    if not isinstance(floor, (list, tuple)):
+        raise ValueError(f"{who}: floor must be None, a normal (3,) or per sequence a list of normals (3,) or None, got {floor!r}")
+    if len(floor) != n_seq:
+        raise ValueError(f"{who}: floor has {len(floor)} entries for {n_seq} sequences")
+    return [None if v is None else normal(v, f"floor[{i}]") for i, v in enumerate(floor)], wf
+
+
 def _check_contact_labels(contacts, recs):
     """Given labels against the checked records (host only) -> per sequence, per record None or an (m, 2) int32 array over f0..f1."""
     who = "smooth_sequences"
@@ -252,7 +287,7 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                      timings: Optional[dict] = None, covariance: Optional[str] = None, noise_px: Optional[float] = None,
                      loss: Optional[str] = None, loss_px: float = LOSS_PX, contacts=None, contact_weight: float = CONTACT_WEIGHT,
                      contact_speed: float = CONTACT_SPEED, contact_min_frames: int = CONTACT_MIN_FRAMES, contact_rounds: int = 1,
-                     ground=None, contact_height: float = CONTACT_HEIGHT) -> List[list]:
+                     ground=None, contact_height: float = CONTACT_HEIGHT, floor=None, floor_weight: Optional[float] = None) -> List[list]:
     """Smooth every identity of every sequence -- (kps (F_s,C,P_s,25|17,3), counts (F_s,C), one Calib per camera), the rows
     track_sequences and fit_sequences take -- from its MvTracklet records (fit_sequences, track_sequences, run_main_batched,
     MvTracker.update_4d, LivePool).  Returns, per sequence, NEW records in the input order (the inputs are not touched): the same
@@ -306,10 +341,25 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     all False / NaN / zeros.  covariance="joints" takes its blocks with the final labels and anchors: the covariance is conditional
     on them, and the E_data behind an estimated smooth_noise_px includes E_contact.  timings gets a "contacts" part (FK, the
     anchors launch and the host's share); "blocks" and "solve" hold every round's.  What this is not: the 18-joint skeleton has no
-    toes, so an ankle that pivots during push-off is held too rigidly if it is labelled; the anchor is not forced onto a floor
-    plane; contact_speed is per frame, so it depends on the frame rate.  LiveSmoother(contacts="auto") is the live twin: a fixed-lag
+    toes, so an ankle that pivots during push-off is held too rigidly if it is labelled; without floor= every run has an anchor of
+    its own and nothing ties one stance's height to the next; contact_speed is per frame, so it depends on the frame rate.
+    LiveSmoother(contacts="auto") is the live twin: a fixed-lag
     window does not know a run's future, so there an anchor is re-estimated while its run is younger than the emitted row and frozen
-    from the tick that emits the run's first row (live_smoothing.py)."""
+    from the tick that emits the run's first row (live_smoothing.py).
+    floor= a normal (3,) for every sequence, or per sequence a list of normals (3,) or None (default None: nothing below is
+    computed or set, the launches and the bits are those of a call without the argument; needs contacts; normalised here): the
+    planted feet of one identity stand on ONE plane.  With T = I - n n^T and one level h per identity (metres along n),
+    E_contact = 1/2 contact_weight sum |T (ankle(x_t) - a)|^2 + 1/2 floor_weight sum (n . ankle(x_t) - h)^2 over the labelled pairs
+    (floor_weight=None: contact_weight; finite >= 0): the horizontal position of a planted foot may be soft while its height is
+    locked.  h is an unknown too, minimised in closed form (the mean of n . ankle over the identity's labelled pairs, both feet);
+    every round's anchors launch is followed by one more (mvmc_smooth_floor_anchors) that takes h and moves the run means onto the
+    plane, and every blocks launch -- the covariance's too -- is mvmc_smooth_blocks_floor.  The joint energy over (x, anchors, h)
+    never increases from round 1 on.  ``smooth_contact_anchor`` is then the point T mean + n h (n . a = h to rounding),
+    ``smooth_contact_cost`` the E_contact above, and every record gets ``smooth_floor_normal`` (3,) (unit; NaN for a sequence whose
+    entry is None, which runs the contacts alone, bit for bit) and ``smooth_floor_level`` (NaN without a contact).  ground= keeps its
+    meaning: it gates the detection only.  estimate_floor() finds the normal from the records of a first call with contacts.  What
+    the floor is not: unlabelled rows carry no term (a swing foot may pass under the plane); the live twin has no floor; there are
+    still no toes; neither the world nor the BVH root is moved onto the floor."""
     t_start = time.perf_counter()
     w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
     noise_px = _check_covariance(covariance, noise_px)
@@ -318,6 +368,10 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     if contacts is not None:
         auto, wc, c_speed, c_min, c_rounds, c_ground, c_height = _check_contact_args(contacts, contact_weight, contact_speed,
                                                                                     contact_min_frames, contact_rounds, ground, contact_height)
+    if floor is not None or floor_weight is not None:
+        if floor is None:
+            raise ValueError("smooth_sequences: floor_weight belongs to floor")
+        normals, wf = _check_floor(floor, floor_weight, contacts, contact_weight, len(sequences))
     if no_sequences(sequences, tracklets_per_sequence, "smooth_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence)
@@ -363,6 +417,10 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
             traj.append((a, x0, filled, mem, nvf, int(sel.rig_of[rec_lo[a]])))
         t0 = lap("prepare", t0)
         res, obs_w, con = {}, {}, {}
+        nrm_h = None          # the group's floor normals (one per rig, NaN: none), when it has one
+        if floor is not None and any(normals[i] is not None for i in lay.seq_ids):
+            nrm_h = np.array([np.full(3, np.nan) if normals[i] is None else normals[i] for i in lay.seq_ids])
+            nrm_d = T(nrm_h)
         cap = max(1, int(max_work_bytes) // (per_row + (8 * _OBS * C if loss is not None else 0)))   # (the weights: (C, 16) per row)
         at = 0
         while at < len(traj):
@@ -406,11 +464,16 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 cmask = T(cm_h)
                 anch = torch.empty((N, 2, 3), dtype=torch.float64, device=d)
                 ckw = dict(cmask=cmask, anchors=anch, contact_weight=wc)
+                if nrm_h is not None:
+                    ckw.update(normals=nrm_d, floor_weight=wf)
+                    lev = torch.empty((len(part),), dtype=torch.float64, device=d)
                 infos, first = [info], None
                 t0 = lap("prepare", t0)
                 for rnd in range(c_rounds):
                     jn_d = dev.fk(x)
                     dev.smooth_contact_anchors(jn_d, id_lo_d, cmask, anch, ctl, auto and rnd == 0, c_speed, c_min, c_ground, c_height)
+                    if nrm_h is not None:
+                        dev.smooth_floor_anchors(jn_d, id_lo_d, rig_d, nrm_d, cmask, anch, lev)
                     if rnd == 0:
                         first = (jn_d.cpu().numpy(), cmask.cpu().numpy(), anch.cpu().numpy())
                     info_r = torch.zeros((len(part), 32), dtype=torch.float64, device=d)   # (a stopped identity's row stays 0)
@@ -444,11 +507,15 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
                 t0 = lap("records", t0)
                 infs = [inf] + [i.cpu().numpy() for i in infos[1:]]
                 anc_h = anch.cpu().numpy()
+                lev_h = lev.cpu().numpy() if nrm_h is not None else None
                 inf = []
                 for s in range(len(part)):
                     sl = slice(id_lo[s], id_lo[s + 1])
+                    n_s = nrm_h[part[s][5]] if nrm_h is not None and not np.isnan(nrm_h[part[s][5], 0]) else None
                     inf_s, con[part[s][0]] = _contact_result([i[s] for i in infs], first[0][sl], first[1][sl], first[2][sl], jn[sl],
-                                                             anc_h[sl], wc)
+                                                             anc_h[sl], wc, n_s, wf if n_s is not None else None)
+                    if floor is not None:
+                        con[part[s][0]] += (np.full(3, np.nan) if n_s is None else n_s.copy(), float(lev_h[s]) if n_s is not None else math.nan)
                     inf.append(inf_s)
                 t0 = lap("contacts", t0)
             for s, p in enumerate(part):
@@ -465,6 +532,8 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
             _weight_fields(out, items, traj, obs_w, fill_gaps, C)
         if contacts is not None:
             _contact_fields(out, items, traj, con, fill_gaps, c_rounds)
+            if floor is not None:
+                _floor_fields(out, items, con, [normals[i] for i in lay.seq_ids], sel.rig_of, rec_lo)
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
@@ -531,13 +600,19 @@ def _covariance_fields(out, items, traj, res, fill_gaps, noise_px):
         t.smooth_cov_status = status
 
 
-def _contact_energy(joints, mask, anchors, wc) -> float:
-    """E_contact = 1/2 wc sum over the labelled (row, foot) pairs of |ankle - anchor|^2: joints (m,18,3), mask (m,2), anchors (m,2,3)."""
+def _contact_energy(joints, mask, anchors, wc, normal=None, wf=None) -> float:
+    """E_contact = 1/2 wc sum over the labelled (row, foot) pairs of |ankle - anchor|^2: joints (m,18,3), mask (m,2), anchors (m,2,3).
+    With a floor (normal (3,) unit, wf; the anchors on the plane): + 1/2 (wf - wc) sum (normal . (ankle - anchor))^2, which makes it
+    1/2 wc sum |T (ankle - run mean)|^2 + 1/2 wf sum (normal . ankle - level)^2."""
     d = np.where(mask[..., None] != 0, joints[:, _FEET] - anchors, 0.0)
-    return 0.5 * wc * float(np.sum(d * d))
+    E = 0.5 * wc * float(np.sum(d * d))
+    if normal is not None:
+        nd = d @ normal
+        E += 0.5 * (wf - wc) * float(np.sum(nd * nd))
+    return E
 
 
-def _contact_result(infs, joints1, mask, anchors1, joints, anchors, wc):
+def _contact_result(infs, joints1, mask, anchors1, joints, anchors, wc, normal=None, wf=None):
     """One identity after its rounds: infs its info row of round 0 and of every later round, joints1 / anchors1 the first round's FK
     joints and anchors, mask (m,2) the labels, joints / anchors the returned joints and the last round's anchors -> (the info row
     _records reads, of the whole call: E_data without the contact part, every round's trials in order; (labels, anchors,
@@ -548,7 +623,7 @@ def _contact_result(infs, joints1, mask, anchors1, joints, anchors, wc):
     cost = np.zeros(2)
     end = infs[0][2:4]
     if live:
-        cost[:] = _contact_energy(joints1, mask, anchors1, wc), _contact_energy(joints, mask, anchors, wc)
+        cost[:] = _contact_energy(joints1, mask, anchors1, wc, normal, wf), _contact_energy(joints, mask, anchors, wc, normal, wf)
         end = np.array([infs[-1][2] - cost[1], infs[-1][3]])
     inf = np.concatenate([infs[0][0:2], end, [float(sum(n_r)), 0.0, 0.0, 0.0], trials])
     return inf, (mask != 0, anchors, cost, n_r)
@@ -562,12 +637,24 @@ def _contact_fields(out, items, traj, con, fill_gaps, rounds):
         if a in tr:
             filled = tr[a][2]
             idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
-            mask, anchors, cost, n_r = con[a]
+            mask, anchors, cost, n_r = con[a][:4]
             t.smooth_contact, t.smooth_contact_anchor = mask[idx].copy(), anchors[idx].copy()
             t.smooth_contact_cost, t.smooth_round_trials = cost, list(n_r)
         else:   # one frame: nothing was solved
             t.smooth_contact, t.smooth_contact_anchor = np.zeros((1, 2), bool), np.full((1, 2, 3), np.nan)
             t.smooth_contact_cost, t.smooth_round_trials = np.zeros(2), [0] * (1 + rounds)
+
+
+def _floor_fields(out, items, con, normals, rig_of, rec_lo):
+    """smooth_floor_normal (3,) and smooth_floor_level of the group's records: the sequence's unit normal (NaN: it has none) and the
+    identity's level along it, NaN without a contact (and for a one-frame record)."""
+    for a, (i, j) in enumerate(items):
+        t = out[i][j]
+        if a in con:
+            t.smooth_floor_normal, t.smooth_floor_level = con[a][4], con[a][5]
+        else:
+            n = normals[int(rig_of[rec_lo[a]])]
+            t.smooth_floor_normal, t.smooth_floor_level = (np.full(3, np.nan) if n is None else n.copy()), math.nan
 
 
 def _weight_fields(out, items, traj, obs_w, fill_gaps, C):
@@ -588,9 +675,20 @@ def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calib
                      covariance: Optional[str] = None, noise_px: Optional[float] = None, loss: Optional[str] = None,
                      loss_px: float = LOSS_PX, contacts=None, contact_weight: float = CONTACT_WEIGHT,
                      contact_speed: float = CONTACT_SPEED, contact_min_frames: int = CONTACT_MIN_FRAMES, contact_rounds: int = 1,
-                     ground=None, contact_height: float = CONTACT_HEIGHT) -> list:
+                     ground=None, contact_height: float = CONTACT_HEIGHT, floor=None, floor_weight: Optional[float] = None) -> list:
     """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records.
-    contacts: None, "auto", or a list aligned with ``tracklets`` (None or a bool array (m, 2) per record)."""
+    contacts: None, "auto", or a list aligned with ``tracklets`` (None or a bool array (m, 2) per record); floor: None or the
+    sequence's floor normal (3,)."""
+    if floor is not None or floor_weight is not None:
+        if floor is not None and isinstance(floor, (list, tuple)) and not (len(floor) == 3 and all(_number(v) for v in floor)):
+            raise ValueError(f"smooth_tracklets: floor must be None or ONE normal (3,), got {floor!r}")
+        return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel,
+                                ang_acc=ang_acc, max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device,
+                                timings=timings, covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px,
+                                contacts=contacts if contacts is None or isinstance(contacts, str) else [contacts],
+                                contact_weight=contact_weight, contact_speed=contact_speed, contact_min_frames=contact_min_frames,
+                                contact_rounds=contact_rounds, ground=ground, contact_height=contact_height, floor=floor,
+                                floor_weight=floor_weight)[0]
     if contacts is not None:
         return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel,
                                 ang_acc=ang_acc, max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device,
@@ -601,3 +699,67 @@ def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calib
     return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel, ang_acc=ang_acc,
                             max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings,
                             covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px)[0]
+
+
+def estimate_floor(tracklets_per_sequence: Sequence[list], min_spread: float = 0.05) -> List[dict]:
+    """The floor normal of every sequence from the planted feet of its smoothed records (host only, NumPy; restated in
+    tests/smooth_floor_np.py: estimate): records that carry ``smooth_contact`` -- those of smooth_sequences(contacts=...).  A run is a
+    maximal stretch of consecutive frame_idxs on which one foot is labelled, m_r its mean ankle and len_r its length; c_id is the
+    length-weighted mean of an identity's m_r over both feet, S = sum len_r (m_r - c_id)(m_r - c_id)^T over every identity of the
+    sequence: each identity stands on a level of its own, the normal is shared.  n is S's eigenvector of the smallest eigenvalue,
+    oriented so that the mean of n . (joint 0 - ankle) over the labelled rows is positive (the body is above its feet).
+    Per sequence a dict: ``normal`` (3,) unit; ``status`` 0 ok, 1 fewer than three runs or sqrt(lambda_mid / sum len_r) < min_spread
+    metres (the footholds do not span a plane -- somebody stepping on the spot or along one line; a condition, not a measurement: the
+    normal is S's eigenvector all the same), 2 no contact at all (NaN normal); ``spread`` (3,) = sqrt(eigenvalues / sum len_r)
+    ascending, metres; ``rms`` = spread[0], the run means' residual about their planes; ``levels`` per record, the length-weighted
+    mean of n . m_r (NaN without a contact); ``n_runs``.  The recipe: smooth with contacts, estimate_floor, smooth again with
+    floor=[f["normal"] if f["status"] == 0 else None for f in floors]."""
+    if not _number(min_spread) or not math.isfinite(min_spread) or min_spread < 0:
+        raise ValueError(f"estimate_floor: min_spread must be a finite number >= 0, got {min_spread!r}")
+    out = []
+    for s, recs in enumerate(tracklets_per_sequence):
+        means, lens, ids, up = [], [], [], []
+        for i, t in enumerate(recs):
+            lab = getattr(t, "smooth_contact", None)
+            if lab is None:
+                raise ValueError(f"estimate_floor: record {i} of sequence {s} has no smooth_contact: smooth it with contacts= first")
+            fr = np.asarray(t.frame_idxs)
+            J = np.array([q[2].keypoints for q in t.poses], np.float64).reshape(len(fr), _JOINTS, 3)
+            lab = np.asarray(lab, bool)
+            for f, K in enumerate(_FEET):
+                k = 0
+                while k < len(fr):
+                    if not lab[k, f]:
+                        k += 1
+                        continue
+                    e = k + 1
+                    while e < len(fr) and lab[e, f] and fr[e] == fr[e - 1] + 1:
+                        e += 1
+                    means.append(J[k:e, K].mean(0))
+                    lens.append(e - k)
+                    ids.append(i)
+                    k = e
+                up.append((J[:, 0] - J[:, K])[lab[:, f]])
+        nan3 = np.full(3, np.nan)
+        if not means:
+            out.append(dict(normal=nan3, status=2, spread=nan3.copy(), rms=math.nan, levels=np.full(len(recs), np.nan), n_runs=0))
+            continue
+        means, lens, ids = np.array(means), np.array(lens, np.float64), np.array(ids)
+        S = np.zeros((3, 3))
+        for i in np.unique(ids):
+            k = ids == i
+            c = (lens[k, None] * means[k]).sum(0) / lens[k].sum()
+            dm = means[k] - c
+            S += (lens[k, None, None] * dm[:, :, None] * dm[:, None, :]).sum(0)
+        lam, V = np.linalg.eigh(S)
+        n = V[:, 0]
+        if np.concatenate(up).mean(0) @ n < 0:
+            n = -n
+        spread = np.sqrt(np.maximum(lam, 0.0) / lens.sum())
+        levels = np.full(len(recs), np.nan)
+        for i in np.unique(ids):
+            k = ids == i
+            levels[i] = (lens[k] * (means[k] @ n)).sum() / lens[k].sum()
+        out.append(dict(normal=n, status=0 if len(means) >= 3 and spread[1] >= min_spread else 1, spread=spread, rms=float(spread[0]),
+                        levels=levels, n_runs=len(means)))
+    return out

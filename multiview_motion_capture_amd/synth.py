@@ -96,7 +96,47 @@ def scene_walk(n_frames: int, n_people: int, seed: int, segment: int = 0, kappa:
     return home_root[None] + y[..., :3], home_ang[None] + y[..., 3:].reshape(n_frames, n_people, 18, 3)
 
 
-def planted_walk(n_frames: int, n_people: int, seed: int, stance: int = 8, side_lens=None, start=None):
+def _rotvec_mat(w: np.ndarray) -> np.ndarray:
+    """Rotation vectors (...,3) -> matrices (...,3,3) (Rodrigues)."""
+    th = np.linalg.norm(w, axis=-1)[..., None, None]
+    k = w / np.where(th[..., 0] > 0, th[..., 0], 1.0)
+    Kx = np.zeros(w.shape[:-1] + (3, 3))
+    Kx[..., 0, 1], Kx[..., 0, 2], Kx[..., 1, 2] = -k[..., 2], k[..., 1], -k[..., 0]
+    Kx[..., 1, 0], Kx[..., 2, 0], Kx[..., 2, 1] = k[..., 2], -k[..., 1], k[..., 0]
+    return np.eye(3) + np.sin(th) * Kx + (1.0 - np.cos(th)) * (Kx @ Kx)
+
+
+def _floor_tilt(ang: np.ndarray, lens: np.ndarray, stance: int, normal: np.ndarray) -> np.ndarray:
+    """planted_walk's angles (F,P,18,3) with the root rotated so that at every change of the stance foot both ankles are at the same
+    height along ``normal`` (unit): at change frame t_c, d = right ankle - left ankle (root-relative), the least rotation that makes
+    d perpendicular to the normal (axis d x n, angle -asin(n . d / |d|)); the rotation vectors interpolated linearly between the
+    change frames, constant before the first and after the last; R_root <- Q R_root, back to Rx Ry Rz Euler angles, unwrapped."""
+    from .smoothing import unwrap_euler
+    F, P = ang.shape[:2]
+    tc = np.arange(int(stance), F, int(stance))
+    if tc.size == 0:
+        return ang
+    rel = batched_fk(np.zeros((tc.size, P, 3)), ang[tc], np.broadcast_to(lens, (tc.size, P, 11)))[:, :, [3, 6]]
+    d = rel[:, :, 1] - rel[:, :, 0]
+    axis = np.cross(d, normal)
+    axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+    rv_c = axis * -np.arcsin((d @ normal) / np.linalg.norm(d, axis=-1))[..., None]        # (n_changes, P, 3)
+    rv = np.empty((F, P, 3))
+    for p in range(P):
+        for e in range(3):
+            rv[:, p, e] = np.interp(np.arange(F), tc, rv_c[:, p, e])
+    R0 = _rot(0, ang[:, :, 0, 0]) @ _rot(1, ang[:, :, 0, 1]) @ _rot(2, ang[:, :, 0, 2])
+    R = _rotvec_mat(rv) @ R0
+    out = ang.copy()
+    out[:, :, 0, 0] = np.arctan2(-R[..., 1, 2], R[..., 2, 2])
+    out[:, :, 0, 1] = np.arcsin(np.clip(R[..., 0, 2], -1.0, 1.0))
+    out[:, :, 0, 2] = np.arctan2(-R[..., 0, 1], R[..., 0, 0])
+    for p in range(P):
+        out[:, p] = unwrap_euler(out[:, p])
+    return out
+
+
+def planted_walk(n_frames: int, n_people: int, seed: int, stance: int = 8, side_lens=None, start=None, floor_normal=None):
     """A walk with planted feet, the ground truth for foot skate: -> root (n_frames, P, 3), angles (n_frames, P, 18, 3), contact
     (n_frames, P, 2) bool (columns: left ankle = skeleton joint 3, right ankle = joint 6).  The angles are scene_walk(seed)'s
     (segment 0: the mean-reverting walk around a home pose); the root is not drawn but PLACED, frame by frame, where the stance
@@ -106,11 +146,22 @@ def planted_walk(n_frames: int, n_people: int, seed: int, stance: int = 8, side_
     not move between two consecutive frames on which it is labelled (to the rounding of one FK: ~1e-16 m).  Everybody starts on
     the left foot, at ``start`` (P, 3) (default: scene_walk's first roots).  side_lens (11,) or (P, 11): the bone lengths the FK is
     taken with (default: the skeleton's reference lengths).  Nothing puts the anchors on a common floor: the swing ankle is
-    wherever the angles put it when its turn comes."""
+    wherever the angles put it when its turn comes.
+    floor_normal (3,) (default None: the output above, bit for bit): a walk on ONE floor.  The whole body is tilted about the root
+    (the root joint's angles alone change) so that at every change of the stance foot both ankles are at the same height along the
+    normal (_floor_tilt): every anchor of one person then lies on one plane with that normal (to ~1e-15 m), each person on a level
+    of their own, and the planted ankles stay where they are as before.  The poses are random, so the tilts are large (up to ~85
+    degrees: these people walk bent over, sideways or on their backs) and the swing ankle may dip several centimetres under the
+    stance level: a ground truth for the geometry of contacts, not a gait."""
     if int(stance) != stance or stance < 2:
         raise ValueError("planted_walk: stance must be an integer >= 2")
     root_s, ang = scene_walk(n_frames, n_people, seed)
     lens = np.asarray(skeleton_arrays()[1] if side_lens is None else side_lens, np.float64) * np.ones((n_people, 11))
+    if floor_normal is not None:
+        n = np.array(floor_normal, np.float64)
+        if n.shape != (3,) or not np.all(np.isfinite(n)) or not np.linalg.norm(n) > 0:
+            raise ValueError("planted_walk: floor_normal must be a finite non-zero (3,) vector")
+        ang = _floor_tilt(ang, lens, int(stance), n / np.linalg.norm(n))
     rel = batched_fk(np.zeros((n_frames, n_people, 3)), ang, np.broadcast_to(lens, (n_frames, n_people, 11)))[:, :, [3, 6]]
     root = np.empty((n_frames, n_people, 3))
     contact = np.zeros((n_frames, n_people, 2), dtype=bool)
@@ -127,7 +178,8 @@ def planted_walk(n_frames: int, n_people: int, seed: int, stance: int = 8, side_
 
 
 def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: int = 0, dtype=np.float32,
-             drop=0.05, pix_sigma=2.0, shuffle=True, frame_seed=None, occlusion=0.0, spurious=0.0, walk=None, segment: int = 0):
+             drop=0.05, pix_sigma=2.0, shuffle=True, frame_seed=None, occlusion=0.0, spurious=0.0, walk=None, segment: int = 0,
+             floor_normal=None):
     """-> dict(kps25 (F,C,P,25,3), counts (F,C) int32, K, Rt, P, gt_joints (F,P,18,3), gt_order (F,C,P)); walk="planted":
     gt_contact (F,P,2) bool too.
 
@@ -149,10 +201,13 @@ def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: i
     with segment = rank cuts one sequence into contiguous shards: what the tracklet stitch has identities to carry across.
     walk="planted": the scene walk's angles, bone lengths and noise streams with the roots of planted_walk(seed) -- one foot of
     every person is planted on every frame, the stance foot changes every 8 frames --, and gt_contact (F,P,2) in the output: the
-    ground truth of foot skate (segment 0 only).
+    ground truth of foot skate (segment 0 only).  floor_normal (3,) (walk="planted" only; default None: the output without the argument
+    bit for bit): planted_walk's walk on one floor, every person's footholds on one plane with that normal.
     walk=None (default): the random walk above, bit for bit the output of earlier versions."""
     K, Rt, Pm = make_cameras(n_views, np.random.default_rng(seed))
     F, C, Pn = n_frames, n_views, n_people
+    if floor_normal is not None and walk != "planted":
+        raise ValueError("generate: floor_normal belongs to walk='planted'")
     _, side = skeleton_arrays()
     if walk == "scene":
         root, ang = scene_walk(F, Pn, seed, segment)
@@ -163,7 +218,7 @@ def generate(n_frames: int, n_views: int, n_people: int, seed: int, chain_len: i
         if segment != 0:
             raise ValueError("generate: walk='planted' has one segment")
         lens = side * np.random.default_rng([seed, 4]).uniform(0.9, 1.1, size=(Pn, 1)) * np.ones((Pn, 11))
-        root, ang, gt_contact = planted_walk(F, Pn, seed, side_lens=lens)
+        root, ang, gt_contact = planted_walk(F, Pn, seed, side_lens=lens, floor_normal=floor_normal)
         frame_seed = [seed, 5, 0]
         rng = np.random.default_rng(frame_seed + [1])
     elif walk is not None:
