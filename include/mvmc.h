@@ -758,6 +758,43 @@ int mvmc_smooth_window_cov_contact(const mvmcSkeleton* skel_host, const double* 
                                    double* jcov, double* pvar, double* cinfo, const int32_t* contact, const double* anchors,
                                    double contact_weight, mvmcStream_t stream);
 
+/* ---- one skeleton per live identity, estimated as frames arrive (live_smoothing.py: lengths="auto"; csrc/mvmc_live_lengths.hip;
+ * restated in tests/live_lengths_np.py, which is the definition).  The window launches above solve every row under its own columns
+ * 57:68; these two launches, one before and one after the tick's window launch, decide what those columns hold.  Both take the
+ * window launch's items (MVMC_SMOOTH_WIN_ITEM_INTS i32 each: slot, d, is_data, reset and src are read, rig by the update alone).
+ * State per identity slot, lens_state (n_slots, MVMC_LIVE_LEN_STATE_DOUBLES) f64:
+ *   [0, 66)    A = sum J^T J, the upper triangle, entry (s, t), s <= t, at s * 11 - s (s - 1) / 2 + (t - s)
+ *   [66, 77)   b = sum J^T (J l_r - r)
+ *   [77, 88)   l, the current skeleton             [88, 99)   l0, the lengths of the identity's first row (the prior's mean)
+ *   99 next_row   100 contributed   101 committed (0 / 1)   102 committed_row (-1 before)        -- integers held as doubles
+ * mvmc_live_lengths_apply, elementwise, one lane per (item, length): a reset item with data sets A = b = 0, l = l0 = row src of
+ *   new_params, the counters to {0, 0, 0, -1}; another item with data gets new_params[src, 57:68] = l; items without data, malformed
+ *   items (slot or src out of range) and rows of new_params no item names are untouched.
+ * mvmc_live_lengths_update, after the window launch, one 64-lane workgroup per item, with n = count[slot] rows: for r = next_row ..
+ *   n - 1 - lag ascending (d > 1: from n - d on, the rows from before a jump of the frame index are passed over for good -- the
+ *   keypoint ring may have been overwritten at their position), unless the identity is committed: a row with >= 2 members contributes
+ *   mvmc_body_lengths' residual r and Jacobian J in the lengths (16 observation rows per member, score-weighted, 1e-5 in the
+ *   denominator), the pose at the row's values, linearised at the row's own lengths l_r: A += J^T J, b += J^T (J l_r - r), contributed
+ *   += 1.  next_row = max(next_row, n - lag).  If a row contributed: (A + prior I) l = b + prior l0 by Cholesky; a pivot that is not
+ *   positive and finite, or a length that is not finite, or not > 0 on a slot with curvature (A_ss > 0; slot 7 has none and a zero
+ *   reference length, the prior alone holds it at l0), keeps the old l (status 1).  commit > 0 and contributed >= commit:
+ *   committed = 1, committed_row = n - lag.  l goes into columns 57:68 of rows max(n - lag, 0) .. n - 1; no other row is written.
+ *   The lanes share a row's (member, observation row) pairs; every sum runs in a fixed order with a fixed butterfly across the lanes
+ *   and no atomics: an identity's bits depend on nothing else in the launch.
+ *   linfo (n_items, MVMC_LIVE_LEN_INFO_DOUBLES) f64 out: {status (0; 1 the solve failed and l was kept; 6 malformed), rows contributed
+ *   this tick, contributed, committed, committed_row, l (11), 1/2 sum r^2 of this tick's contributing rows}.  An item whose slot or rig
+ *   is out of range, or whose rows to visit lie outside the ring (count < 1, next_row outside [0, n], n - next_row >
+ *   MVMC_SMOOTH_WIN_RING), is malformed: status 6, the rest of its linfo NaN, nothing else written.
+ * 0 <= lag < MVMC_SMOOTH_WIN_MAX, prior finite > 0, commit >= 0 (0: never), else MVMC_ERR_ARG; argument errors return before any HIP
+ * call; nothing is allocated or synchronised inside. ---- */
+#define MVMC_LIVE_LEN_STATE_DOUBLES 103
+#define MVMC_LIVE_LEN_INFO_DOUBLES 17
+int mvmc_live_lengths_apply(const int32_t* items, int n_items, double* new_params, int n_new, double* lens_state, int n_slots,
+                            mvmcStream_t stream);
+int mvmc_live_lengths_update(const mvmcSkeleton* skel_host, const double* kps17, int n_views, int p_max, const double* Pmats, int n_rigs,
+                             const int32_t* items, int n_items, double* rows, const int32_t* members, const int32_t* count, int n_slots,
+                             int lag, double prior, int commit, double* lens_state, double* linfo, mvmcStream_t stream);
+
 /* ---- re-linking of the records of one person (multiview_motion_capture_amd/relinking.py).  No counterpart in the reference.  Per
  * sequence, its records in (first frame, track id) order are the nodes; record a may be followed by record b when 1 <= gap =
  * first(b) - last(a) <= max_gap, at the cost mean_k |last_joints(a)[k] + v gap - first_joints(b)[k]| (metres; v = the mean of a's end

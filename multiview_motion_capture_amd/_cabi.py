@@ -28,6 +28,7 @@ SMOOTH_COV_INFO_DOUBLES, SMOOTH_JOINTS = 8, 18
 SMOOTH_WIN_MAX, SMOOTH_WIN_RING, SMOOTH_WIN_ITEM_INTS, SMOOTH_WIN_INFO_DOUBLES = 32, 66, 8, 16
 SMOOTH_COV_ITEM_INTS = 4                                                                          # MVMC_SMOOTH_COV_ITEM_INTS
 SMOOTH_LIVE_CONTACT_DOUBLES = 10                                                                  # MVMC_SMOOTH_LIVE_CONTACT_DOUBLES
+LIVE_LEN_STATE_DOUBLES, LIVE_LEN_INFO_DOUBLES = 103, 17                                            # MVMC_LIVE_LEN_*
 SMOOTH_LOSS_NONE, SMOOTH_LOSS_HUBER, SMOOTH_LOSS_CAUCHY = 0, 1, 2                                     # MVMC_SMOOTH_LOSS_*
 SMOOTH_FOOT_L, SMOOTH_FOOT_R = 3, 6                                                                   # MVMC_SMOOTH_FOOT_*: the ankles
 RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
@@ -50,6 +51,7 @@ SYMBOLS = (
     "mvmc_smooth_blocks_floor", "mvmc_smooth_floor_anchors",
     "mvmc_smooth_window_cov_work_doubles", "mvmc_smooth_window_cov",
     "mvmc_smooth_window_contact", "mvmc_smooth_window_cov_contact",
+    "mvmc_live_lengths_apply", "mvmc_live_lengths_update",
     "mvmc_rig_part_doubles", "mvmc_rig_red_doubles", "mvmc_rig_start", "mvmc_rig_accumulate", "mvmc_rig_step",
     "mvmc_rig_accumulate_robust", "mvmc_rig_step_robust", "mvmc_rig_weights",
     "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
@@ -184,6 +186,8 @@ def load():
                                        f64, vp, vp],
         "mvmc_smooth_window_cov_contact": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, f64, f64, f64, f64, i32, i32, f64,
                                            vp, C.c_longlong, vp, vp, vp, vp, vp, f64, vp],
+        "mvmc_live_lengths_apply": [vp, i32, vp, i32, vp, i32, vp],
+        "mvmc_live_lengths_update": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, i32, vp, vp, vp],
         "mvmc_relink_work_words": [i32],
         "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
         "mvmc_rig_part_doubles": [i32],

@@ -101,7 +101,11 @@ svt_kernel(const TS* __restrict__ Sg, const int32_t* __restrict__ gcounts, int G
         if (in) Yg[i * ldw + j] = 0.0;
     }
     __syncthreads();
-    if (n == 0) {
+    if (n == 0) {   // an empty graph: no iteration and no pair (its outputs are zero, as outside every graph's n x n block)
+        for (int e = tid; e < ldw * ldw; e += SVT_NT) {
+            x_bin[(size_t)f * ldw * ldw + e] = 0;
+            if (x_out) x_out[(size_t)f * ldw * ldw + e] = 0.0;
+        }
         if (tid == 0) iters_out[f] = 0;
         return;   // (uniform)
     }

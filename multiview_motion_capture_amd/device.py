@@ -706,6 +706,46 @@ def smooth_window_cov(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Ten
     return jcov, pvar, cinfo
 
 
+def live_lengths_apply(items: torch.Tensor, new_params: torch.Tensor, lens_state: torch.Tensor) -> None:
+    """Before the tick's smooth_window (include/mvmc.h: mvmc_live_lengths_apply), one launch: a reset item's slot of lens_state
+    (n_slots,103) starts from its row of new_params (B,68); the data row of every other item gets the slot's skeleton in columns
+    57:68.  Both tensors are updated in place."""
+    n = items.shape[0]
+    _req(items, torch.int32, "items", (n, _cabi.SMOOTH_WIN_ITEM_INTS))
+    B = new_params.shape[0]
+    _req(new_params, torch.float64, "new_params", (B, 68))
+    n_slots = lens_state.shape[0]
+    _req(lens_state, torch.float64, "lens_state", (n_slots, _cabi.LIVE_LEN_STATE_DOUBLES))
+    check(_cabi.load().mvmc_live_lengths_apply(_p(items), n, _p(new_params), B, _p(lens_state), n_slots, _stream()),
+          "mvmc_live_lengths_apply")
+
+
+def live_lengths_update(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor, rows: torch.Tensor, members: torch.Tensor,
+                        count: torch.Tensor, lag: int, prior: float, commit: Optional[int], lens_state: torch.Tensor,
+                        skeleton: Optional[MvmcSkeleton] = None) -> torch.Tensor:
+    """After the tick's smooth_window (include/mvmc.h: mvmc_live_lengths_update), one launch: the rows that moved behind ``lag`` add
+    their normal equations in the 11 lengths to lens_state (n_slots,103), the skeleton is solved again under ``prior`` and written
+    into the rows the next tick solves again (rows and lens_state are updated in place).  items, kps17, Pmats, rows, members, count
+    as smooth_window takes them; commit None: never.  -> linfo (n,17)."""
+    sk = skeleton if skeleton is not None else make_skeleton()
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    n = items.shape[0]
+    _req(items, torch.int32, "items", (n, _cabi.SMOOTH_WIN_ITEM_INTS))
+    n_slots = rows.shape[0]
+    _req(rows, torch.float64, "rows", (n_slots, _cabi.SMOOTH_WIN_RING, 68))
+    _req(members, torch.int32, "members", (n_slots, _cabi.SMOOTH_WIN_RING, Cn))
+    _req(count, torch.int32, "count", (n_slots, 2))
+    _req(lens_state, torch.float64, "lens_state", (n_slots, _cabi.LIVE_LEN_STATE_DOUBLES))
+    linfo = torch.empty((n, _cabi.LIVE_LEN_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
+    check(_cabi.load().mvmc_live_lengths_update(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(rows),
+                                                _p(members), _p(count), n_slots, int(lag), float(prior),
+                                                0 if commit is None else int(commit), _p(lens_state), _p(linfo), _stream()),
+          "mvmc_live_lengths_update")
+    return linfo
+
+
 def ik_solve_fd(kps17: torch.Tensor, Pmats: torch.Tensor, members: torch.Tensor, init_params: Optional[torch.Tensor] = None,
                 cold: Optional[torch.Tensor] = None, max_nfev_cold=50, max_nfev_warm=5, stage_mask=3,
                 skeleton: Optional[MvmcSkeleton] = None):

@@ -58,6 +58,24 @@ contact_min_frames is required, or no run could reach its length before it freez
 E_data, as the device's row costs do (the offline smoother subtracts it; here contact_cost gives it).  covariance="joints" with
 contacts is mvmc_smooth_window_cov_contact: A_w carries the contact term of the labels and anchors as they stand after the tick, the
 covariance is conditional on them as the offline one is.  Measured: tools/live_smooth_contact_probe.py, INTEGRATION.md section C.5.
+
+lengths="auto" (default None: the launches, their arguments, the state and the bits are the ones without it) keeps ONE skeleton per
+identity, estimated as frames arrive (restated in tests/live_lengths_np.py, which is the definition; csrc/mvmc_live_lengths.hip).
+The tracker's IK fits the 11 side lengths again on every frame, and the window launches solve every row under its own columns 57:68;
+two more launches per tick decide what those columns hold, the window launch -- plain, robust or contact -- is unchanged.  Per
+identity slot one more device tensor holds A (11x11), b, the current skeleton l, l0 = the lengths of the identity's first row, and
+four counters.  mvmc_live_lengths_apply, before the window launch: a new identity starts with A = b = 0 and l = l0; the data row of
+every other identity gets l (a missing row copies the previous row, so it carries that row's).  mvmc_live_lengths_update, after the
+window launch and before the covariance launch, on the solved values: every row that moved behind the lag (index <= n - 1 - lag;
+after a jump of the frame index only the rows the jump appended, the keypoint ring may have lost the older ones), if it is a data row
+with two views or more, adds the normal equations of body_fit's length residual in the 11 lengths, linearised at the row's own
+lengths -- a quadratic in ABSOLUTE lengths, so rows linearised at different points add up; then (A + lengths_prior I) l = b +
+lengths_prior l0 (Cholesky; a failed solve keeps l, status 1; slot 7 has no curvature, the prior holds it at l0) and l goes into
+the rows n - lag .. n - 1, which the next tick solves again.  Consequences: the estimate is causal and uses rows up to f - lag; an
+emitted pose was solved against the lengths it carries, and it and every older row keep them; with lengths_commit=N the identity
+stops updating once N rows have contributed, and from ``committed_row`` (n - lag of that tick) on every row of the identity carries
+one bit-identical vector, so bvh_export.save_bvh takes committed_part(record).  lengths_prior is in px^2 / m^2, against a diagonal of
+A of about 1e7 after 20 rows; its default is tools/live_lengths_probe.py's choice (profiles/live_lengths_probe.json).
 """
 from __future__ import annotations
 
@@ -73,6 +91,7 @@ from .smoothing import (ANG_ACC, ANG_VEL, CONTACT_HEIGHT, CONTACT_MIN_FRAMES, CO
                         LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, _check_contact_args, check_loss, unwrap_euler_many)
 from .tracker import T_WIDE
 
+LENGTHS_PRIOR = 100.0  # px^2 / m^2: the weight of the identity's first lengths in the running skeleton (tools/live_lengths_probe.py)
 WINDOW_MAX = 32     # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
 N_ITER_MAX = 8      # include/mvmc.h: MVMC_SMOOTH_WIN_INFO_DOUBLES - 8
 RING = 66           # include/mvmc.h: MVMC_SMOOTH_WIN_RING
@@ -126,6 +145,46 @@ def check_contacts(contacts, contact_weight, contact_speed, contact_min_frames, 
     return dict(lag=int(lag), weight=wc, speed=speed, min_frames=min_frames, ground=g, height=height)
 
 
+def check_lengths(lengths, lengths_prior, lengths_commit) -> Optional[dict]:
+    """LiveSmoother's running-skeleton arguments (host only) -> None, or dict(prior, commit) of the update launch.  lengths_prior
+    None: LENGTHS_PRIOR; a lengths_prior or a lengths_commit without lengths="auto" is an error, whatever its value."""
+    if lengths is not None and not (isinstance(lengths, str) and lengths == "auto"):
+        raise ValueError(f"LiveSmoother: lengths must be None or \"auto\", got {lengths if isinstance(lengths, (str, bool)) else type(lengths).__name__!r}")
+    if lengths_prior is not None and (isinstance(lengths_prior, (str, bytes, bool))
+                                      or not isinstance(lengths_prior, (int, float, np.integer, np.floating))
+                                      or not math.isfinite(lengths_prior) or not lengths_prior > 0):
+        raise ValueError(f"LiveSmoother: lengths_prior must be None or a finite number > 0, got {lengths_prior!r}")
+    if lengths_commit is not None and (isinstance(lengths_commit, bool) or not isinstance(lengths_commit, (int, np.integer))
+                                       or lengths_commit < 1):
+        raise ValueError(f"LiveSmoother: lengths_commit must be None or an integer >= 1, got {lengths_commit!r}")
+    if lengths is None:
+        if lengths_commit is not None or lengths_prior is not None:
+            raise ValueError("LiveSmoother: lengths_prior / lengths_commit without lengths=\"auto\" have nothing to act on")
+        return None
+    return dict(prior=LENGTHS_PRIOR if lengths_prior is None else float(lengths_prior),
+                commit=None if lengths_commit is None else int(lengths_commit))
+
+
+def committed_part(record):
+    """The part of a lengths="auto" record from its ``live_lengths_committed_row`` on: a record whose rows share one bit-identical
+    bone-length vector (bvh_export.save_bvh takes it), its per-row attributes (smooth_*) cut to the same rows; ``hits`` counts the
+    data rows kept (the rows not in smooth_filled), as a record's hits count the poses the tracker appended.  ValueError when the
+    identity never committed (no lengths_commit, too few rows, or not a record of such a smoother)."""
+    c = getattr(record, "live_lengths_committed_row", None)
+    n = len(getattr(record, "poses", ()))
+    if c is None or c < 0 or c >= n:
+        raise ValueError("committed_part: the record has no committed skeleton (LiveSmoother(lengths=\"auto\", lengths_commit=N), and N "
+                         "rows must have contributed)")
+    c = int(c)
+    filled = getattr(record, "smooth_filled", None)
+    t = new_record(record.track_id, list(record.poses[c:]), src=record, hits=n - c if filled is None else int((~filled[c:]).sum()))
+    for name, v in vars(record).items():
+        if name.startswith("smooth_") and isinstance(v, np.ndarray) and v.shape[:1] == (n,):
+            setattr(t, name, v[c:].copy())
+    t.live_lengths, t.live_lengths_rows, t.live_lengths_committed_row = record.live_lengths.copy(), record.live_lengths_rows, 0
+    return t
+
+
 def cov_entry(jc6, pv, ci, noise_px: Optional[float]) -> dict:
     """One emitted row's unit-variance device outputs (jcov (18,6), pvar (39,), cinfo (8,)) -> its TickOutput.cov entry."""
     status, e_data, n_res, edof = int(ci[0]), float(ci[1]), float(ci[2]), float(ci[3])
@@ -147,7 +206,9 @@ class TickOutput:
     noise_px, edof, nres, status 0 solved / 1 singular / 2 a one-row identity (NaN arrays)) of the emitted row, conditional on the
     window's frozen history (the module's docstring); ``contact``: empty unless the smoother has contacts="auto", then track_id ->
     dict(contact (2,) bool, anchor (2,3) m, NaN without a label) of the emitted row, and every ``solved`` entry has contact_cost =
-    [E_contact at the start, at the end] of the tick -- its cost's E_data INCLUDES the contact part, as the device's row costs do."""
+    [E_contact at the start, at the end] of the tick -- its cost's E_data INCLUDES the contact part, as the device's row costs do;
+    ``lengths``: empty unless the smoother has lengths="auto", then track_id -> dict(lengths (11,) the running skeleton after the tick,
+    contributed (rows so far), committed, committed_row (-1 before), status 0 / 1 the tick's solve failed and the skeleton was kept)."""
 
     def __init__(self):
         self.emitted: list = []
@@ -155,6 +216,7 @@ class TickOutput:
         self.solved: Dict[int, dict] = {}
         self.cov: Dict[int, dict] = {}
         self.contact: Dict[int, dict] = {}
+        self.lengths: Dict[int, dict] = {}
 
 
 class _Ident:
@@ -169,6 +231,7 @@ class _Ident:
         self.joints: List[Optional[np.ndarray]] = []
         self.cov: Dict[int, tuple] = {}                # row -> (joint_sigma, param_sigma, noise_px) as emitted (covariance="joints")
         self.contact: Dict[int, tuple] = {}            # row -> (labels (2,) bool, anchors (2,3)) once it is final (contacts="auto")
+        self.len: Optional[tuple] = None               # (skeleton (11,), rows contributed, committed_row) after its last tick (lengths="auto")
         self.n_final = 0
 
     @property
@@ -201,10 +264,12 @@ class LiveSmoother:
                  device=None, skeleton=None, loss: Optional[str] = None, loss_px: float = LOSS_PX, covariance: Optional[str] = None,
                  noise_px: Optional[float] = None, contacts: Optional[str] = None, contact_weight: float = CONTACT_WEIGHT,
                  contact_speed: float = CONTACT_SPEED, contact_min_frames: int = CONTACT_MIN_FRAMES, ground=None,
-                 contact_height: float = CONTACT_HEIGHT):
+                 contact_height: float = CONTACT_HEIGHT, lengths: Optional[str] = None, lengths_prior: Optional[float] = None,
+                 lengths_commit: Optional[int] = None):
         self.w = check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc)
         self._ct = check_contacts(contacts, contact_weight, contact_speed, contact_min_frames, ground, contact_height, lag)
         self._noise_px = check_covariance(covariance, noise_px)
+        self._len = check_lengths(lengths, lengths_prior, lengths_commit)
         self._cov = covariance is not None
         loss_px = check_loss("LiveSmoother", loss, loss_px)
         self._rob = dict(loss=loss, loss_px=loss_px) if loss is not None else {}     # loss=None: the launch without the arguments
@@ -281,6 +346,9 @@ class LiveSmoother:
             if self._ct is not None:      # per row and foot a label and an anchor, beside the rows
                 self._st["clab"] = torch.zeros((n_slots, RING, 2), dtype=torch.int32, device=d)
                 self._st["canc"] = torch.full((n_slots, RING, 2, 3), math.nan, dtype=torch.float64, device=d)
+            if self._len is not None:     # per slot the running skeleton's A, b, l, l0 and counters (include/mvmc.h)
+                from ._cabi import LIVE_LEN_STATE_DOUBLES
+                self._st["lens"] = torch.zeros((n_slots, LIVE_LEN_STATE_DOUBLES), dtype=torch.float64, device=d)
         if self._Pm_dirty:
             self._st["Pm"] = torch.from_numpy(self._Pm_h.copy()).to(self._st["d"])
             self._Pm_dirty = False
@@ -430,6 +498,11 @@ class LiveSmoother:
         ct = None if self._ct is None else dict(labels=st["clab"], anchors=st["canc"], **self._ct)
         if ct is not None and want_fin:      # the finished identities' labels and anchors, gathered before the launch as their rows are
             C_fin = (st["clab"].view(-1, 2).index_select(0, i_fin), st["canc"].view(-1, 6).index_select(0, i_fin))
+        ln = self._len
+        # the finished identities' skeletons, gathered before the apply launch as their rows are (the apply resets a reused slot): a
+        # finished record reports the device's state itself.  (The host's copy from the identity's last report, idn.len, holds the
+        # same values, since the state changes only in a tick that reports it; tracklets() and close_session use that copy.)
+        S_fin = st["lens"].index_select(0, T(np.array([idn.slot for _, idn in fin], np.int64))) if ln is not None and fin else None
         B = len(newp)
         if B:
             frame_of = np.array([p[0] for p in prob], np.int32)
@@ -444,12 +517,20 @@ class LiveSmoother:
             newp_d = torch.zeros((0, 68), dtype=torch.float64, device=d)
         parts = []
         if items:
-            args = (st["kps"], st["Pm"], T(np.array(items, np.int32)), newp_d, mem_d, st["rows"], st["members"], st["count"], W,
+            items_d = T(np.array(items, np.int32))
+            if ln is not None:      # the running skeletons into the tick's data rows, a new identity's state from its row
+                dev.live_lengths_apply(items_d, newp_d, st["lens"])
+            args = (st["kps"], st["Pm"], items_d, newp_d, mem_d, st["rows"], st["members"], st["count"], W,
                     self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton)
             if ct is None:
                 parts.append(dev.smooth_window(*args, **self._rob).reshape(-1))
             else:
                 parts += [p.reshape(-1) for p in dev.smooth_window(*args, **self._rob, contact=ct)]
+            if ln is not None:      # the rows that moved behind the lag into the skeletons, the skeletons into the rows after them
+                parts.append(dev.live_lengths_update(st["kps"], st["Pm"], items_d, st["rows"], st["members"], st["count"], self.lag,
+                                                     ln["prior"], ln["commit"], st["lens"], self.skeleton).reshape(-1))
+        if S_fin is not None:
+            parts.append(S_fin.reshape(-1))
         # the covariance of the emitted rows: ONE launch for all of them, none when nothing is emitted (or it is not asked for)
         cov_of = [a for a, (key, idn, f) in enumerate(solved_of) if f - self.lag - idn.f0 >= 0] if self._cov else []
         if cov_of:
@@ -482,6 +563,10 @@ class LiveSmoother:
             return a
         inf_h = take(len(items) * 16, (len(items), 16))
         cin_h = take(len(items) * 10, (len(items), 10)) if ct is not None and items else None
+        lin_h = take(len(items) * 17, (len(items), 17)) if ln is not None and items else None
+        if S_fin is not None:      # (A, b, l, l0, counters: include/mvmc.h)
+            for (key, idn), S in zip(fin, take(len(fin) * 103, (len(fin), 103))):
+                idn.len = (S[77:88].copy(), int(S[100]), int(S[102]))
         nc = len(cov_of)
         jc_h, pv_h, ci_h = take(nc * 108, (nc, 18, 6)), take(nc * 39, (nc, 39)), take(nc * 8, (nc, 8))
         P_h = take(n_rows * 68, (n_rows, 68))
@@ -519,6 +604,12 @@ class LiveSmoother:
                 out[key].solved[idn.tid] = dict(cost=inf_h[a, :4].copy(), trials=[int(v) for v in inf_h[a, 8:8 + n_t]], stop=int(inf_h[a, 7]))
                 if ct is not None:
                     out[key].solved[idn.tid]["contact_cost"] = cin_h[a, 8:10].copy()
+            if ln is not None:
+                if int(lin_h[a, 0]) == 6:
+                    raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed skeleton item")
+                q = out[key].lengths[idn.tid] = dict(lengths=lin_h[a, 5:16].copy(), contributed=int(lin_h[a, 2]),
+                                                     committed=bool(lin_h[a, 3]), committed_row=int(lin_h[a, 4]), status=int(lin_h[a, 0]))
+                idn.len = (q["lengths"], q["contributed"], q["committed_row"])
             r = f - self.lag - idn.f0
             if r >= 0 and ct is not None:
                 out[key].contact[idn.tid] = dict(contact=cin_h[a, :2] != 0, anchor=cin_h[a, 2:8].reshape(2, 3).copy())
@@ -594,7 +685,9 @@ class LiveSmoother:
 
     # -- records -----------------------------------------------------------------------------------------------------------------------
     def _record(self, idn: _Ident, n: int, state: Optional[int] = None, live=None):
-        """The identity's rows 0..n-1 as an MvTracklet-like record (save_bvh takes it); ``live``: values of the rows not final yet."""
+        """The identity's rows 0..n-1 as an MvTracklet-like record; ``live``: values of the rows not final yet.  Its rows carry the
+        lengths they were solved under, which differ from row to row: bvh_export.save_bvh takes only committed_part(record) of a
+        smoother with lengths="auto" and lengths_commit, or the record after body_fit.fit_sequences."""
         from .motion_capture import TrackState
         rows = [(idn.params[r], idn.joints[r]) + (idn.contact[r] if self._ct is not None else ()) if idn.params[r] is not None else live[r]
                 for r in range(n)]
@@ -608,6 +701,9 @@ class LiveSmoother:
         if self._ct is not None:      # the rows' stored labels and anchors as they stand
             t.smooth_contact = np.array([q[2] for q in rows], bool).reshape(n, 2)
             t.smooth_contact_anchor = np.array([q[3] for q in rows], np.float64).reshape(n, 2, 3)
+        if self._len is not None:      # the running skeleton after the identity's last tick
+            t.live_lengths, t.live_lengths_rows = idn.len[0].copy(), idn.len[1]
+            t.live_lengths_committed_row = idn.len[2] if idn.len[2] < n else -1
         if self._cov:      # per row the values recorded when it was emitted; NaN on the rows that never were
             t.smooth_joint_sigma, t.smooth_param_sigma, t.smooth_noise_px = np.full((n, 18), np.nan), np.full((n, 39), np.nan), np.full(n, np.nan)
             for r, (js, ps, s) in idn.cov.items():
@@ -622,7 +718,10 @@ class LiveSmoother:
         stored labels and anchors as they stand (those of the last <= lag rows are still tentative).  With covariance="joints"
         (here, in ``finished`` and from close_session) also smooth_joint_sigma (n,18), smooth_param_sigma (n,39), smooth_noise_px (n,): per
         row the values of TickOutput.cov when the row was emitted, NaN on the rows that never were (the last <= lag rows of a record,
-        and the rows a jump of the frame index skipped)."""
+        and the rows a jump of the frame index skipped).  With lengths="auto" (here, in ``finished`` and from close_session) also
+        live_lengths (11,) the running skeleton after the identity's last tick, live_lengths_rows the rows that contributed to it, and
+        live_lengths_committed_row (-1: not committed, or committed past the record's last row): from it on every row has live_lengths
+        in its bone_lens, bit for bit (committed_part cuts the record there)."""
         sess = self._session(key, "tracklets")
         want = [(idn, r) for idn in sess.ids.values() for r in range(idn.n_final, idn.n)]
         live = {}
