@@ -368,10 +368,10 @@ extern "C" int mvmc_ik_solve_stages_rigs(const mvmcSkeleton* skel_host, const do
                                          const int32_t* rig_of_problem, const int32_t* members, int n_problems, int v_max, int n_views,
                                          int p_max, const double* init_params, int stage_mask, int max_nfev, double* params_out,
                                          double* joints_out, double* info_out, double* scratch, mvmcStream_t stream) {
+    if (stage_mask < 1 || stage_mask > 3 || max_nfev < 1 || n_rigs < 1 || v_max <= 0 || n_views <= 0 || p_max <= 0) return MVMC_ERR_ARG;
+    if (n_problems <= 0) return n_problems == 0 ? MVMC_OK : MVMC_ERR_ARG;   // (before the pointers, as the two entries above: empty tables may be NULL)
     if (!skel_host || !kps17 || !Pmats || !rig_of_problem || !members || !init_params || !params_out || !joints_out || !scratch)
         return MVMC_ERR_ARG;
-    if (stage_mask < 1 || stage_mask > 3 || max_nfev < 1 || n_rigs < 1 || v_max <= 0 || n_views <= 0 || p_max <= 0) return MVMC_ERR_ARG;
-    if (n_problems <= 0) return n_problems == 0 ? MVMC_OK : MVMC_ERR_ARG;
     SkelDev sk;
     if (!skel_to_dev(skel_host, &sk)) return MVMC_ERR_ARG;
     if (sk.n_side != MVMC_N_SIDE) return MVMC_ERR_UNSUPPORTED;

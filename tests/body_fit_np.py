@@ -119,9 +119,11 @@ def len_terms(roots, As, pv_prob, pv_P, pv_obs, lens):
     return E, H, g
 
 
-def length_step(params, obs, projs, lens, free=None, max_iter=10):
+def length_step(params, obs, projs, lens, free=None, max_iter=10, mu0=LM_MU0, ftol=LM_FTOL, xtol=LM_XTOL, log=None):
     """Levenberg-Marquardt on the free slots of the identity's lengths, every problem's root and angles fixed.
-    params (n,68); obs / projs: per problem (V,16,3) / (V,3,4).  -> (lens, free, dict(E0, E, trace)); trace: 1 accepted, 0 rejected."""
+    params (n,68); obs / projs: per problem (V,16,3) / (V,3,4).  -> (lens, free, dict(E0, E, trace)); trace: 1 accepted, 0 rejected.
+    log: a list that receives one dict per look at the system (E, dmax = |d|_inf, pred, stop: None / "xtol" / "pred" / "ftol", and for
+    a look that made a trial Et and accepted): what the tests' decision margins are computed from."""
     lens = np.array(lens, np.float64)
     basis = [len_basis(p) for p in params]
     roots = np.array([b[0] for b in basis])
@@ -136,22 +138,28 @@ def length_step(params, obs, projs, lens, free=None, max_iter=10):
     trace = []
     if not free.any() or max_iter <= 0:
         return lens, free, dict(E0=E0, E=E, trace=trace)
-    mu = LM_MU0
+    mu = mu0
     for _ in range(max_iter):
         Hf = H[np.ix_(free, free)]
         d = np.linalg.solve(Hf + mu * np.diag(np.diag(Hf)), -g[free])
         # (stops before a trial whose predicted reduction is below LM_FTOL E: such a trial's accept / reject is decided by rounding)
-        if np.abs(d).max() < LM_XTOL or -(d @ g[free] + 0.5 * d @ Hf @ d) < LM_FTOL * E:
+        dmax, pred = np.abs(d).max(), -(d @ g[free] + 0.5 * d @ Hf @ d)
+        look = dict(E=E, dmax=dmax, pred=pred, stop="xtol" if dmax < xtol else "pred" if pred < ftol * E else None)
+        if log is not None:
+            log.append(look)
+        if look["stop"]:
             break
         trial = lens.copy()
         trial[free] += d
         E2, H2, g2 = len_terms(roots, As, pv_prob, pv_P, pv_obs, trial)
+        look.update(Et=E2, accepted=bool(E2 < E))
         if E2 < E:
             red = E - E2
             lens, E_old, E, H, g = trial, E, E2, H2, g2
             mu /= 10.0
             trace.append(1)
-            if red < LM_FTOL * E_old:
+            if red < ftol * E_old:
+                look["stop"] = "ftol"
                 break
         else:
             mu *= 10.0
@@ -159,12 +167,76 @@ def length_step(params, obs, projs, lens, free=None, max_iter=10):
     return lens, free, dict(E0=E0, E=E, trace=trace)
 
 
-def pose_step(param, ob, pr, lens, max_nfev=5):
-    """solve_pose_reproj with the identity's lengths, warm from the problem's pose -> (params (68,), cost)."""
+def length_margins(log, ftol=LM_FTOL, xtol=LM_XTOL):
+    """The smallest relative distance of a length step's decisions from their thresholds (length_step's log): dict(trial = |Et - E| / E
+    over the trials, pred = |pred / (ftol E) - 1| and dmax = |dmax / xtol - 1| over the looks, red = |(E - Et) / (ftol E) - 1| over the
+    accepted trials); inf where there was no such decision."""
+    m = dict(trial=np.inf, pred=np.inf, dmax=np.inf, red=np.inf)
+    for k in log:
+        m["dmax"] = min(m["dmax"], abs(k["dmax"] / xtol - 1.0))
+        if k["stop"] != "xtol":                     # (the kernel's || evaluates pred either way; it decides only past the xtol test)
+            m["pred"] = min(m["pred"], abs(k["pred"] / (ftol * k["E"]) - 1.0) if ftol * k["E"] > 0 else np.inf)
+        if "Et" in k:
+            m["trial"] = min(m["trial"], abs(k["Et"] - k["E"]) / k["E"])
+            if k["accepted"]:
+                m["red"] = min(m["red"], abs((k["E"] - k["Et"]) / (ftol * k["E"]) - 1.0) if ftol * k["E"] > 0 else np.inf)
+    return m
+
+
+def pose_step(param, ob, pr, lens, max_nfev=5, trace=None):
+    """solve_pose_reproj with the identity's lengths, warm from the problem's pose -> (params (68,), cost).  trace: trf_np.trf's."""
     f1 = lambda x: o.ik_residual(x[:3], x[3:57], lens, ob, pr)
     j1 = lambda x, f: t.ik_jacobian(x[:3], x[3:57], lens, ob, pr, False)
-    r = t.trf(f1, j1, param[:57].copy(), max_nfev, solver="ne_clean")
+    r = t.trf(f1, j1, param[:57].copy(), max_nfev, solver="ne_clean", trace=trace)
     return np.concatenate([r["x"], lens]), r["cost"]
+
+
+def pose_margin(trace, ftol=1e-8, xtol=1e-8, gtol=1e-8):
+    """The smallest relative distance of a pose step's trust-region decisions from their thresholds (trf_np.trf's trace): the trial's
+    cost against the cost, the ratio against 0.25 and 0.75, the step against 0.95 Delta, the reduction against ftol cost, the step
+    against xtol (xtol + |x|), the gradient against gtol; and the weakest eigenvalue of a model relative to its largest, where it lies
+    between the null cluster (1e-13) and 1e-6 (tests/test_gpu_ik_whole_solves.py: such a model's step is not reproducible to 1e-8 m)."""
+    m = np.inf
+    for e in trace:
+        if "model" in e:
+            lam = e["lam"] / e["lam"][0]
+            weak = lam[(lam > 1e-13) & (lam < 1e-6)]
+            m = min([m, abs(e["g_inf"] / gtol - 1.0)] + ([0.0] if weak.size else []))
+            continue
+        red = e["cost"] - e["cost_new"]
+        m = min(m, abs(red) / e["cost"], abs(e["ratio"] / 0.25 - 1.0), abs(e["ratio"] / 0.75 - 1.0),
+                abs(e["step_norm"] / (0.95 * e["Delta"]) - 1.0), abs(red / (ftol * e["cost"]) - 1.0),
+                abs(e["step_norm"] / (xtol * (xtol + np.linalg.norm(e["x"]))) - 1.0))
+    return m
+
+
+def select_padded(kps17, counts, Pmats, frame_of, rig_of, rank, joints, max_dist=D_MAX):
+    """select() on the device's own tables (include/mvmc.h: mvmc_body_observe), which may hold what ingest would have filtered: kps17
+    (F,C,P,17,3) read as given, counts (F,C) clamped to [0, P], Pmats (R,C,3,4); per problem frame_of (a row of kps17: two problems
+    compete when they name the same row), rig_of, rank, joints (B,18,3).  A problem whose frame or rig is out of range chooses nothing.
+    -> choice (B,C) pose index (f C + c) P + p before the conflicts or -1, dist (B,C), members (B,C), n_views (B,)."""
+    F, C, Pmax = kps17.shape[:3]
+    B = len(frame_of)
+    choice = -np.ones((B, C), np.int64)
+    dist = np.full((B, C), np.inf)
+    for b in range(B):
+        f, r = int(frame_of[b]), int(rig_of[b])
+        if not (0 <= f < F and 0 <= r < Pmats.shape[0]):
+            continue
+        for c in range(C):
+            for p in range(min(max(int(counts[f, c]), 0), Pmax)):
+                d = reproj_dist(joints[b], kps17[f, c, p], Pmats[r, c])
+                if d < max_dist and d < dist[b, c]:              # (NaN: never a candidate)
+                    choice[b, c], dist[b, c] = (f * C + c) * Pmax + p, d
+    members = choice.copy()
+    for b in range(B):
+        for c in range(C):
+            for b2 in range(B):
+                if choice[b, c] < 0 or b2 == b or frame_of[b2] != frame_of[b] or choice[b2, c] != choice[b, c]:
+                    continue
+                if dist[b2, c] < dist[b, c] or (dist[b2, c] == dist[b, c] and rank[b2] < rank[b]):
+                    members[b, c] = -1
+    return choice, dist, members, (members >= 0).sum(axis=1)
 
 
 def observations(sel_row, views_f, P):
