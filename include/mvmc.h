@@ -1000,6 +1000,43 @@ int mvmc_pair_refit(const double* xn, const int32_t* seq, const int32_t* pair, i
                     const double* norm, const double* E, const int32_t* count, const double* thr, int n_hyp, int refit_rounds,
                     double* pose, int32_t* round_count, int32_t* mask, double* points, mvmcStream_t stream);
 
+/* ---- detections with exchanged left / right limbs (multiview_motion_capture_amd/exchanges.py; restated in tests/exchange_np.py).  No
+ * counterpart in the reference.  Against the 3-D joints of finished records, every detection's arms, legs and face are tested for a
+ * left / right exchange of their labels and the exchange is undone in the caller's keypoints.
+ * Limb groups as COCO-17 pairs (left, right): arms (5,6) (7,8) (9,10), flag bit 0; legs (11,12) (13,14) (15,16), bit 1; face (3,4),
+ * bit 2 -- the pairs among reprojection_error's 15 common joints (motion_capture.py:403-414), compared with the same BASIC_18 joints;
+ * the eyes (1,2) follow the face, in BODY_25 input the feet (19,20,21) <-> (22,23,24) follow the legs.
+ *
+ * mvmc_exchange_observe: mvmc_body_observe's problems, arguments and conflict rule with an exchange-aware distance.  Per (problem b,
+ * camera c) the problem's joints are projected once (1e-5 in the denominator).  For a pose of b's frame in camera c, a common keypoint
+ * is valid when its score > min_score; a group's costs run over its pairs with BOTH keypoints valid, summed in the order above, left
+ * keypoint before right: e0 the pixel distances under the labels as they are, e1 with each keypoint compared with the other side's
+ * joint; n_g the keypoints counted.  d* = (the as-is distances of the valid keypoints outside such pairs -- pair order, then the nose
+ * -- + min(e0, e1) of arms, legs, face in this order) / (valid common keypoints).  The pose with the smallest d* that is finite and
+ * below max_dist is chosen (ties: the lower slot); then, as in mvmc_body_observe, of two problems of one frame that chose one pose
+ * the smaller d* keeps it (equal: the lower rank), the other takes nothing.  Group g of the pose a problem keeps is exchanged iff
+ * n_g >= 2 and e1 + margin_px n_g < e0 and e1 < ratio e0 (both strict; products and sums rounded one by one).
+ *   kps17, counts, n_frames, n_views, p_max, Pmats, n_rigs, frame_of, rig_of, joints, order, grp_lo, grp_hi, rank, n_problems,
+ *   min_score, max_dist: as mvmc_body_observe.  margin_px finite and >= 0, 0 < ratio <= 1: else MVMC_ERR_ARG
+ *   members (B,C) i32 out: the kept pose index q = (f C + c) P + p, or -1; dist (B,C) f64 out: d* of the nearest pose BEFORE the
+ *   conflicts (+inf: none); flags (B,C) u8 out: bit g = group g of the kept pose is exchanged (0 without one); cost (B,C,3,2) f64
+ *   out: e0, e1 per group of the kept pose, NaN for a group without a fully valid pair and where no pose is kept
+ * No workspace, no allocation, no synchronisation, no atomics: every sum runs inside one lane in a fixed order, so a problem's
+ * outputs are the same bits alone, in a batch and from run to run. */
+int mvmc_exchange_observe(const double* kps17, const int32_t* counts, int n_frames, int n_views, int p_max, const double* Pmats,
+                          int n_rigs, const int32_t* frame_of, const int32_t* rig_of, const double* joints, const int32_t* order,
+                          const int32_t* grp_lo, const int32_t* grp_hi, const int32_t* rank, int n_problems, double min_score,
+                          double max_dist, double margin_px, double ratio, int32_t* members, double* dist, uint8_t* flags,
+                          double* cost, mvmcStream_t stream);
+
+/* mvmc_exchange_apply: the repaired copy of the caller's keypoints.  kps_in, kps_out (n_slots, n_joints, 3) f32|f64 (dtype as
+ * mvmc_ingest; n_joints 17 or 25; n_slots = F C P pose slots, different buffers); slot_flags (n_slots) u8: bit g = exchange group g
+ * of the slot.  One lane per (x, y, score) triple copies the triple that belongs under its name: its partner's where the slot's flag
+ * names its group -- also in a pair of which only one keypoint was valid, and in the followers -- its own otherwise.  No arithmetic
+ * and no conversion: every triple of the output is a triple of the input, bit for bit. */
+int mvmc_exchange_apply(const void* kps_in, int dtype, long long n_slots, int n_joints, const uint8_t* slot_flags, void* kps_out,
+                        mvmcStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

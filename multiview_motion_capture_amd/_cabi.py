@@ -57,6 +57,7 @@ SYMBOLS = (
     "mvmc_rig_part_doubles_intr", "mvmc_rig_red_doubles_intr", "mvmc_rig_accumulate_intr", "mvmc_rig_step_intr",
     "mvmc_lens_undistort", "mvmc_lens_distort",
     "mvmc_pair_moments", "mvmc_pair_consensus", "mvmc_pair_refit",
+    "mvmc_exchange_observe", "mvmc_exchange_apply",
     "mvmc_debug_st_affinity_wg", "mvmc_debug_track_wave",
 )
 
@@ -207,6 +208,8 @@ def load():
         "mvmc_pair_moments": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp],
         "mvmc_pair_consensus": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
         "mvmc_pair_refit": [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp],
+        "mvmc_exchange_observe": [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, vp, vp, vp, vp],
+        "mvmc_exchange_apply": [vp, i32, C.c_longlong, i32, vp, vp, vp],
     }
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
                 "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong,

@@ -398,6 +398,50 @@ def body_observe(kps17: torch.Tensor, counts: torch.Tensor, Pmats: torch.Tensor,
     return members, n_views, choice, dist
 
 
+def exchange_observe(kps17: torch.Tensor, counts: torch.Tensor, Pmats: torch.Tensor, frame_of: torch.Tensor, rig_of: torch.Tensor,
+                     joints: torch.Tensor, order: torch.Tensor, grp_lo: torch.Tensor, grp_hi: torch.Tensor, rank: torch.Tensor,
+                     max_dist: float, min_score=0.1, margin_px=4.0, ratio=0.7):
+    """Exchange-aware observation selection (include/mvmc.h: mvmc_exchange_observe); the arguments of body_observe plus the decision's
+    margin_px and ratio -> members (B,C) i32 (kept pose index into kps17 or -1), dist (B,C) f64 (d* of the nearest pose before the
+    conflicts, +inf: none), flags (B,C) u8 (bit 0 arms, 1 legs, 2 face exchanged), cost (B,C,3,2) f64 (e0, e1 per group, NaN:
+    undecided)."""
+    F, Cn, P = kps17.shape[:3]
+    _req(kps17, torch.float64, "kps17", (F, Cn, P, 17, 3))
+    _req(counts, torch.int32, "counts", (F, Cn))
+    _req(Pmats, torch.float64, "Pmats", (None, Cn, 3, 4))
+    B = joints.shape[0]
+    _req(joints, torch.float64, "joints", (B, 18, 3))
+    for name, t in (("frame_of", frame_of), ("rig_of", rig_of), ("order", order), ("grp_lo", grp_lo), ("grp_hi", grp_hi),
+                    ("rank", rank)):
+        _req(t, torch.int32, name, (B,))
+    d = joints.device
+    members = torch.empty((B, Cn), dtype=torch.int32, device=d)
+    dist = torch.empty((B, Cn), dtype=torch.float64, device=d)
+    flags = torch.empty((B, Cn), dtype=torch.uint8, device=d)
+    cost = torch.empty((B, Cn, 3, 2), dtype=torch.float64, device=d)
+    check(_cabi.load().mvmc_exchange_observe(_p(kps17), _p(counts), F, Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(frame_of), _p(rig_of),
+                                             _p(joints), _p(order), _p(grp_lo), _p(grp_hi), _p(rank), B, float(min_score),
+                                             float(max_dist), float(margin_px), float(ratio), _p(members), _p(dist), _p(flags), _p(cost),
+                                             _stream()), "mvmc_exchange_observe")
+    return members, dist, flags, cost
+
+
+def exchange_apply(kps: torch.Tensor, slot_flags: torch.Tensor) -> torch.Tensor:
+    """The repaired copy of kps (F,C,P,25|17,3) f32|f64 (include/mvmc.h: mvmc_exchange_apply): slot_flags (F,C,P) u8, bit 0 arms, 1
+    legs, 2 face of the slot exchanged.  Same shape and dtype; every triple of the result is a triple of the input."""
+    if not isinstance(kps, torch.Tensor) or kps.dtype not in (torch.float32, torch.float64):
+        raise ValueError("exchange_apply: kps must be float32 or float64")
+    _req(kps, kps.dtype, "kps")
+    if kps.dim() != 5 or kps.shape[3] not in (17, 25) or kps.shape[4] != 3:
+        raise ValueError(f"exchange_apply: expected (F,C,P,25|17,3), got {tuple(kps.shape)}")
+    F, Cn, P, J, _ = kps.shape
+    _req(slot_flags, torch.uint8, "slot_flags", (F, Cn, P))
+    out = torch.empty_like(kps)
+    dt = _cabi.MVMC_F32 if kps.dtype == torch.float32 else _cabi.MVMC_F64
+    check(_cabi.load().mvmc_exchange_apply(_p(kps), dt, F * Cn * P, J, _p(slot_flags), _p(out), _stream()), "mvmc_exchange_apply")
+    return out
+
+
 def body_lengths(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor, members: torch.Tensor, params: torch.Tensor,
                  id_lo: torch.Tensor, lens: torch.Tensor, free_mask: torch.Tensor, fix_free: bool, max_iter: int, mu0: float,
                  ftol: float, xtol: float, skeleton: Optional[MvmcSkeleton] = None):
