@@ -47,6 +47,16 @@ def _req(t: torch.Tensor, dtype, name: str, shape=None):
     return t
 
 
+def _call(name: str, *args) -> None:
+    """The library's entry ``name`` on the current stream (its last argument); a status other than MVMC_OK raises."""
+    check(getattr(_cabi.load(), name)(*args, _stream()), name)
+
+
+def _ground4(ground):
+    """(normal (3,), offset) or None -> the 4 host doubles {normal, offset} the contact entries take, or None."""
+    return None if ground is None else (C.c_double * 4)(*[float(v) for v in ground[0]], float(ground[1]))
+
+
 # ----------------------------------------------------------------------------
 # skeleton constants (inverse_kinematics.py:120-173) -- data, restated
 # ----------------------------------------------------------------------------
@@ -502,29 +512,23 @@ def smooth_blocks(kps17: torch.Tensor, Pmats: torch.Tensor, rig_of: torch.Tensor
     _req(blk, torch.float64, "blk", (2, N, _cabi.SMOOTH_BLOCK_DOUBLES))
     if (normals is None) != (floor_weight is None) or (normals is not None and cmask is None):
         raise ValueError("smooth_blocks: normals and floor_weight go together, with cmask, anchors and contact_weight")
+    name = "mvmc_smooth_blocks"
+    args = [C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of), _p(ctl), N, _p(blk)]
     if cmask is not None or anchors is not None or contact_weight is not None:
         if cmask is None or anchors is None or contact_weight is None:
             raise ValueError("smooth_blocks: cmask, anchors and contact_weight go together")
         _req(cmask, torch.int32, "cmask", (N, 2))
         _req(anchors, torch.float64, "anchors", (N, 2, 3))
-        code, px = smooth_loss_args(loss, loss_px, "smooth_blocks")
+        name += "_contact"
+        args += [*smooth_loss_args(loss, loss_px, "smooth_blocks"), _p(cmask), _p(anchors), float(contact_weight)]
         if normals is not None:
             _req(normals, torch.float64, "normals", (Pmats.shape[0], 3))
-            check(_cabi.load().mvmc_smooth_blocks_floor(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
-                                                        _p(ctl), N, _p(blk), code, px, _p(cmask), _p(anchors), float(contact_weight),
-                                                        _p(normals), float(floor_weight), _stream()), "mvmc_smooth_blocks_floor")
-            return
-        check(_cabi.load().mvmc_smooth_blocks_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
-                                                      _p(ctl), N, _p(blk), code, px, _p(cmask), _p(anchors), float(contact_weight),
-                                                      _stream()), "mvmc_smooth_blocks_contact")
-        return
-    if loss is None:
-        check(_cabi.load().mvmc_smooth_blocks(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of), _p(ctl),
-                                              N, _p(blk), _stream()), "mvmc_smooth_blocks")
-        return
-    code, px = smooth_loss_args(loss, loss_px, "smooth_blocks")
-    check(_cabi.load().mvmc_smooth_blocks_robust(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), _p(rig_of), _p(members), _p(x), _p(id_of),
-                                                 _p(ctl), N, _p(blk), code, px, _stream()), "mvmc_smooth_blocks_robust")
+            name = "mvmc_smooth_blocks_floor"
+            args += [_p(normals), float(floor_weight)]
+    elif loss is not None:
+        name += "_robust"
+        args += smooth_loss_args(loss, loss_px, "smooth_blocks")
+    _call(name, *args)
 
 
 def smooth_contact_anchors(joints: torch.Tensor, id_lo: torch.Tensor, cmask: torch.Tensor, anchors: torch.Tensor, ctl: torch.Tensor,
@@ -540,9 +544,7 @@ def smooth_contact_anchors(joints: torch.Tensor, id_lo: torch.Tensor, cmask: tor
     _req(cmask, torch.int32, "cmask", (N, 2))
     _req(anchors, torch.float64, "anchors", (N, 2, 3))
     _req(ctl, torch.int32, "ctl", (n_ids, 4))
-    g = None
-    if ground is not None:
-        g = (C.c_double * 4)(*[float(v) for v in ground[0]], float(ground[1]))
+    g = _ground4(ground)
     check(_cabi.load().mvmc_smooth_contact_anchors(_p(joints), _p(id_lo), n_ids, N, int(bool(detect)), float(speed), int(min_run),
                                                    int(g is not None), g, float(height), _p(cmask), _p(anchors), _p(ctl), _stream()),
           "mvmc_smooth_contact_anchors")
@@ -670,33 +672,24 @@ def smooth_window(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Tensor,
     rv, ra, av, aa = (float(w) for w in weights)
     info = torch.empty((n, _cabi.SMOOTH_WIN_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
     work = smooth_window_work(n, window, rows.device)
+    name = "mvmc_smooth_window"
+    args = [C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(new_params), _p(new_members), B, _p(rows),
+            _p(members), _p(count), n_slots, int(window), int(n_iter), rv, ra, av, aa, float(mu0), float(ftol), float(xtol), _p(info),
+            _p(work), int(work.numel())]
     if contact is not None:
         _req(contact["labels"], torch.int32, "contact labels", (n_slots, _cabi.SMOOTH_WIN_RING, 2))
         _req(contact["anchors"], torch.float64, "contact anchors", (n_slots, _cabi.SMOOTH_WIN_RING, 2, 3))
         code, px = smooth_loss_args(loss, loss_px, "smooth_window")
-        g = None
-        if contact["ground"] is not None:
-            g = (C.c_double * 4)(*[float(v) for v in contact["ground"][0]], float(contact["ground"][1]))
+        g = _ground4(contact["ground"])
         cinfo = torch.empty((n, _cabi.SMOOTH_LIVE_CONTACT_DOUBLES), dtype=torch.float64, device=rows.device)
-        check(_cabi.load().mvmc_smooth_window_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n,
-                                                      _p(new_params), _p(new_members), B, _p(rows), _p(members), _p(count), n_slots,
-                                                      int(window), int(n_iter), rv, ra, av, aa, float(mu0), float(ftol), float(xtol),
-                                                      _p(info), _p(work), int(work.numel()), code, px, _p(contact["labels"]),
-                                                      _p(contact["anchors"]), int(contact["lag"]), float(contact["weight"]),
-                                                      float(contact["speed"]), int(contact["min_frames"]), int(g is not None), g,
-                                                      float(contact["height"]), _p(cinfo), _stream()), "mvmc_smooth_window_contact")
+        _call(name + "_contact", *args, code, px, _p(contact["labels"]), _p(contact["anchors"]), int(contact["lag"]),
+              float(contact["weight"]), float(contact["speed"]), int(contact["min_frames"]), int(g is not None), g,
+              float(contact["height"]), _p(cinfo))
         return info, cinfo
     if loss is None:
-        check(_cabi.load().mvmc_smooth_window(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(new_params),
-                                              _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window), int(n_iter), rv, ra,
-                                              av, aa, float(mu0), float(ftol), float(xtol), _p(info), _p(work), int(work.numel()), _stream()),
-              "mvmc_smooth_window")
-        return info
-    code, px = smooth_loss_args(loss, loss_px, "smooth_window")
-    check(_cabi.load().mvmc_smooth_window_robust(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n,
-                                                 _p(new_params), _p(new_members), B, _p(rows), _p(members), _p(count), n_slots, int(window),
-                                                 int(n_iter), rv, ra, av, aa, float(mu0), float(ftol), float(xtol), _p(info), _p(work),
-                                                 int(work.numel()), code, px, _stream()), "mvmc_smooth_window_robust")
+        _call(name, *args)
+    else:
+        _call(name + "_robust", *args, *smooth_loss_args(loss, loss_px, "smooth_window"))
     return info
 
 
@@ -734,19 +727,15 @@ def smooth_window_cov(kps17: torch.Tensor, Pmats: torch.Tensor, items: torch.Ten
     pvar = torch.empty((n, _cabi.SMOOTH_K), dtype=torch.float64, device=rows.device)
     cinfo = torch.empty((n, _cabi.SMOOTH_COV_INFO_DOUBLES), dtype=torch.float64, device=rows.device)
     work = smooth_window_cov_work(n, window, rows.device)
+    name = "mvmc_smooth_window_cov"
+    args = [C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(rows), _p(members), _p(count), n_slots,
+            int(window), rv, ra, av, aa, float(mu), int(bool(full)), code, px, _p(work), int(work.numel()), _p(jcov), _p(pvar), _p(cinfo)]
     if contact is not None:
         _req(contact["labels"], torch.int32, "contact labels", (n_slots, _cabi.SMOOTH_WIN_RING, 2))
         _req(contact["anchors"], torch.float64, "contact anchors", (n_slots, _cabi.SMOOTH_WIN_RING, 2, 3))
-        check(_cabi.load().mvmc_smooth_window_cov_contact(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n,
-                                                          _p(rows), _p(members), _p(count), n_slots, int(window), rv, ra, av, aa,
-                                                          float(mu), int(bool(full)), code, px, _p(work), int(work.numel()), _p(jcov),
-                                                          _p(pvar), _p(cinfo), _p(contact["labels"]), _p(contact["anchors"]),
-                                                          float(contact["weight"]), _stream()), "mvmc_smooth_window_cov_contact")
-        return jcov, pvar, cinfo
-    check(_cabi.load().mvmc_smooth_window_cov(C.byref(sk), _p(kps17), Cn, P, _p(Pmats), int(Pmats.shape[0]), _p(items), n, _p(rows),
-                                              _p(members), _p(count), n_slots, int(window), rv, ra, av, aa, float(mu), int(bool(full)),
-                                              code, px, _p(work), int(work.numel()), _p(jcov), _p(pvar), _p(cinfo), _stream()),
-          "mvmc_smooth_window_cov")
+        name += "_contact"
+        args += [_p(contact["labels"]), _p(contact["anchors"]), float(contact["weight"])]
+    _call(name, *args)
     return jcov, pvar, cinfo
 
 

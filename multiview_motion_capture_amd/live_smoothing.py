@@ -81,21 +81,42 @@ from __future__ import annotations
 
 import math
 import time
-from typing import Dict, List, Optional, Sequence
+from dataclasses import dataclass, field
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
+from . import smoothing
+from ._cabi import (LIVE_LEN_INFO_DOUBLES, LIVE_LEN_STATE_DOUBLES, N_PARAM, SMOOTH_COV_INFO_DOUBLES, SMOOTH_JOINTS, SMOOTH_K,
+                    SMOOTH_LIVE_CONTACT_DOUBLES, SMOOTH_MAX_VIEWS, SMOOTH_WIN_INFO_DOUBLES, SMOOTH_WIN_MAX, SMOOTH_WIN_RING)
 from .body_fit import MAX_DIST, MIN_SCORE
 from .sequences import frame_buckets, new_record, pose_slot, pose_tuples
-from .smoothing import (ANG_ACC, ANG_VEL, CONTACT_HEIGHT, CONTACT_MIN_FRAMES, CONTACT_SPEED, CONTACT_WEIGHT, COV_MU, LM_FTOL, LM_MU0,
-                        LM_XTOL, LOSS_PX, ROOT_ACC, ROOT_VEL, _check_contact_args, check_loss, unwrap_euler_many)
+from .smoothing import (ANG_ACC, ANG_VEL, CONTACT_HEIGHT, CONTACT_MIN_FRAMES, CONTACT_SPEED, CONTACT_WEIGHT, COV_E_DATA, COV_EDOF, COV_MU,
+                        COV_NRES, COV_STATUS, INFO_COST, INFO_STOP, INFO_TRACE, INFO_TRIALS, LM_FTOL, LM_MU0, LM_XTOL, LOSS_PX, ROOT_ACC,
+                        ROOT_VEL, check_loss, scale_covariance, unwrap_euler_many)
 from .tracker import T_WIDE
 
+ANGLES = slice(3, 3 + 3 * SMOOTH_JOINTS)     # the Euler triples in a row of N_PARAM parameters: after the root, before the lengths
 LENGTHS_PRIOR = 100.0  # px^2 / m^2: the weight of the identity's first lengths in the running skeleton (tools/live_lengths_probe.py)
-WINDOW_MAX = 32     # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
-N_ITER_MAX = 8      # include/mvmc.h: MVMC_SMOOTH_WIN_INFO_DOUBLES - 8
-RING = 66           # include/mvmc.h: MVMC_SMOOTH_WIN_RING
-MAX_VIEWS = 64      # include/mvmc.h: MVMC_SMOOTH_MAX_VIEWS
+WINDOW_MAX = SMOOTH_WIN_MAX                  # include/mvmc.h: MVMC_SMOOTH_WIN_MAX
+N_ITER_MAX = SMOOTH_WIN_INFO_DOUBLES - 8     # include/mvmc.h: "n_iter <= MVMC_SMOOTH_WIN_INFO_DOUBLES - 8"
+RING = SMOOTH_WIN_RING                       # include/mvmc.h: MVMC_SMOOTH_WIN_RING
+MAX_VIEWS = SMOOTH_MAX_VIEWS                 # include/mvmc.h: MVMC_SMOOTH_MAX_VIEWS
+# The columns of the device's outputs and state, each with the line of include/mvmc.h it restates.
+# (mvmc_smooth_window's info and mvmc_smooth_window_cov's cinfo have the offline entries' columns: smoothing.INFO_*, COV_*)
+STATUS_MALFORMED = 6                         # the stop reason / status of a skipped item, in info, cinfo and linfo alike
+# mvmc_smooth_window_contact, cinfo: "label L, R and anchor L (3), R (3) of the row n - 1 - lag (...), E_contact at the start and at
+# the end of the tick"
+CINFO_LABELS, CINFO_ANCHORS, CINFO_COST = slice(0, 2), slice(2, 8), slice(8, 10)
+# mvmc_live_lengths_update, linfo: "{status (...), rows contributed this tick, contributed, committed, committed_row, l (11), 1/2 sum
+# r^2 of this tick's contributing rows}"
+LINFO_STATUS, LINFO_CONTRIBUTED, LINFO_COMMITTED, LINFO_COMMITTED_ROW, LINFO_LENGTHS = 0, 2, 3, 4, slice(5, 16)
+# lens_state: "[77, 88) l, the current skeleton ... 99 next_row 100 contributed 101 committed (0 / 1) 102 committed_row (-1 before)"
+LENS_L, LENS_CONTRIBUTED, LENS_COMMITTED_ROW = slice(77, 88), 100, 102
+# the names above end where the header's widths (_cabi) end
+assert INFO_TRACE + N_ITER_MAX == SMOOTH_WIN_INFO_DOUBLES and CINFO_COST.stop == SMOOTH_LIVE_CONTACT_DOUBLES
+assert COV_EDOF < SMOOTH_COV_INFO_DOUBLES and LINFO_LENGTHS.stop + 1 == LIVE_LEN_INFO_DOUBLES
+assert LENS_COMMITTED_ROW + 1 == LIVE_LEN_STATE_DOUBLES
 
 
 def check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc) -> np.ndarray:
@@ -106,43 +127,26 @@ def check_parameters(window, lag, n_iter, root_vel, root_acc, ang_vel, ang_acc) 
         raise ValueError("LiveSmoother: 0 <= lag < window required")
     if int(n_iter) != n_iter or not 1 <= int(n_iter) <= N_ITER_MAX:
         raise ValueError(f"LiveSmoother: 1 <= n_iter <= {N_ITER_MAX} required")
-    w = np.array([root_vel, root_acc, ang_vel, ang_acc], dtype=np.float64)
-    if not np.all(np.isfinite(w)) or np.any(w < 0):
-        raise ValueError("LiveSmoother: the prior weights must be finite and >= 0")
-    if not (w[0] + w[1] > 0 and w[2] + w[3] > 0):
-        raise ValueError("LiveSmoother: root_vel + root_acc > 0 and ang_vel + ang_acc > 0 required")
-    return w
+    return smoothing.check_prior_weights("LiveSmoother", root_vel, root_acc, ang_vel, ang_acc)
 
 
 def check_covariance(covariance, noise_px) -> Optional[float]:
-    """LiveSmoother's covariance arguments (host only; smoothing._check_covariance's rules) -> noise_px as a float, or None."""
-    if covariance is not None and not (isinstance(covariance, str) and covariance == "joints"):
-        raise ValueError(f"LiveSmoother: covariance must be None or \"joints\", got {covariance!r}")
-    if noise_px is None:
-        return None
-    if covariance is None:
-        raise ValueError("LiveSmoother: noise_px without covariance=\"joints\" has nothing to scale")
-    if isinstance(noise_px, (str, bytes, bool)) or not isinstance(noise_px, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(noise_px) or not noise_px > 0:
-        raise ValueError(f"LiveSmoother: noise_px must be None or a finite number > 0, got {noise_px!r}")
-    return float(noise_px)
+    """LiveSmoother's covariance arguments (host only; smooth_sequences' rules) -> noise_px as a float, or None."""
+    return smoothing.check_covariance("LiveSmoother", covariance, noise_px)
 
 
 def check_contacts(contacts, contact_weight, contact_speed, contact_min_frames, ground, contact_height, lag) -> Optional[dict]:
-    """LiveSmoother's foot-contact arguments (host only; smoothing._check_contact_args' rules) -> None, or the launch's dict."""
+    """LiveSmoother's foot-contact arguments (host only; smooth_sequences' rules for the scalars) -> None, or the launch's dict."""
     if contacts is None:
         return None
     if not (isinstance(contacts, str) and contacts == "auto"):
         raise ValueError(f"LiveSmoother: contacts must be None or \"auto\", got {contacts if isinstance(contacts, (str, bool)) else type(contacts).__name__!r}")
-    try:
-        _, wc, speed, min_frames, _, g, height = _check_contact_args("auto", contact_weight, contact_speed, contact_min_frames, 1, ground,
-                                                                     contact_height)
-    except ValueError as e:
-        raise ValueError(str(e).replace("smooth_sequences", "LiveSmoother")) from None
-    if int(lag) + 1 < min_frames:
-        raise ValueError(f"LiveSmoother: lag + 1 >= contact_min_frames required (lag {int(lag)}, contact_min_frames {min_frames}): a run "
-                         "could not reach its length before it freezes")
-    return dict(lag=int(lag), weight=wc, speed=speed, min_frames=min_frames, ground=g, height=height)
+    c = smoothing._check_contact_args("auto", contact_weight, contact_speed, contact_min_frames, 1, ground, contact_height,
+                                      who="LiveSmoother")
+    if int(lag) + 1 < c.min_frames:
+        raise ValueError(f"LiveSmoother: lag + 1 >= contact_min_frames required (lag {int(lag)}, contact_min_frames {c.min_frames}): a "
+                         "run could not reach its length before it freezes")
+    return dict(lag=int(lag), weight=c.weight, speed=c.speed, min_frames=c.min_frames, ground=c.ground, height=c.height)
 
 
 def check_lengths(lengths, lengths_prior, lengths_commit) -> Optional[dict]:
@@ -150,9 +154,7 @@ def check_lengths(lengths, lengths_prior, lengths_commit) -> Optional[dict]:
     None: LENGTHS_PRIOR; a lengths_prior or a lengths_commit without lengths="auto" is an error, whatever its value."""
     if lengths is not None and not (isinstance(lengths, str) and lengths == "auto"):
         raise ValueError(f"LiveSmoother: lengths must be None or \"auto\", got {lengths if isinstance(lengths, (str, bool)) else type(lengths).__name__!r}")
-    if lengths_prior is not None and (isinstance(lengths_prior, (str, bytes, bool))
-                                      or not isinstance(lengths_prior, (int, float, np.integer, np.floating))
-                                      or not math.isfinite(lengths_prior) or not lengths_prior > 0):
+    if lengths_prior is not None and (not smoothing._number(lengths_prior) or not math.isfinite(lengths_prior) or not lengths_prior > 0):
         raise ValueError(f"LiveSmoother: lengths_prior must be None or a finite number > 0, got {lengths_prior!r}")
     if lengths_commit is not None and (isinstance(lengths_commit, bool) or not isinstance(lengths_commit, (int, np.integer))
                                        or lengths_commit < 1):
@@ -187,15 +189,36 @@ def committed_part(record):
 
 def cov_entry(jc6, pv, ci, noise_px: Optional[float]) -> dict:
     """One emitted row's unit-variance device outputs (jcov (18,6), pvar (39,), cinfo (8,)) -> its TickOutput.cov entry."""
-    status, e_data, n_res, edof = int(ci[0]), float(ci[1]), float(ci[2]), float(ci[3])
-    if noise_px is not None:
-        s = noise_px
-    else:
-        s = math.sqrt(2.0 * e_data / (n_res - edof)) if status == 0 and n_res - edof > 0 else math.nan
-    jc = jc6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(18, 3, 3)
-    return dict(joint_cov=(s * s) * jc, joint_sigma=np.sqrt((s * s) * (jc[:, 0, 0] + jc[:, 1, 1] + jc[:, 2, 2])),
-                param_sigma=np.sqrt((s * s) * pv), noise_px=float(s), edof=edof,
+    status, e_data, n_res, edof = int(ci[COV_STATUS]), float(ci[COV_E_DATA]), float(ci[COV_NRES]), float(ci[COV_EDOF])
+    s, joint_cov, joint_sigma, param_sigma = scale_covariance(jc6, pv, status, e_data, n_res, edof, noise_px)
+    return dict(joint_cov=joint_cov, joint_sigma=joint_sigma, param_sigma=param_sigma, noise_px=s, edof=edof,
                 nres=int(n_res) if status == 0 and math.isfinite(n_res) else 0, status=status)
+
+
+class ReadBack:
+    """One read-back of several device tensors: they are registered under a name, fetch() concatenates them as float64, copies the
+    result to the host ONCE -- the caller's one synchronisation -- and hands the parts back by name in their registered shapes (views
+    of the one host array; integer and bool parts come back as float64)."""
+
+    def __init__(self):
+        self._parts: Dict[str, tuple] = {}
+
+    def add(self, name: str, tensor, shape=None) -> None:
+        """Registers ``tensor`` (any dtype that float64 holds exactly) under ``name``; ``shape``: the shape to hand back, default its own."""
+        if name in self._parts:
+            raise ValueError(f"ReadBack: the part {name!r} is registered twice")
+        self._parts[name] = (tensor, tuple(tensor.shape if shape is None else shape))
+
+    def fetch(self) -> Dict[str, np.ndarray]:
+        import torch
+        if not self._parts:
+            return {}
+        host = torch.cat([t.to(torch.float64).reshape(-1) for t, _ in self._parts.values()]).cpu().numpy()
+        out, at = {}, 0
+        for name, (t, shape) in self._parts.items():
+            out[name] = host[at:at + t.numel()].reshape(shape)
+            at += t.numel()
+        return out
 
 
 class TickOutput:
@@ -254,6 +277,39 @@ class _Session:
         self.key, self.s, self.calibs = key, s, list(calibs)
         self.f_last: Optional[int] = None
         self.ids: Dict[int, _Ident] = {}
+
+
+class _Problem(NamedTuple):
+    """One selection problem of a tick: a data row's joints against the frame its session delivered."""
+    ring: int                 # the frame's place in the keypoint ring
+    rig: int
+    joints: np.ndarray        # (18,3) the tracker's
+    slot: int                 # the identity's row in the session's table
+
+
+class _Stepped(NamedTuple):
+    """An identity a tick steps, in the order of the tick's items."""
+    key: object
+    idn: _Ident
+    f: int
+    emit_row: int             # the row of frame f - lag, negative: nothing is emitted yet
+    was_final: int            # the identity's final rows before the tick
+
+
+@dataclass
+class _TickPlan:
+    """What the host packs for one tick (LiveSmoother._pack) and hands to the launches and to the collection of the results."""
+    kps: np.ndarray                                      # (sessions, C, P, 25|17, 3) the delivered frames
+    counts: np.ndarray                                   # (sessions, C)
+    ring_at: np.ndarray                                  # (sessions,) their places in the keypoint ring
+    items: list = field(default_factory=list)            # per stepped identity the 8 ints of include/mvmc.h's window item
+    new_rows: list = field(default_factory=list)         # [(identity, params (68,))] the tick's data rows, the items' src
+    problems: List[_Problem] = field(default_factory=list)     # one per data row
+    stepped: List[_Stepped] = field(default_factory=list)      # one per item
+    finished: list = field(default_factory=list)         # [(key, identity)] the tracklets that left their session's table
+    want_fin: list = field(default_factory=list)         # [(identity, row)] read back: the finished identities' rows not final yet
+    want: list = field(default_factory=list)             # then per item the rows that leave the window and the emitted row
+    cov_of: list = field(default_factory=list)           # the items (indices into stepped) whose emitted row gets a covariance
 
 
 class LiveSmoother:
@@ -340,41 +396,56 @@ class LiveSmoother:
             self._st = dict(
                 d=d, kps=torch.zeros((self.capacity * self.W, self.C, self.P, 17, 3), dtype=torch.float64, device=d),
                 cnt=torch.zeros((self.capacity * self.W, self.C), dtype=torch.int32, device=d),
-                rows=torch.zeros((n_slots, RING, 68), dtype=torch.float64, device=d),
+                rows=torch.zeros((n_slots, RING, N_PARAM), dtype=torch.float64, device=d),
                 members=torch.full((n_slots, RING, self.C), -1, dtype=torch.int32, device=d),
                 count=torch.zeros((n_slots, 2), dtype=torch.int32, device=d), Pm=None)
             if self._ct is not None:      # per row and foot a label and an anchor, beside the rows
                 self._st["clab"] = torch.zeros((n_slots, RING, 2), dtype=torch.int32, device=d)
                 self._st["canc"] = torch.full((n_slots, RING, 2, 3), math.nan, dtype=torch.float64, device=d)
             if self._len is not None:     # per slot the running skeleton's A, b, l, l0 and counters (include/mvmc.h)
-                from ._cabi import LIVE_LEN_STATE_DOUBLES
                 self._st["lens"] = torch.zeros((n_slots, LIVE_LEN_STATE_DOUBLES), dtype=torch.float64, device=d)
         if self._Pm_dirty:
             self._st["Pm"] = torch.from_numpy(self._Pm_h.copy()).to(self._st["d"])
             self._Pm_dirty = False
         return self._st
 
+    def _gather(self, st, wanted, T) -> dict:
+        """[(ident, row)] -> their rows (n,68) as they stand on the device, with contacts also their labels (n,2) and anchors (n,2,3):
+        device tensors, nothing is read back."""
+        idx = T(np.array([i.slot * RING + r % RING for i, r in wanted], np.int64))
+        g = dict(rows=st["rows"].flatten(0, 1).index_select(0, idx))      # (slot, ring position) -> one axis
+        if self._ct is not None:
+            g["labels"] = st["clab"].flatten(0, 1).index_select(0, idx)
+            g["anchors"] = st["canc"].flatten(0, 1).index_select(0, idx)
+        return g
+
+    def _read_rows(self, rb: ReadBack, gathered: list) -> None:
+        """Registers the rows of _gather's results, one after the other, their FK joints and (with contacts) their labels and anchors
+        as "rows" (n,68), "joints" (n,18,3), "labels" (n,2), "anchors" (n,2,3)."""
+        import torch
+
+        from . import device as dev
+        cat = lambda name: torch.cat([g[name] for g in gathered]) if len(gathered) > 1 else gathered[0][name]
+        rows = cat("rows")
+        rb.add("rows", rows)
+        rb.add("joints", dev.fk(rows, self.skeleton))
+        if self._ct is not None:
+            rb.add("labels", cat("labels"))
+            rb.add("anchors", cat("anchors"))
+
     def _fetch(self, wanted):
         """[(ident, row)] -> per row (params (68,), joints (18,3)) as they stand on the device (one read-back); with contacts also the
         row's labels (2,) bool and anchors (2,3)."""
-        import torch
-
         from . import device as dev
         if not wanted:
             return []
         st = self._state()
-        idx = torch.as_tensor([i.slot * RING + r % RING for i, r in wanted], dtype=torch.int64).to(st["d"])
-        P = st["rows"].view(-1, 68).index_select(0, idx)
-        J = dev.fk(P, self.skeleton)
-        n = len(wanted)
+        rb = ReadBack()
+        self._read_rows(rb, [self._gather(st, wanted, dev.uploader(st["d"]))])
+        h = rb.fetch()
         if self._ct is None:
-            P_h, J_h = P.cpu().numpy(), J.cpu().numpy()
-            return [(P_h[k], J_h[k]) for k in range(n)]
-        host = torch.cat([P.reshape(-1), J.reshape(-1), st["clab"].view(-1, 2).index_select(0, idx).to(torch.float64).reshape(-1),
-                          st["canc"].view(-1, 6).index_select(0, idx).reshape(-1)]).cpu().numpy()
-        P_h, J_h = host[:n * 68].reshape(n, 68), host[n * 68:n * 122].reshape(n, 18, 3)
-        L_h, A_h = host[n * 122:n * 124].reshape(n, 2) != 0, host[n * 124:].reshape(n, 2, 3)
-        return [(P_h[k], J_h[k], L_h[k], A_h[k]) for k in range(n)]
+            return list(zip(h["rows"], h["joints"]))
+        return list(zip(h["rows"], h["joints"], h["labels"] != 0, h["anchors"]))
 
     # -- ticks -------------------------------------------------------------------------------------------------------------------------
     def _check_table(self, key, f, inputs, meta, params, joints):
@@ -397,7 +468,7 @@ class LiveSmoother:
             raise ValueError(f"session {key}: counts must be ({self.C},) with 0 <= counts <= {kps.shape[1]}")
         meta, params, joints = np.asarray(meta), np.asarray(params, np.float64), np.asarray(joints, np.float64)
         n = meta.shape[0] if meta.ndim == 2 else -1
-        if meta.ndim != 2 or meta.shape[1] != 4 or params.shape != (n, 68) or joints.shape != (n, 18, 3):
+        if meta.ndim != 2 or meta.shape[1] != 4 or params.shape != (n, N_PARAM) or joints.shape != (n, SMOOTH_JOINTS, 3):
             raise ValueError(f"session {key}: the table must be meta (n,4), params (n,68), joints (n,18,3)")
         if n > T_WIDE:
             raise ValueError(f"session {key}: {n} live identities, at most {T_WIDE}")
@@ -427,27 +498,34 @@ class LiveSmoother:
             return out
         if len({w[2].shape[2] for w in work}) != 1:
             raise ValueError("update_tables: the sessions of one tick must all deliver 25-row or all 17-row poses")
-        import torch
-
-        from . import device as dev
         st = self._state()
-        d, C, W = st["d"], self.C, self.W
-        T = dev.uploader(d)
-        # ---- host: the tick's rows, items and selection problems ----
-        J = work[0][2].shape[2]
-        kst = np.zeros((len(work), C, self.P, J, 3))
-        cst = np.zeros((len(work), C), np.int32)
-        ring_at = np.zeros(len(work), np.int64)
-        items, newp, prob, fin, solved_of = [], [], [], [], []
+        plan = self._pack(work)
+        t_pack = time.perf_counter()
+        host = self._launch(plan, st).fetch()      # the tick's one synchronisation
+        t_launch = time.perf_counter()
+        self._collect(plan, host, out)
+        t_end = time.perf_counter()
+        self.timings["pack"] += t_pack - t_start
+        self.timings["launch"] += t_launch - t_pack
+        self.timings["records"] += t_end - t_launch
+        return out
+
+    def _pack(self, work) -> _TickPlan:
+        """Stage 1, host: the checked tables [(key, f, kps, counts, meta, params, joints)] -> the tick's rows, items and selection
+        problems, and which rows are wanted back.  The identities' host records grow here; the device is not touched."""
+        C, W = self.C, self.W
+        plan = _TickPlan(kps=np.zeros((len(work), C, self.P, work[0][2].shape[2], 3)), counts=np.zeros((len(work), C), np.int32),
+                         ring_at=np.zeros(len(work), np.int64))
+        items, new_rows, problems, stepped = plan.items, plan.new_rows, plan.problems, plan.stepped
         for i, (key, f, kps, cnt, meta, params, joints) in enumerate(work):
             sess = self._sessions[key]
             dd = 1 if sess.f_last is None else f - sess.f_last
-            kst[i, :, :kps.shape[1]] = kps
-            cst[i] = cnt
-            ring_at[i] = sess.s * W + f % W
+            plan.kps[i, :, :kps.shape[1]] = kps
+            plan.counts[i] = cnt
+            plan.ring_at[i] = sess.s * W + f % W
             tids = [int(t) for t in meta[:, 0]]
             for tid in [t for t in sess.ids if t not in tids]:
-                fin.append((key, sess.ids.pop(tid)))
+                plan.finished.append((key, sess.ids.pop(tid)))
             for k, tid in enumerate(tids):
                 idn = sess.ids.get(tid)
                 new = idn is None
@@ -459,177 +537,164 @@ class LiveSmoother:
                 idn.append(data, C)
                 idn.hits, idn.state = int(meta[k, 2]), int(meta[k, 1])
                 if data:
-                    newp.append((idn, params[k].copy()))
-                    prob.append((int(ring_at[i]), sess.s, joints[k], k))
-                items.append([idn.slot, sess.s, dd, int(data), int(new), len(newp) - 1 if data else -1, f, len(items) * W])
-                solved_of.append((key, idn, f))
+                    new_rows.append((idn, params[k].copy()))
+                    problems.append(_Problem(int(plan.ring_at[i]), sess.s, joints[k], k))
+                # include/mvmc.h, an item: {slot, rig, d, is_data, reset, src, first_frame, work_row}
+                items.append([idn.slot, sess.s, dd, int(data), int(new), len(new_rows) - 1 if data else -1, f, len(items) * W])
+                stepped.append(_Stepped(key, idn, f, f - self.lag - idn.f0, idn.n_final))
             sess.f_last = f
-        pairs = [(idn, p) for idn, p in newp if idn.prev_in is not None]
-        un = unwrap_euler_many([np.stack([idn.prev_in, p[3:57].reshape(18, 3)]) for idn, p in pairs])
+        pairs = [(idn, p) for idn, p in plan.new_rows if idn.prev_in is not None]
+        un = unwrap_euler_many([np.stack([idn.prev_in, p[ANGLES].reshape(SMOOTH_JOINTS, 3)]) for idn, p in pairs])
         for (idn, p), u in zip(pairs, un):
-            p[3:57] = u[1].ravel()
-        for idn, p in newp:
-            idn.prev_in = p[3:57].reshape(18, 3).copy()
+            p[ANGLES] = u[1].ravel()
+        for idn, p in plan.new_rows:
+            idn.prev_in = p[ANGLES].reshape(SMOOTH_JOINTS, 3).copy()
         # rows wanted back: the finished identities' rows that are not final yet (gathered before the launch, their slots are free
         # for the tick's new identities), then per item the rows that leave the window and the emitted row
-        want_fin = []
-        for key, idn in fin:
-            keep = idn.last_data()
-            want_fin += [(idn, r) for r in range(idn.n_final, keep)]
+        for key, idn in plan.finished:
+            plan.want_fin += [(idn, r) for r in range(idn.n_final, idn.last_data())]
             self._free_id.append(idn.slot)
         self._free_id.sort()
-        want = []
-        was_final = [idn.n_final for _, idn, _ in solved_of]
-        for key, idn, f in solved_of:
-            nf = idn.n - min(W, idn.n)
-            want += [(idn, r) for r in range(idn.n_final, nf)]
-            idn.n_final = nf
-            if f - self.lag - idn.f0 >= 0:
-                want.append((idn, f - self.lag - idn.f0))
-        t_pack = time.perf_counter()
-        # ---- device: ingest into the sessions' rings, selection, ONE window launch, the rows wanted back ----
-        k17, c17 = dev.ingest(T(kst), T(cst))
-        at_d = T(ring_at)
+        for s in plan.stepped:
+            nf = s.idn.n - min(W, s.idn.n)
+            plan.want += [(s.idn, r) for r in range(s.idn.n_final, nf)]
+            s.idn.n_final = nf
+            if s.emit_row >= 0:
+                plan.want.append((s.idn, s.emit_row))
+        if self._cov:      # the emitted rows get a covariance; no launch when nothing is emitted (or it is not asked for)
+            plan.cov_of = [a for a, s in enumerate(plan.stepped) if s.emit_row >= 0]
+        return plan
+
+    def _launch(self, plan: _TickPlan, st) -> ReadBack:
+        """Stage 2, device: ingest into the sessions' rings, selection, the optional skeleton apply, ONE window launch, the optional
+        skeleton update and covariance launches, and the gathers of the rows wanted back.  Nothing is synchronised: what the host
+        needs is registered in the ReadBack this returns."""
+        import torch
+
+        from . import device as dev
+        d, C, W = st["d"], self.C, self.W
+        T = dev.uploader(d)
+        rb = ReadBack()
+        k17, c17 = dev.ingest(T(plan.kps), T(plan.counts))
+        at_d = T(plan.ring_at)
         st["kps"].index_copy_(0, at_d, k17)
         st["cnt"].index_copy_(0, at_d, c17)
-        slot_idx = lambda wl: T(np.array([i.slot * RING + r % RING for i, r in wl], np.int64))
-        i_fin = slot_idx(want_fin) if want_fin else None
-        P_fin = st["rows"].view(-1, 68).index_select(0, i_fin) if want_fin else None
         ct = None if self._ct is None else dict(labels=st["clab"], anchors=st["canc"], **self._ct)
-        if ct is not None and want_fin:      # the finished identities' labels and anchors, gathered before the launch as their rows are
-            C_fin = (st["clab"].view(-1, 2).index_select(0, i_fin), st["canc"].view(-1, 6).index_select(0, i_fin))
         ln = self._len
+        # the finished identities' rows (with contacts their labels and anchors too), gathered before the launch
+        gathered = [self._gather(st, plan.want_fin, T)] if plan.want_fin else []
         # the finished identities' skeletons, gathered before the apply launch as their rows are (the apply resets a reused slot): a
         # finished record reports the device's state itself.  (The host's copy from the identity's last report, idn.len, holds the
         # same values, since the state changes only in a tick that reports it; tracklets() and close_session use that copy.)
-        S_fin = st["lens"].index_select(0, T(np.array([idn.slot for _, idn in fin], np.int64))) if ln is not None and fin else None
-        B = len(newp)
-        if B:
-            frame_of = np.array([p[0] for p in prob], np.int32)
+        if ln is not None and plan.finished:
+            lens_fin = st["lens"].index_select(0, T(np.array([idn.slot for _, idn in plan.finished], np.int64)))
+        if plan.new_rows:
+            frame_of = np.array([p.ring for p in plan.problems], np.int32)
             order, lo, hi = frame_buckets(frame_of)
-            mem_d, nv_d, _, _ = dev.body_observe(st["kps"], st["cnt"], st["Pm"], T(frame_of), T(np.array([p[1] for p in prob], np.int32)),
-                                                 T(np.array([p[2] for p in prob])), T(order), T(lo), T(hi),
-                                                 T(np.array([p[3] for p in prob], np.int32)), MAX_DIST, MIN_SCORE)
-            newp_d = T(np.array([p for _, p in newp]))
+            mem_d, nv_d, _, _ = dev.body_observe(st["kps"], st["cnt"], st["Pm"], T(frame_of),
+                                                 T(np.array([p.rig for p in plan.problems], np.int32)),
+                                                 T(np.array([p.joints for p in plan.problems])), T(order), T(lo), T(hi),
+                                                 T(np.array([p.slot for p in plan.problems], np.int32)), MAX_DIST, MIN_SCORE)
+            newp_d = T(np.array([p for _, p in plan.new_rows]))
         else:
             mem_d = torch.zeros((0, C), dtype=torch.int32, device=d)
             nv_d = torch.zeros((0,), dtype=torch.int32, device=d)
-            newp_d = torch.zeros((0, 68), dtype=torch.float64, device=d)
-        parts = []
-        if items:
-            items_d = T(np.array(items, np.int32))
+            newp_d = torch.zeros((0, N_PARAM), dtype=torch.float64, device=d)
+        if plan.items:
+            items_d = T(np.array(plan.items, np.int32))
             if ln is not None:      # the running skeletons into the tick's data rows, a new identity's state from its row
                 dev.live_lengths_apply(items_d, newp_d, st["lens"])
             args = (st["kps"], st["Pm"], items_d, newp_d, mem_d, st["rows"], st["members"], st["count"], W,
                     self.n_iter, self.w, LM_MU0, LM_FTOL, LM_XTOL, self.skeleton)
             if ct is None:
-                parts.append(dev.smooth_window(*args, **self._rob).reshape(-1))
+                rb.add("info", dev.smooth_window(*args, **self._rob))
             else:
-                parts += [p.reshape(-1) for p in dev.smooth_window(*args, **self._rob, contact=ct)]
+                info, cinfo = dev.smooth_window(*args, **self._rob, contact=ct)
+                rb.add("info", info)
+                rb.add("cinfo", cinfo)
             if ln is not None:      # the rows that moved behind the lag into the skeletons, the skeletons into the rows after them
-                parts.append(dev.live_lengths_update(st["kps"], st["Pm"], items_d, st["rows"], st["members"], st["count"], self.lag,
-                                                     ln["prior"], ln["commit"], st["lens"], self.skeleton).reshape(-1))
-        if S_fin is not None:
-            parts.append(S_fin.reshape(-1))
-        # the covariance of the emitted rows: ONE launch for all of them, none when nothing is emitted (or it is not asked for)
-        cov_of = [a for a, (key, idn, f) in enumerate(solved_of) if f - self.lag - idn.f0 >= 0] if self._cov else []
-        if cov_of:
-            citems = [[solved_of[a][1].slot, self._sessions[solved_of[a][0]].s, solved_of[a][2] - self.lag - solved_of[a][1].f0, k * W]
-                      for k, a in enumerate(cov_of)]
-            parts += [p.reshape(-1) for p in dev.smooth_window_cov(st["kps"], st["Pm"], T(np.array(citems, np.int32)), st["rows"],
-                                                                   st["members"], st["count"], W, self.w, COV_MU,
-                                                                   self._noise_px is None, self.skeleton, **self._rob,
-                                                                   **({} if ct is None else dict(contact=ct)))]
-        i_want = slot_idx(want) if want else None
-        Pg = [p for p in (P_fin, st["rows"].view(-1, 68).index_select(0, i_want) if want else None) if p is not None]
-        n_rows = len(want_fin) + len(want)
-        if n_rows:
-            Pall = torch.cat(Pg) if len(Pg) > 1 else Pg[0]
-            parts += [Pall.reshape(-1), dev.fk(Pall, self.skeleton).reshape(-1)]
-            if ct is not None:      # the same rows' labels and anchors join the read-back
-                Lg = ([C_fin[0]] if want_fin else []) + ([st["clab"].view(-1, 2).index_select(0, i_want)] if want else [])
-                Ag = ([C_fin[1]] if want_fin else []) + ([st["canc"].view(-1, 6).index_select(0, i_want)] if want else [])
-                parts += [torch.cat(Lg).to(torch.float64).reshape(-1), torch.cat(Ag).reshape(-1)]
-        parts += [mem_d.to(torch.float64).reshape(-1), nv_d.to(torch.float64).reshape(-1)]
-        host = torch.cat(parts).cpu().numpy()      # the tick's one synchronisation
-        t_launch = time.perf_counter()
-        # ---- host: the records ----
-        at = 0
+                rb.add("linfo", dev.live_lengths_update(st["kps"], st["Pm"], items_d, st["rows"], st["members"], st["count"], self.lag,
+                                                        ln["prior"], ln["commit"], st["lens"], self.skeleton))
+        if ln is not None and plan.finished:
+            rb.add("lens_fin", lens_fin)
+        if plan.cov_of:      # the covariance of the emitted rows: ONE launch for all of them
+            # include/mvmc.h, a covariance item: {slot, rig, emit_row, work_row}
+            citems = [[plan.stepped[a].idn.slot, self._sessions[plan.stepped[a].key].s, plan.stepped[a].emit_row, k * W]
+                      for k, a in enumerate(plan.cov_of)]
+            jcov, pvar, cinfo = dev.smooth_window_cov(st["kps"], st["Pm"], T(np.array(citems, np.int32)), st["rows"], st["members"],
+                                                      st["count"], W, self.w, COV_MU, self._noise_px is None, self.skeleton,
+                                                      **self._rob, **({} if ct is None else dict(contact=ct)))
+            rb.add("jcov", jcov)
+            rb.add("pvar", pvar)
+            rb.add("cov_info", cinfo)
+        if plan.want:
+            gathered.append(self._gather(st, plan.want, T))
+        if gathered:
+            self._read_rows(rb, gathered)
+        rb.add("members", mem_d)
+        rb.add("n_views", nv_d)
+        return rb
 
-        def take(n, shape):
-            nonlocal at
-            a = host[at:at + n].reshape(shape)
-            at += n
-            return a
-        inf_h = take(len(items) * 16, (len(items), 16))
-        cin_h = take(len(items) * 10, (len(items), 10)) if ct is not None and items else None
-        lin_h = take(len(items) * 17, (len(items), 17)) if ln is not None and items else None
-        if S_fin is not None:      # (A, b, l, l0, counters: include/mvmc.h)
-            for (key, idn), S in zip(fin, take(len(fin) * 103, (len(fin), 103))):
-                idn.len = (S[77:88].copy(), int(S[100]), int(S[102]))
-        nc = len(cov_of)
-        jc_h, pv_h, ci_h = take(nc * 108, (nc, 18, 6)), take(nc * 39, (nc, 39)), take(nc * 8, (nc, 8))
-        P_h = take(n_rows * 68, (n_rows, 68))
-        J_h = take(n_rows * 54, (n_rows, 18, 3))
-        if ct is not None:
-            L_h, A_h = take(n_rows * 2, (n_rows, 2)) != 0, take(n_rows * 6, (n_rows, 2, 3))
-        mem_h = take(B * C, (B, C)).astype(np.int64)
-        nv_h = take(B, (B,)).astype(np.int64)
-        sel_h = pose_slot(mem_h, self.P)
-        for b, (idn, _) in enumerate(newp):
+    def _collect(self, plan: _TickPlan, host: Dict[str, np.ndarray], out: Dict[object, TickOutput]) -> None:
+        """Stage 3, host: the read-back into the identities' records, the finished records and the sessions' TickOutputs."""
+        ct, ln = self._ct is not None, self._len is not None
+        for (key, idn), S in zip(plan.finished, host.get("lens_fin", ())):
+            idn.len = (S[LENS_L].copy(), int(S[LENS_CONTRIBUTED]), int(S[LENS_COMMITTED_ROW]))
+        nv_h = host["n_views"].astype(np.int64)
+        sel_h = pose_slot(host["members"].astype(np.int64), self.P)
+        for b, (idn, _) in enumerate(plan.new_rows):
             idn.views[-1], idn.sel[-1] = int(nv_h[b]), sel_h[b]
-        got = {}
-        for k, (idn, r) in enumerate(want_fin + want):
-            got[(id(idn), r)] = k
-        for key, idn in fin:
-            keep = idn.last_data()
-            for r in range(idn.n_final, keep):
+        P_h, J_h = host.get("rows"), host.get("joints")
+        L_h, A_h = (host["labels"] != 0, host["anchors"]) if ct and P_h is not None else (None, None)
+        got = {(id(idn), r): k for k, (idn, r) in enumerate(plan.want_fin + plan.want)}
+
+        def final(idn, lo, hi):      # rows lo .. hi - 1 keep the values read back for good
+            for r in range(lo, hi):
                 k = got[(id(idn), r)]
                 idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
-                if ct is not None:
+                if ct:
                     idn.contact[r] = (L_h[k].copy(), A_h[k].copy())
+        for key, idn in plan.finished:
+            keep = idn.last_data()
+            final(idn, idn.n_final, keep)
             idn.n_final = keep
             out[key].finished.append(self._record(idn, keep, 3))
         emit = []
-        for a, (key, idn, f) in enumerate(solved_of):
-            for r in range(was_final[a], idn.n_final):
-                k = got[(id(idn), r)]
-                idn.params[r], idn.joints[r] = P_h[k].copy(), J_h[k].copy()
-                if ct is not None:
-                    idn.contact[r] = (L_h[k].copy(), A_h[k].copy())
+        info, cinfo, linfo = host.get("info"), host.get("cinfo"), host.get("linfo")
+        for a, (key, idn, f, r, was_final) in enumerate(plan.stepped):
+            final(idn, was_final, idn.n_final)
             if idn.n >= 2:
-                n_t = int(inf_h[a, 4])
-                if int(inf_h[a, 7]) == 6:
+                inf = info[a]
+                if int(inf[INFO_STOP]) == STATUS_MALFORMED:
                     raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed item")
-                out[key].solved[idn.tid] = dict(cost=inf_h[a, :4].copy(), trials=[int(v) for v in inf_h[a, 8:8 + n_t]], stop=int(inf_h[a, 7]))
-                if ct is not None:
-                    out[key].solved[idn.tid]["contact_cost"] = cin_h[a, 8:10].copy()
-            if ln is not None:
-                if int(lin_h[a, 0]) == 6:
+                out[key].solved[idn.tid] = dict(cost=inf[INFO_COST].copy(),
+                                                trials=[int(v) for v in inf[INFO_TRACE:INFO_TRACE + int(inf[INFO_TRIALS])]],
+                                                stop=int(inf[INFO_STOP]))
+                if ct:
+                    out[key].solved[idn.tid]["contact_cost"] = cinfo[a, CINFO_COST].copy()
+            if ln:
+                lin = linfo[a]
+                if int(lin[LINFO_STATUS]) == STATUS_MALFORMED:
                     raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed skeleton item")
-                q = out[key].lengths[idn.tid] = dict(lengths=lin_h[a, 5:16].copy(), contributed=int(lin_h[a, 2]),
-                                                     committed=bool(lin_h[a, 3]), committed_row=int(lin_h[a, 4]), status=int(lin_h[a, 0]))
+                q = out[key].lengths[idn.tid] = dict(lengths=lin[LINFO_LENGTHS].copy(), contributed=int(lin[LINFO_CONTRIBUTED]),
+                                                     committed=bool(lin[LINFO_COMMITTED]), committed_row=int(lin[LINFO_COMMITTED_ROW]),
+                                                     status=int(lin[LINFO_STATUS]))
                 idn.len = (q["lengths"], q["contributed"], q["committed_row"])
-            r = f - self.lag - idn.f0
-            if r >= 0 and ct is not None:
-                out[key].contact[idn.tid] = dict(contact=cin_h[a, :2] != 0, anchor=cin_h[a, 2:8].reshape(2, 3).copy())
+            if r >= 0 and ct:
+                cin = cinfo[a]
+                out[key].contact[idn.tid] = dict(contact=cin[CINFO_LABELS] != 0, anchor=cin[CINFO_ANCHORS].reshape(2, 3).copy())
             if r >= 0:
                 emit.append((key, idn.tid, f - self.lag, got[(id(idn), r)], bool(idn.filled[r]), int(idn.views[r])))
-        for k, a in enumerate(cov_of):
-            key, idn, f = solved_of[a]
-            if int(ci_h[k, 0]) == 6:
+        for k, a in enumerate(plan.cov_of):
+            key, idn, f, r, _ = plan.stepped[a]
+            if int(host["cov_info"][k, COV_STATUS]) == STATUS_MALFORMED:
                 raise RuntimeError(f"session {key}, identity {idn.tid}: the device skipped a malformed covariance item")
-            c = out[key].cov[idn.tid] = cov_entry(jc_h[k], pv_h[k], ci_h[k], self._noise_px)
-            idn.cov[f - self.lag - idn.f0] = (c["joint_sigma"], c["param_sigma"], c["noise_px"])
+            c = out[key].cov[idn.tid] = cov_entry(host["jcov"][k], host["pvar"][k], host["cov_info"][k], self._noise_px)
+            idn.cov[r] = (c["joint_sigma"], c["param_sigma"], c["noise_px"])
         if emit:      # the tick's emitted poses in one pass
             ks = [e[3] for e in emit]
             for (key, tid, _, _, filled, views), pose in zip(emit, pose_tuples([e[2] for e in emit], P_h[ks], J_h[ks])):
                 out[key].emitted.append((tid,) + pose + (filled, views))
-        t_end = time.perf_counter()
-        self.timings["pack"] += t_pack - t_start
-        self.timings["launch"] += t_launch - t_pack
-        self.timings["records"] += t_end - t_launch
-        return out
 
     # -- the pool route ----------------------------------------------------------------------------------------------------------------
     def _pool_table(self, sid, fi):
@@ -705,7 +770,8 @@ class LiveSmoother:
             t.live_lengths, t.live_lengths_rows = idn.len[0].copy(), idn.len[1]
             t.live_lengths_committed_row = idn.len[2] if idn.len[2] < n else -1
         if self._cov:      # per row the values recorded when it was emitted; NaN on the rows that never were
-            t.smooth_joint_sigma, t.smooth_param_sigma, t.smooth_noise_px = np.full((n, 18), np.nan), np.full((n, 39), np.nan), np.full(n, np.nan)
+            t.smooth_joint_sigma, t.smooth_param_sigma = np.full((n, SMOOTH_JOINTS), np.nan), np.full((n, SMOOTH_K), np.nan)
+            t.smooth_noise_px = np.full(n, np.nan)
             for r, (js, ps, s) in idn.cov.items():
                 if r < n:
                     t.smooth_joint_sigma[r], t.smooth_param_sigma[r], t.smooth_noise_px[r] = js, ps, s

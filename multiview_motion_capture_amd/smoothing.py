@@ -48,7 +48,7 @@ from __future__ import annotations
 
 import math
 import time
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
@@ -150,12 +150,23 @@ def initial_trajectories(frames_list: Sequence[np.ndarray], params_list: Sequenc
     return out
 
 
-def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes):
+# ---- the argument checks of both smoothers (host only): ``who`` is the name in the message, "smooth_sequences" or "LiveSmoother" ----
+def _number(v) -> bool:
+    """A real number: int, float or a NumPy scalar of either; no bool, no string."""
+    return not isinstance(v, (str, bytes, bool)) and isinstance(v, (int, float, np.integer, np.floating))
+
+
+def check_prior_weights(who: str, root_vel, root_acc, ang_vel, ang_acc) -> np.ndarray:
     w = np.array([root_vel, root_acc, ang_vel, ang_acc], dtype=np.float64)
     if not np.all(np.isfinite(w)) or np.any(w < 0):
-        raise ValueError("smooth_sequences: the prior weights must be finite and >= 0")
+        raise ValueError(f"{who}: the prior weights must be finite and >= 0")
     if not (w[0] + w[1] > 0 and w[2] + w[3] > 0):
-        raise ValueError("smooth_sequences: root_vel + root_acc > 0 and ang_vel + ang_acc > 0 required")
+        raise ValueError(f"{who}: root_vel + root_acc > 0 and ang_vel + ang_acc > 0 required")
+    return w
+
+
+def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes):
+    w = check_prior_weights("smooth_sequences", root_vel, root_acc, ang_vel, ang_acc)
     if int(max_iter) != max_iter or not 0 <= int(max_iter) <= MAX_ITER_CAP:
         raise ValueError(f"smooth_sequences: 0 <= max_iter <= {MAX_ITER_CAP} required")
     if not int(max_work_bytes) > 0:
@@ -163,36 +174,42 @@ def _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_byte
     return w
 
 
-def _check_covariance(covariance, noise_px):
+def check_covariance(who: str, covariance, noise_px) -> Optional[float]:
+    """The covariance arguments of smooth_sequences and LiveSmoother -> noise_px as a float, or None."""
     if covariance is not None and not (isinstance(covariance, str) and covariance == "joints"):
-        raise ValueError(f"smooth_sequences: covariance must be None or \"joints\", got {covariance!r}")
+        raise ValueError(f"{who}: covariance must be None or \"joints\", got {covariance!r}")
     if noise_px is None:
         return None
     if covariance is None:
-        raise ValueError("smooth_sequences: noise_px without covariance=\"joints\" has nothing to scale")
-    if isinstance(noise_px, (str, bytes, bool)) or not isinstance(noise_px, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(noise_px) or not noise_px > 0:
-        raise ValueError(f"smooth_sequences: noise_px must be None or a finite number > 0, got {noise_px!r}")
+        raise ValueError(f"{who}: noise_px without covariance=\"joints\" has nothing to scale")
+    if not _number(noise_px) or not math.isfinite(noise_px) or not noise_px > 0:
+        raise ValueError(f"{who}: noise_px must be None or a finite number > 0, got {noise_px!r}")
     return float(noise_px)
 
 
 def check_loss(who: str, loss, loss_px) -> float:
-    """The robust-loss arguments of smooth_sequences and LiveSmoother (host only) -> loss_px as a float."""
+    """The robust-loss arguments of smooth_sequences and LiveSmoother -> loss_px as a float."""
     if not (loss is None or isinstance(loss, str)) or loss not in LOSSES:
         raise ValueError(f"{who}: loss must be None, \"huber\" or \"cauchy\", got {loss!r}")
-    if isinstance(loss_px, (str, bytes, bool)) or not isinstance(loss_px, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(loss_px) or not loss_px > 0:
+    if not _number(loss_px) or not math.isfinite(loss_px) or not loss_px > 0:
         raise ValueError(f"{who}: loss_px must be a finite number > 0, got {loss_px!r}")
     return float(loss_px)
 
 
-def _number(v) -> bool:
-    return not isinstance(v, (str, bytes, bool)) and isinstance(v, (int, float, np.integer, np.floating))
+class _Contacts(NamedTuple):
+    """The checked scalar foot-contact arguments."""
+    auto: bool
+    weight: float
+    speed: float
+    min_frames: int
+    rounds: int
+    ground: Optional[tuple]      # (normal (3,), offset)
+    height: float
 
 
-def _check_contact_args(contacts, contact_weight, contact_speed, contact_min_frames, contact_rounds, ground, contact_height):
-    """The scalar foot-contact arguments (host only) -> (auto, weight, speed, min_frames, rounds, ground or None, height)."""
-    who = "smooth_sequences"
+def _check_contact_args(contacts, contact_weight, contact_speed, contact_min_frames, contact_rounds, ground, contact_height,
+                        who: str = "smooth_sequences") -> _Contacts:
+    """The scalar foot-contact arguments of smooth_sequences and, with contacts="auto" and one round, of LiveSmoother."""
     auto = isinstance(contacts, str)
     if auto and contacts != "auto":
         raise ValueError(f"{who}: contacts must be None, \"auto\" or per sequence a list of label arrays, got {contacts!r}")
@@ -219,7 +236,8 @@ def _check_contact_args(contacts, contact_weight, contact_speed, contact_min_fra
         if normal.shape != (3,) or not np.all(np.isfinite(normal)) or not _number(off) or not math.isfinite(off):
             raise ValueError(f"{who}: ground must be (normal (3,), offset) of finite numbers")
         g = (normal, float(off))
-    return auto, float(contact_weight), float(contact_speed), int(contact_min_frames), int(contact_rounds), g, float(contact_height)
+    return _Contacts(auto, float(contact_weight), float(contact_speed), int(contact_min_frames), int(contact_rounds), g,
+                     float(contact_height))
 
 
 def _check_floor(floor, floor_weight, contacts, contact_weight, n_seq):
@@ -279,6 +297,114 @@ def _check_contact_labels(contacts, recs):
 def _check(sequences, tracklets_per_sequence):
     return check_records(sequences, tracklets_per_sequence, "smooth_sequences", increasing=True, finite=True,
                          cameras=(1, MAX_VIEWS, f"sequence {{s}}: {{C}} cameras, at most {MAX_VIEWS}"))
+
+
+class _Options(NamedTuple):
+    """smooth_sequences' keyword arguments after their checks (_options)."""
+    w: np.ndarray                        # the four prior weights
+    max_iter: int
+    fill_gaps: bool
+    max_work_bytes: int
+    loss: Optional[str]
+    loss_px: float
+    covariance: bool
+    noise_px: Optional[float]
+    contacts: Optional[_Contacts]
+    normals: Optional[list]              # floor=: per sequence None or the unit normal (3,)
+    floor_weight: Optional[float]
+
+    @property
+    def robust(self) -> dict:
+        """The loss arguments of the device calls; loss=None: the calls without the arguments."""
+        return dict(loss=self.loss, loss_px=self.loss_px) if self.loss is not None else {}
+
+    def row_bytes(self, C: int) -> int:
+        """Device bytes per trajectory row of a group with C cameras: what max_work_bytes caps."""
+        n = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
+        if self.covariance:
+            n += 8 * (_JOINTS * 6 + _K)
+        if self.contacts is not None:
+            n += 4 * 2 + 8 * 6 + 8 * _JOINTS * 3     # labels, anchors and the FK joints of the rounds
+        if self.loss is not None:
+            n += 8 * _OBS * C                        # the weights: (C, 16) per row
+        return n
+
+
+def _options(n_seq, root_vel, root_acc, ang_vel, ang_acc, max_iter, fill_gaps, max_work_bytes, covariance, noise_px, loss, loss_px,
+             contacts, contact_weight, contact_speed, contact_min_frames, contact_rounds, ground, contact_height, floor,
+             floor_weight) -> _Options:
+    """smooth_sequences' keyword arguments, checked (host only): the contact arguments are read only with contacts, the floor's only
+    with floor= or floor_weight=."""
+    w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
+    noise_px = check_covariance("smooth_sequences", covariance, noise_px)
+    loss_px = check_loss("smooth_sequences", loss, loss_px)
+    ct = None
+    if contacts is not None:
+        ct = _check_contact_args(contacts, contact_weight, contact_speed, contact_min_frames, contact_rounds, ground, contact_height)
+    normals = wf = None
+    if floor is not None or floor_weight is not None:
+        if floor is None:
+            raise ValueError("smooth_sequences: floor_weight belongs to floor")
+        normals, wf = _check_floor(floor, floor_weight, contacts, contact_weight, n_seq)
+    return _Options(w, int(max_iter), bool(fill_gaps), int(max_work_bytes), loss, loss_px, covariance is not None, noise_px, ct,
+                    normals, wf)
+
+
+class _Identity(NamedTuple):
+    """An identity with two frames or more, rows f0..f1 of its record (the missing ones included)."""
+    item: int                 # its index in the group's items
+    x0: np.ndarray            # (m, 68) the initial trajectory
+    filled: np.ndarray        # (m,) bool: the frame is missing from the record
+    members: np.ndarray       # (m, C) i32 the selected pose per camera, -1 none
+    n_views: np.ndarray       # (m,) i32
+    rig: int
+
+
+class _Cov(NamedTuple):
+    """mvmc_smooth_cov's unit-variance outputs of one identity."""
+    jcov: np.ndarray          # (m, 18, 6)
+    pvar: np.ndarray          # (m, 39)
+    info: np.ndarray          # (8,)
+
+
+class _Contact(NamedTuple):
+    mask: np.ndarray          # (m, 2) bool
+    anchors: np.ndarray       # (m, 2, 3)
+    cost: np.ndarray          # [E_contact at the first anchors, at the end]
+    round_trials: list
+
+
+class _Floor(NamedTuple):
+    normal: np.ndarray        # (3,) unit, NaN: the sequence has none
+    level: float
+
+
+class _Result(NamedTuple):
+    """What the solve returns for one _Identity; the optional parts are None unless the option is on."""
+    x: np.ndarray             # (m, 68)
+    joints: np.ndarray        # (m, 18, 3)
+    info: np.ndarray          # mvmc_smooth_step's info row (with contacts: of the whole call, _contact_result)
+    cov: Optional[_Cov] = None
+    weights: Optional[np.ndarray] = None
+    contact: Optional[_Contact] = None
+    floor: Optional[_Floor] = None
+
+
+class _Group(NamedTuple):
+    """What every partition of one camera group reads."""
+    items: list                          # (sequence, record) per identity
+    k17: object                          # the group's ingested keypoints and projections, on the device
+    Pm_d: object
+    normals: Optional[list]              # floor=: per rig None or the unit normal
+    normals_h: Optional[np.ndarray]      # (rigs, 3), NaN: none; None: no rig of the group has a floor
+    normals_d: object                    # the same on the device
+
+
+# mvmc_smooth_step's and mvmc_smooth_window's info row (include/mvmc.h): "E_data, E_prior at the start; E_data, E_prior at the end;
+# trials, accepted, mu, stop reason; per trial 1 / 0, -1 after the last"
+INFO_COST, INFO_TRIALS, INFO_STOP, INFO_TRACE = slice(0, 4), 4, 7, 8
+# mvmc_smooth_cov's and mvmc_smooth_window_cov's cinfo (include/mvmc.h): "{status, E_data at x, n_res = ..., edof, ...}"
+COV_STATUS, COV_E_DATA, COV_NRES, COV_EDOF = 0, 1, 2, 3
 
 
 def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence: Sequence[list], root_vel: float = ROOT_VEL,
@@ -361,207 +487,211 @@ def smooth_sequences(sequences: Sequence[SequenceInput], tracklets_per_sequence:
     the floor is not: unlabelled rows carry no term (a swing foot may pass under the plane); the live twin has no floor; there are
     still no toes; neither the world nor the BVH root is moved onto the floor."""
     t_start = time.perf_counter()
-    w = _check_weights(root_vel, root_acc, ang_vel, ang_acc, max_iter, max_work_bytes)
-    noise_px = _check_covariance(covariance, noise_px)
-    loss_px = check_loss("smooth_sequences", loss, loss_px)
-    rob = dict(loss=loss, loss_px=loss_px) if loss is not None else {}     # loss=None: the calls without the arguments
-    if contacts is not None:
-        auto, wc, c_speed, c_min, c_rounds, c_ground, c_height = _check_contact_args(contacts, contact_weight, contact_speed,
-                                                                                    contact_min_frames, contact_rounds, ground, contact_height)
-    if floor is not None or floor_weight is not None:
-        if floor is None:
-            raise ValueError("smooth_sequences: floor_weight belongs to floor")
-        normals, wf = _check_floor(floor, floor_weight, contacts, contact_weight, len(sequences))
+    opt = _options(len(sequences), root_vel, root_acc, ang_vel, ang_acc, max_iter, fill_gaps, max_work_bytes, covariance, noise_px, loss,
+                   loss_px, contacts, contact_weight, contact_speed, contact_min_frames, contact_rounds, ground, contact_height, floor,
+                   floor_weight)
     if no_sequences(sequences, tracklets_per_sequence, "smooth_sequences"):
         return []
     shapes, recs = _check(sequences, tracklets_per_sequence)
-    given = _check_contact_labels(contacts, recs) if contacts is not None and not auto else None
+    given = _check_contact_labels(contacts, recs) if opt.contacts is not None and not opt.contacts.auto else None
     import torch
 
     from . import device as dev
     d = torch.device(device)
     T = dev.uploader(d)
-    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records") + (("covariance",) if covariance else ())
-                        + (("weights",) if loss is not None else ()) + (("contacts",) if contacts is not None else ()))
+    lap, tm = stopwatch(timings, d, ("prepare", "select", "blocks", "solve", "records") + (("covariance",) if opt.covariance else ())
+                        + (("weights",) if opt.loss is not None else ()) + (("contacts",) if opt.contacts is not None else ()))
     tm["prepare"] = time.perf_counter() - t_start
     out: List[list] = [[None] * len(r) for r in recs]
-    per_row = 8 * (2 * _BLOCK + _WORK + 2 * 68) + 4 * 8
-    if covariance:
-        per_row += 8 * (_JOINTS * 6 + _K)
-    if contacts is not None:
-        per_row += 4 * 2 + 8 * 6 + 8 * _JOINTS * 3     # labels, anchors and the FK joints of the rounds
     for lay in plan_groups(shapes, 1):
         if not any(recs[i] for i in lay.seq_ids):
             continue
         t0 = time.perf_counter()
-        grp = stack_group(lay, sequences)
+        stacked = stack_group(lay, sequences)
         t0 = lap("prepare", t0)
-        sel = select_views(grp, recs, d, MAX_DIST, MIN_SCORE)      # on the record frames
-        items, rec_lo, C, k17, Pm_d = sel.items, sel.rec_lo, lay.n_views, sel.k17, sel.Pm_d
-        mem_h = sel.members.cpu().numpy()
-        nv_h = sel.n_views.cpu().numpy()
+        sel = select_views(stacked, recs, d, MAX_DIST, MIN_SCORE)      # on the record frames
+        mem_h, nv_h = sel.members.cpu().numpy(), sel.n_views.cpu().numpy()
         t0 = lap("select", t0)
-        # full trajectories of the identities with two frames or more
-        traj = []
-        multi = [a for a in range(len(items)) if sel.n_of[a] >= 2]
-        inits = initial_trajectories([recs[items[a][0]][items[a][1]][0] for a in multi], [recs[items[a][0]][items[a][1]][1] for a in multi])
-        for a, (x0, filled) in zip(multi, inits):
-            i, j = items[a]
-            f = recs[i][j][0]
-            m = x0.shape[0]
-            mem = -np.ones((m, C), np.int32)
-            nvf = np.zeros(m, np.int32)
-            rows = f - f[0]
-            mem[rows] = mem_h[rec_lo[a]:rec_lo[a + 1]]
-            nvf[rows] = nv_h[rec_lo[a]:rec_lo[a + 1]]
-            traj.append((a, x0, filled, mem, nvf, int(sel.rig_of[rec_lo[a]])))
-        t0 = lap("prepare", t0)
-        res, obs_w, con = {}, {}, {}
-        nrm_h = None          # the group's floor normals (one per rig, NaN: none), when it has one
-        if floor is not None and any(normals[i] is not None for i in lay.seq_ids):
-            nrm_h = np.array([np.full(3, np.nan) if normals[i] is None else normals[i] for i in lay.seq_ids])
-            nrm_d = T(nrm_h)
-        cap = max(1, int(max_work_bytes) // (per_row + (8 * _OBS * C if loss is not None else 0)))   # (the weights: (C, 16) per row)
-        at = 0
-        while at < len(traj):
-            b = at + 1
-            rows = traj[at][1].shape[0]
-            while b < len(traj) and rows + traj[b][1].shape[0] <= cap:
-                rows += traj[b][1].shape[0]
-                b += 1
-            part = traj[at:b]
-            at = b
-            t0 = time.perf_counter()
-            x_h = np.concatenate([p[1] for p in part])
-            N = x_h.shape[0]
-            m_of = np.array([p[1].shape[0] for p in part])
-            id_lo = np.concatenate([[0], np.cumsum(m_of)]).astype(np.int32)
-            id_of = np.repeat(np.arange(len(part), dtype=np.int32), m_of)
-            x = T(x_h)
-            xt = x.clone()
-            mem_d = T(np.concatenate([p[3] for p in part]))
-            rig_d = T(np.repeat(np.array([p[5] for p in part], np.int32), m_of))
-            ctl = torch.zeros((len(part), 4), dtype=torch.int32, device=d)
-            ctl[:, 1] = 1
-            info = torch.empty((len(part), 32), dtype=torch.float64, device=d)
-            blk = torch.empty((2, N, _BLOCK), dtype=torch.float64, device=d)
-            work = torch.empty((N, _WORK), dtype=torch.float64, device=d)
-            id_of_d, id_lo_d = T(id_of), T(id_lo)
-            t0 = lap("prepare", t0)
-            for phase in range(int(max_iter) + 1):
-                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x if phase == 0 else xt, id_of_d, ctl, blk, **rob)
-                t0 = lap("blocks", t0)
-                dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info, work)
-                t0 = lap("solve", t0)
-            ckw = {}
-            if contacts is not None:
-                cm_h = np.zeros((N, 2), np.int32)
-                if given is not None:
-                    for s, p in enumerate(part):
-                        g = given[items[p[0]][0]][items[p[0]][1]]
-                        if g is not None:
-                            cm_h[id_lo[s]:id_lo[s + 1]] = g
-                cmask = T(cm_h)
-                anch = torch.empty((N, 2, 3), dtype=torch.float64, device=d)
-                ckw = dict(cmask=cmask, anchors=anch, contact_weight=wc)
-                if nrm_h is not None:
-                    ckw.update(normals=nrm_d, floor_weight=wf)
-                    lev = torch.empty((len(part),), dtype=torch.float64, device=d)
-                infos, first = [info], None
-                t0 = lap("prepare", t0)
-                for rnd in range(c_rounds):
-                    jn_d = dev.fk(x)
-                    dev.smooth_contact_anchors(jn_d, id_lo_d, cmask, anch, ctl, auto and rnd == 0, c_speed, c_min, c_ground, c_height)
-                    if nrm_h is not None:
-                        dev.smooth_floor_anchors(jn_d, id_lo_d, rig_d, nrm_d, cmask, anch, lev)
-                    if rnd == 0:
-                        first = (jn_d.cpu().numpy(), cmask.cpu().numpy(), anch.cpu().numpy())
-                    info_r = torch.zeros((len(part), 32), dtype=torch.float64, device=d)   # (a stopped identity's row stays 0)
-                    infos.append(info_r)
-                    t0 = lap("contacts", t0)
-                    for phase in range(int(max_iter) + 1):
-                        dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x if phase == 0 else xt, id_of_d, ctl, blk, **rob, **ckw)
-                        t0 = lap("blocks", t0)
-                        dev.smooth_step(x, xt, blk, id_lo_d, w, LM_MU0, LM_FTOL, LM_XTOL, int(max_iter), phase, ctl, info_r, work)
-                        t0 = lap("solve", t0)
-            cov = None
-            if covariance:
-                # the blocks AT x (the loop's last blocks are the last trial's, which may have been rejected) into buffer 0, steered
-                # by a control word of its own: the solve's ctl and info stay as they are, and blk is not read again
-                ctl_x = torch.zeros((len(part), 4), dtype=torch.int32, device=d)
-                ctl_x[:, 1] = 1
-                jcov = torch.empty((N, _JOINTS, 6), dtype=torch.float64, device=d)
-                pvar = torch.empty((N, _K), dtype=torch.float64, device=d)
-                cinfo = torch.empty((len(part), _COV_INFO), dtype=torch.float64, device=d)
-                dev.smooth_blocks(k17, Pm_d, rig_d, mem_d, x, id_of_d, ctl_x, blk, **rob, **ckw)
-                dev.smooth_cov(x, blk[0], id_lo_d, w, COV_MU, k17, Pm_d, rig_d, mem_d, work, jcov, pvar, cinfo)
-                t0 = lap("covariance", t0)
-                cov = (jcov.cpu().numpy(), pvar.cpu().numpy(), cinfo.cpu().numpy())
-            if loss is not None:
-                wts = dev.smooth_obs_weights(k17, Pm_d, rig_d, mem_d, x, loss, loss_px)
-                t0 = lap("weights", t0)
-                wts_h = wts.cpu().numpy()
-            jn = dev.fk(x).cpu().numpy()
-            xs, inf = x.cpu().numpy(), info.cpu().numpy()
-            if contacts is not None:
-                t0 = lap("records", t0)
-                infs = [inf] + [i.cpu().numpy() for i in infos[1:]]
-                anc_h = anch.cpu().numpy()
-                lev_h = lev.cpu().numpy() if nrm_h is not None else None
-                inf = []
-                for s in range(len(part)):
-                    sl = slice(id_lo[s], id_lo[s + 1])
-                    n_s = nrm_h[part[s][5]] if nrm_h is not None and not np.isnan(nrm_h[part[s][5], 0]) else None
-                    inf_s, con[part[s][0]] = _contact_result([i[s] for i in infs], first[0][sl], first[1][sl], first[2][sl], jn[sl],
-                                                             anc_h[sl], wc, n_s, wf if n_s is not None else None)
-                    if floor is not None:
-                        con[part[s][0]] += (np.full(3, np.nan) if n_s is None else n_s.copy(), float(lev_h[s]) if n_s is not None else math.nan)
-                    inf.append(inf_s)
-                t0 = lap("contacts", t0)
-            for s, p in enumerate(part):
-                sl = slice(id_lo[s], id_lo[s + 1])
-                res[p[0]] = (xs[sl], jn[sl], inf[s]) + ((cov[0][sl], cov[1][sl], cov[2][s]) if cov else ())
-                if loss is not None:
-                    obs_w[p[0]] = wts_h[sl]
-            lap("records", t0)
+        idents = _identities(sel, mem_h, nv_h, lay.n_views, recs)
+        normals = nrm_h = nrm_d = None        # the group's floor normals: per rig, and as one array (NaN: none) when it has any
+        if opt.normals is not None:
+            normals = [opt.normals[i] for i in lay.seq_ids]
+            if any(n is not None for n in normals):
+                nrm_h = np.array([np.full(3, np.nan) if n is None else n for n in normals])
+                nrm_d = T(nrm_h)
+        grp = _Group(sel.items, sel.k17, sel.Pm_d, normals, nrm_h, nrm_d)
+        lap("prepare", t0)
+        res = {}
+        for part in _partitions(idents, max(1, opt.max_work_bytes // opt.row_bytes(lay.n_views))):
+            res.update(_solve_partition(part, grp, opt, given, lap, T))
         t0 = time.perf_counter()
-        _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, sel.Pg)
-        if covariance:
-            _covariance_fields(out, items, traj, res, fill_gaps, noise_px)
-        if loss is not None:
-            _weight_fields(out, items, traj, obs_w, fill_gaps, C)
-        if contacts is not None:
-            _contact_fields(out, items, traj, con, fill_gaps, c_rounds)
-            if floor is not None:
-                _floor_fields(out, items, con, [normals[i] for i in lay.seq_ids], sel.rig_of, rec_lo)
+        kept = _records(out, sel.items, recs, tracklets_per_sequence, idents, res, mem_h, nv_h, sel.rec_lo, opt.fill_gaps, sel.Pg)
+        _option_fields(kept, opt, lay.n_views, [None if normals is None else normals[int(sel.rig_of[lo])] for lo in sel.rec_lo[:-1]])
         lap("records", t0)
     if timings is not None:
         timings.update(tm)
     return out
 
 
-def _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, rec_lo, fill_gaps, Pg):
-    tr = {p[0]: p for p in traj}
+def _identities(sel, mem_h, nv_h, C: int, recs) -> List[_Identity]:
+    """The group's identities with two frames or more, each with its full trajectory f0..f1: the initial values, and the selection of
+    its record frames (mem_h, nv_h: select_views' members and view counts on the host) spread over the rows."""
+    multi = [a for a in range(len(sel.items)) if sel.n_of[a] >= 2]
+    rec_of = [recs[sel.items[a][0]][sel.items[a][1]] for a in multi]
+    out = []
+    for a, (frames, _, _), (x0, filled) in zip(multi, rec_of, initial_trajectories([r[0] for r in rec_of], [r[1] for r in rec_of])):
+        lo, hi = sel.rec_lo[a], sel.rec_lo[a + 1]
+        m = x0.shape[0]
+        mem = -np.ones((m, C), np.int32)
+        nvf = np.zeros(m, np.int32)
+        mem[frames - frames[0]] = mem_h[lo:hi]
+        nvf[frames - frames[0]] = nv_h[lo:hi]
+        out.append(_Identity(a, x0, filled, mem, nvf, int(sel.rig_of[lo])))
+    return out
+
+
+
+
+def _partitions(idents: List[_Identity], cap: int):
+    """The identities in order, cut greedily into launch sequences of at most ``cap`` rows (an identity larger than the cap alone)."""
+    at = 0
+    while at < len(idents):
+        b, rows = at + 1, idents[at].x0.shape[0]
+        while b < len(idents) and rows + idents[b].x0.shape[0] <= cap:
+            rows += idents[b].x0.shape[0]
+            b += 1
+        yield idents[at:b]
+        at = b
+
+
+def _solve_partition(part: List[_Identity], grp: _Group, opt: _Options, given, lap, T) -> dict:
+    """One launch sequence for the identities of ``part``: upload, round 0, the contact rounds, the optional covariance and weights
+    launches, the read-back -> {item index: _Result}."""
+    import torch
+
+    from . import device as dev
+    t0 = time.perf_counter()
+    x_h = np.concatenate([p.x0 for p in part])
+    N, n_ids = x_h.shape[0], len(part)
+    m_of = np.array([p.x0.shape[0] for p in part])
+    id_lo = np.concatenate([[0], np.cumsum(m_of)]).astype(np.int32)
+    rows_of = [slice(id_lo[s], id_lo[s + 1]) for s in range(n_ids)]
+    x = T(x_h)
+    d = x.device
+    xt = x.clone()
+    mem_d = T(np.concatenate([p.members for p in part]))
+    rig_d = T(np.repeat(np.array([p.rig for p in part], np.int32), m_of))
+    ctl = torch.zeros((n_ids, 4), dtype=torch.int32, device=d)
+    ctl[:, 1] = 1
+    info = torch.empty((n_ids, 32), dtype=torch.float64, device=d)
+    blk = torch.empty((2, N, _BLOCK), dtype=torch.float64, device=d)
+    work = torch.empty((N, _WORK), dtype=torch.float64, device=d)
+    id_of_d, id_lo_d = T(np.repeat(np.arange(n_ids, dtype=np.int32), m_of)), T(id_lo)
+    view = (grp.k17, grp.Pm_d, rig_d, mem_d)
+    t0 = lap("prepare", t0)
+
+    def lm_loop(t0, info, **term):
+        """max_iter + 1 launches of the blocks (at x, then at the trial) and of the step, under ctl; -> the clock."""
+        for phase in range(opt.max_iter + 1):
+            dev.smooth_blocks(*view, x if phase == 0 else xt, id_of_d, ctl, blk, **opt.robust, **term)
+            t0 = lap("blocks", t0)
+            dev.smooth_step(x, xt, blk, id_lo_d, opt.w, LM_MU0, LM_FTOL, LM_XTOL, opt.max_iter, phase, ctl, info, work)
+            t0 = lap("solve", t0)
+        return t0
+    t0 = lm_loop(t0, info)
+    ct, floor = opt.contacts, grp.normals_h is not None
+    term = {}
+    if ct is not None:
+        cm_h = np.zeros((N, 2), np.int32)
+        if given is not None:
+            for p, sl in zip(part, rows_of):
+                g = given[grp.items[p.item][0]][grp.items[p.item][1]]
+                if g is not None:
+                    cm_h[sl] = g
+        cmask = T(cm_h)
+        anch = torch.empty((N, 2, 3), dtype=torch.float64, device=d)
+        term = dict(cmask=cmask, anchors=anch, contact_weight=ct.weight)
+        if floor:
+            term.update(normals=grp.normals_d, floor_weight=opt.floor_weight)
+            lev = torch.empty((n_ids,), dtype=torch.float64, device=d)
+        infos, jn1 = [info], None      # (jn1, cm1, an1: the first round's joints, labels and anchors, on the host)
+        t0 = lap("prepare", t0)
+        for rnd in range(ct.rounds):
+            jn_d = dev.fk(x)
+            dev.smooth_contact_anchors(jn_d, id_lo_d, cmask, anch, ctl, ct.auto and rnd == 0, ct.speed, ct.min_frames, ct.ground, ct.height)
+            if floor:
+                dev.smooth_floor_anchors(jn_d, id_lo_d, rig_d, grp.normals_d, cmask, anch, lev)
+            if rnd == 0:
+                jn1, cm1, an1 = jn_d.cpu().numpy(), cmask.cpu().numpy(), anch.cpu().numpy()
+            infos.append(torch.zeros((n_ids, 32), dtype=torch.float64, device=d))   # (a stopped identity's row stays 0)
+            t0 = lap("contacts", t0)
+            t0 = lm_loop(t0, infos[-1], **term)
+    cov = wts_h = None
+    if opt.covariance:
+        # the blocks AT x (the loop's last blocks are the last trial's, which may have been rejected) into buffer 0, steered
+        # by a control word of its own: the solve's ctl and info stay as they are, and blk is not read again
+        ctl_x = torch.zeros((n_ids, 4), dtype=torch.int32, device=d)
+        ctl_x[:, 1] = 1
+        jcov = torch.empty((N, _JOINTS, 6), dtype=torch.float64, device=d)
+        pvar = torch.empty((N, _K), dtype=torch.float64, device=d)
+        cinfo = torch.empty((n_ids, _COV_INFO), dtype=torch.float64, device=d)
+        dev.smooth_blocks(*view, x, id_of_d, ctl_x, blk, **opt.robust, **term)
+        dev.smooth_cov(x, blk[0], id_lo_d, opt.w, COV_MU, *view, work, jcov, pvar, cinfo)
+        t0 = lap("covariance", t0)
+        cov = _Cov(jcov.cpu().numpy(), pvar.cpu().numpy(), cinfo.cpu().numpy())
+    if opt.loss is not None:
+        wts = dev.smooth_obs_weights(*view, x, opt.loss, opt.loss_px)
+        t0 = lap("weights", t0)
+        wts_h = wts.cpu().numpy()
+    jn = dev.fk(x).cpu().numpy()
+    xs, inf = x.cpu().numpy(), info.cpu().numpy()
+    inf_of, contact_of, floor_of = list(inf), [None] * n_ids, [None] * n_ids
+    if ct is not None:
+        t0 = lap("records", t0)
+        infs = [inf] + [i.cpu().numpy() for i in infos[1:]]
+        anc_h = anch.cpu().numpy()
+        lev_h = lev.cpu().numpy() if floor else None
+        for s, (p, sl) in enumerate(zip(part, rows_of)):
+            n_s = grp.normals_h[p.rig] if floor and not np.isnan(grp.normals_h[p.rig, 0]) else None
+            inf_of[s], contact_of[s] = _contact_result([i[s] for i in infs], jn1[sl], cm1[sl], an1[sl], jn[sl],
+                                                       anc_h[sl], ct.weight, n_s, opt.floor_weight if n_s is not None else None)
+            if opt.normals is not None:
+                floor_of[s] = _Floor(np.full(3, np.nan), math.nan) if n_s is None else _Floor(n_s.copy(), float(lev_h[s]))
+        t0 = lap("contacts", t0)
+    res = {p.item: _Result(xs[sl], jn[sl], inf_of[s], None if cov is None else _Cov(cov.jcov[sl], cov.pvar[sl], cov.info[s]),
+                           None if wts_h is None else wts_h[sl], contact_of[s], floor_of[s])
+           for s, (p, sl) in enumerate(zip(part, rows_of))}
+    lap("records", t0)
+    return res
+
+
+def _records(out, items, recs, tracklets_per_sequence, idents, res, mem_h, nv_h, rec_lo, fill_gaps, Pg) -> list:
+    """The group's new records into ``out``, with the attributes every call sets.  idents: the _Identity of every identity that was
+    solved, res: {item index: _Result} (either may be given as plain tuples in the fields' order); mem_h, nv_h, rec_lo: the selection
+    of the record frames.  The identity lookup and the kept rows are made here, once: -> per item (record, _Result or None for a
+    one-frame record, the kept rows of the trajectory or None) for _option_fields."""
+    by_item = {p.item: p for p in (_Identity(*p) for p in idents)}
+    kept = []
     for a, (i, j) in enumerate(items):
         src = tracklets_per_sequence[i][j]
         f, par, jnt = recs[i][j]
-        if a in tr:
-            _, _, filled, mem, nvf, _ = tr[a]
-            xs, jn, inf = res[a][:3]
-            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
-            poses = pose_tuples(f[0] + idx, xs[idx], jn[idx])
-            cost = np.array([inf[0], inf[1], inf[2], inf[3]])
-            n_t = int(inf[4])
-            trials = [int(v) for v in inf[8:8 + n_t]]
-            filled_k, views_k, mem_k = filled[idx], nvf[idx], mem[idx]
+        p = by_item.get(a)
+        if p is not None:
+            r = _Result(*res[a])
+            idx = np.arange(p.filled.size) if fill_gaps else np.flatnonzero(~p.filled)
+            poses = pose_tuples(f[0] + idx, r.x[idx], r.joints[idx])
+            cost = np.array(r.info[INFO_COST])
+            trials = [int(v) for v in r.info[INFO_TRACE:INFO_TRACE + int(r.info[INFO_TRIALS])]]
+            filled_k, views_k, mem_k = p.filled[idx], p.n_views[idx], p.members[idx]
         else:   # one frame: nothing to smooth (a copy of the input's pose)
+            r = idx = None
             poses = pose_tuples(f[:1], par[:1], jnt[:1])
             cost = np.zeros(4)
             trials = []
             filled_k = np.zeros(1, bool)
             views_k = nv_h[rec_lo[a]:rec_lo[a + 1]].astype(np.int32)
             mem_k = mem_h[rec_lo[a]:rec_lo[a + 1]]
-        t = new_record(src.track_id, poses, src)
+        t = out[i][j] = new_record(src.track_id, poses, src)
         if getattr(src, "bone_lens", None) is not None:
             t.bone_lens = np.array(src.bone_lens, np.float64).copy()
         t.smooth_filled = np.asarray(filled_k, bool)
@@ -569,35 +699,52 @@ def _records(out, items, recs, tracklets_per_sequence, traj, res, mem_h, nv_h, r
         t.smooth_select = pose_slot(mem_k, Pg)
         t.smooth_cost = cost
         t.smooth_trials = trials
-        out[i][j] = t
+        kept.append((t, r, idx))
+    return kept
 
 
-def _covariance_fields(out, items, traj, res, fill_gaps, noise_px):
-    """The smooth_* covariance attributes of the group's records (smooth_sequences' docstring), from the unit-variance device outputs."""
-    tr = {p[0]: p for p in traj}
-    for a, (i, j) in enumerate(items):
-        t = out[i][j]
-        if a in tr:
-            filled = tr[a][2]
-            jc6, pv, ci = res[a][3:6]
-            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
-            status, e_data, n_res, edof = int(ci[0]), float(ci[1]), ci[2], float(ci[3])
-            jc = jc6[idx][:, :, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, _JOINTS, 3, 3)
-            pv = pv[idx]
-        else:   # fewer than two frames: nothing was solved
-            status, e_data, n_res, edof = 2, 0.0, np.nan, np.nan
-            jc, pv = np.full((1, _JOINTS, 3, 3), np.nan), np.full((1, _K), np.nan)
-        if noise_px is not None:
-            s = noise_px
-        else:
-            s = math.sqrt(2.0 * e_data / (n_res - edof)) if status == 0 and n_res - edof > 0 else math.nan
-        t.smooth_noise_px = float(s)
-        t.smooth_joint_cov = (s * s) * jc
-        t.smooth_joint_sigma = np.sqrt((s * s) * (jc[:, :, 0, 0] + jc[:, :, 1, 1] + jc[:, :, 2, 2]))
-        t.smooth_param_sigma = np.sqrt((s * s) * pv)
-        t.smooth_edof = edof
-        t.smooth_nres = int(n_res) if status == 0 else 0
-        t.smooth_cov_status = status
+def _option_fields(kept: list, opt: _Options, C: int, normal_of: list) -> None:
+    """The attributes of the options that are on (smooth_sequences' docstring) on _records' records; normal_of: per item the floor
+    normal of its sequence or None."""
+    for (t, r, idx), n in zip(kept, normal_of):
+        if opt.covariance:
+            _covariance_fields(t, r, idx, opt.noise_px)
+        if opt.loss is not None:      # a one-frame record has nothing solved: NaN
+            t.smooth_obs_weight = r.weights[idx].copy() if r is not None else np.full((1, C, _OBS), np.nan)
+        if opt.contacts is not None:
+            _contact_fields(t, r, idx, opt.contacts.rounds)
+            if opt.normals is not None:
+                t.smooth_floor_normal, t.smooth_floor_level = r.floor if r is not None else \
+                    (np.full(3, np.nan) if n is None else n.copy(), math.nan)
+
+
+def scale_covariance(jc6, pv, status: int, e_data: float, n_res, edof: float, noise_px: Optional[float]):
+    """The covariance launches' unit-variance outputs jc6 (..., 18, 6) and pv (..., 39) -> (noise, joint_cov (..., 18, 3, 3) m^2,
+    joint_sigma (..., 18) m, param_sigma (..., 39)): scaled by noise^2 with noise = noise_px if given, else the estimate
+    sqrt(2 E_data / (n_res - edof)), NaN when the launch did not solve (status != 0) or that is not positive; the six stored entries
+    of every symmetric 3 x 3 block expanded."""
+    if noise_px is not None:
+        s = noise_px
+    else:
+        s = math.sqrt(2.0 * e_data / (n_res - edof)) if status == 0 and n_res - edof > 0 else math.nan
+    jc = jc6[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(jc6.shape[:-1] + (3, 3))
+    return float(s), (s * s) * jc, np.sqrt((s * s) * (jc[..., 0, 0] + jc[..., 1, 1] + jc[..., 2, 2])), np.sqrt((s * s) * pv)
+
+
+def _covariance_fields(t, r: Optional[_Result], idx, noise_px) -> None:
+    """The smooth_* covariance attributes of one record (smooth_sequences' docstring), from the unit-variance device outputs."""
+    if r is not None:
+        ci = r.cov.info
+        status, e_data, n_res, edof = int(ci[COV_STATUS]), float(ci[COV_E_DATA]), ci[COV_NRES], float(ci[COV_EDOF])
+        jc6, pv = r.cov.jcov[idx], r.cov.pvar[idx]
+    else:   # fewer than two frames: nothing was solved
+        status, e_data, n_res, edof = 2, 0.0, np.nan, np.nan
+        jc6, pv = np.full((1, _JOINTS, 6), np.nan), np.full((1, _K), np.nan)
+    t.smooth_noise_px, t.smooth_joint_cov, t.smooth_joint_sigma, t.smooth_param_sigma = scale_covariance(jc6, pv, status, e_data, n_res,
+                                                                                                          edof, noise_px)
+    t.smooth_edof = edof
+    t.smooth_nres = int(n_res) if status == 0 else 0
+    t.smooth_cov_status = status
 
 
 def _contact_energy(joints, mask, anchors, wc, normal=None, wf=None) -> float:
@@ -626,47 +773,17 @@ def _contact_result(infs, joints1, mask, anchors1, joints, anchors, wc, normal=N
         cost[:] = _contact_energy(joints1, mask, anchors1, wc, normal, wf), _contact_energy(joints, mask, anchors, wc, normal, wf)
         end = np.array([infs[-1][2] - cost[1], infs[-1][3]])
     inf = np.concatenate([infs[0][0:2], end, [float(sum(n_r)), 0.0, 0.0, 0.0], trials])
-    return inf, (mask != 0, anchors, cost, n_r)
+    return inf, _Contact(mask != 0, anchors, cost, n_r)
 
 
-def _contact_fields(out, items, traj, con, fill_gaps, rounds):
-    """The smooth_contact* attributes and smooth_round_trials of the group's records (smooth_sequences' docstring)."""
-    tr = {p[0]: p for p in traj}
-    for a, (i, j) in enumerate(items):
-        t = out[i][j]
-        if a in tr:
-            filled = tr[a][2]
-            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
-            mask, anchors, cost, n_r = con[a][:4]
-            t.smooth_contact, t.smooth_contact_anchor = mask[idx].copy(), anchors[idx].copy()
-            t.smooth_contact_cost, t.smooth_round_trials = cost, list(n_r)
-        else:   # one frame: nothing was solved
-            t.smooth_contact, t.smooth_contact_anchor = np.zeros((1, 2), bool), np.full((1, 2, 3), np.nan)
-            t.smooth_contact_cost, t.smooth_round_trials = np.zeros(2), [0] * (1 + rounds)
-
-
-def _floor_fields(out, items, con, normals, rig_of, rec_lo):
-    """smooth_floor_normal (3,) and smooth_floor_level of the group's records: the sequence's unit normal (NaN: it has none) and the
-    identity's level along it, NaN without a contact (and for a one-frame record)."""
-    for a, (i, j) in enumerate(items):
-        t = out[i][j]
-        if a in con:
-            t.smooth_floor_normal, t.smooth_floor_level = con[a][4], con[a][5]
-        else:
-            n = normals[int(rig_of[rec_lo[a]])]
-            t.smooth_floor_normal, t.smooth_floor_level = (np.full(3, np.nan) if n is None else n.copy()), math.nan
-
-
-def _weight_fields(out, items, traj, obs_w, fill_gaps, C):
-    """smooth_obs_weight (n, C, 16) of the group's records, rows as poses; a one-frame record has nothing solved: NaN."""
-    tr = {p[0]: p for p in traj}
-    for a, (i, j) in enumerate(items):
-        if a in tr:
-            filled = tr[a][2]
-            idx = np.arange(filled.size) if fill_gaps else np.flatnonzero(~filled)
-            out[i][j].smooth_obs_weight = obs_w[a][idx].copy()
-        else:
-            out[i][j].smooth_obs_weight = np.full((1, C, _OBS), np.nan)
+def _contact_fields(t, r: Optional[_Result], idx, rounds: int) -> None:
+    """The smooth_contact* attributes and smooth_round_trials of one record (smooth_sequences' docstring)."""
+    if r is not None:
+        t.smooth_contact, t.smooth_contact_anchor = r.contact.mask[idx].copy(), r.contact.anchors[idx].copy()
+        t.smooth_contact_cost, t.smooth_round_trials = r.contact.cost, list(r.contact.round_trials)
+    else:   # one frame: nothing was solved
+        t.smooth_contact, t.smooth_contact_anchor = np.zeros((1, 2), bool), np.full((1, 2, 3), np.nan)
+        t.smooth_contact_cost, t.smooth_round_trials = np.zeros(2), [0] * (1 + rounds)
 
 
 def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calibs: list, root_vel: float = ROOT_VEL,
@@ -679,26 +796,16 @@ def smooth_tracklets(tracklets: list, kps: np.ndarray, counts: np.ndarray, calib
     """smooth_sequences for one sequence: records of kps (F,C,P,25|17,3), counts (F,C) and one Calib per camera -> new records.
     contacts: None, "auto", or a list aligned with ``tracklets`` (None or a bool array (m, 2) per record); floor: None or the
     sequence's floor normal (3,)."""
-    if floor is not None or floor_weight is not None:
-        if floor is not None and isinstance(floor, (list, tuple)) and not (len(floor) == 3 and all(_number(v) for v in floor)):
-            raise ValueError(f"smooth_tracklets: floor must be None or ONE normal (3,), got {floor!r}")
-        return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel,
-                                ang_acc=ang_acc, max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device,
-                                timings=timings, covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px,
-                                contacts=contacts if contacts is None or isinstance(contacts, str) else [contacts],
-                                contact_weight=contact_weight, contact_speed=contact_speed, contact_min_frames=contact_min_frames,
-                                contact_rounds=contact_rounds, ground=ground, contact_height=contact_height, floor=floor,
-                                floor_weight=floor_weight)[0]
-    if contacts is not None:
-        return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel,
-                                ang_acc=ang_acc, max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device,
-                                timings=timings, covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px,
-                                contacts=contacts if isinstance(contacts, str) else [contacts], contact_weight=contact_weight,
-                                contact_speed=contact_speed, contact_min_frames=contact_min_frames, contact_rounds=contact_rounds,
-                                ground=ground, contact_height=contact_height)[0]
+    if floor is not None and isinstance(floor, (list, tuple)) and not (len(floor) == 3 and all(_number(v) for v in floor)):
+        raise ValueError(f"smooth_tracklets: floor must be None or ONE normal (3,), got {floor!r}")
+    # (smooth_sequences reads the contact arguments only with contacts, the floor's only with floor= or floor_weight=)
     return smooth_sequences([(kps, counts, calibs)], [tracklets], root_vel=root_vel, root_acc=root_acc, ang_vel=ang_vel, ang_acc=ang_acc,
                             max_iter=max_iter, fill_gaps=fill_gaps, max_work_bytes=max_work_bytes, device=device, timings=timings,
-                            covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px)[0]
+                            covariance=covariance, noise_px=noise_px, loss=loss, loss_px=loss_px,
+                            contacts=contacts if contacts is None or isinstance(contacts, str) else [contacts],
+                            contact_weight=contact_weight, contact_speed=contact_speed, contact_min_frames=contact_min_frames,
+                            contact_rounds=contact_rounds, ground=ground, contact_height=contact_height, floor=floor,
+                            floor_weight=floor_weight)[0]
 
 
 def estimate_floor(tracklets_per_sequence: Sequence[list], min_spread: float = 0.05) -> List[dict]:
