@@ -821,6 +821,44 @@ int mvmc_relink(const double* rec, const int32_t* frames, const int32_t* seq, in
                 double near_dist, double speed, int32_t* succ, int32_t* head, int32_t* pos, double* link_cost, int32_t* status,
                 double* work, long long work_words, mvmcStream_t stream);
 
+/* ---- re-identification of a person after a long hole, by bone lengths (multiview_motion_capture_amd/relinking.py:
+ * reidentify_sequences; restated in tests/reid_np.py).  No counterpart in the reference.  Two launches.
+ * SIGNATURE of a record from the joints of ALL its poses, one 256-lane workgroup per record.  Per pose and bone j = 1 .. 17: b_j =
+ * sqrt(dx dx + dy dy + dz dz) of joint j minus its parent (no contraction).  Ten sides: the values 0 - 6 and 8 - 10 of the skeleton's
+ * side map (7 is the root and has no bone); sides 0 - 6 have a left and a right bone and the value (b_lo + b_hi) / 2 in joint order,
+ * sides 8, 9, 10 one bone; a pose gives a side a value only when all its bones are finite.  Per side with m values: med = the lower
+ * median (rank (m - 1) / 2 in ascending order), mad = the lower median of |x - med|, se = 1.4826 mad 1.2533 / sqrt(m) evaluated in
+ * that order; a side with m < min_poses is undefined (med = se = NaN).  Both medians are exact selections (counting passes over the
+ * bit patterns, integer counts only): the result does not depend on the order of the values.
+ *   joints (n_poses,18,3) f64; rec (N,2) i32 per record: its first pose row, its poses (1 .. MVMC_REID_MAX_POSES)
+ *   sig (N,20) f64 out: med (10), se (10); cnt (N,10) i32 out: the values per side; ends (N,6) f64 out: the joint centroid (the mean
+ *   of the 18 joints, summed in joint order) of the first pose, of the last pose
+ *   status (N) i32 out: 0 ok, 2 the row of rec does not fit n_poses / the capacity / work (nothing else is read or written for it)
+ *   work: a record of more than MVMC_REID_LDS_POSES poses keeps its values in words 10 first .. 10 (first + poses) of it, so
+ *     work_words >= 10 n_poses serves every record; records that use it must not share pose rows; may be NULL when none needs it.
+ * LINKS, one 256-lane workgroup per sequence, nodes in (first frame, track id) order as in mvmc_relink.  z(A, B) = sqrt(mean over the
+ * sides defined in both of (l_A - l_B)^2 / (se_A^2 + se_B^2 + 2 floor^2)), summed in side order; undefined with fewer than 5 common
+ * sides.  A -> B is a candidate when A != B, gap = first(B) - last(A) >= 1 (and <= max_gap when max_gap > 0; 0 = no bound), z is
+ * defined and <= max_z, and |first centroid of B - last centroid of A| <= reach + speed gap (a non-finite distance allows nothing).
+ * Veto: records overlap when first(Q) <= last(R) and first(R) <= last(Q); the candidate is refused when another record Q overlaps B
+ * but not A with z(A, B) > ratio z(A, Q), or overlaps A but not B with z(A, B) > ratio z(Q, B) (an undefined z vetoes nothing; a Q
+ * that overlaps both ends vetoes nothing).  The links taken are an optimal assignment on the n x 2n matrix (z where allowed, max_z in
+ * a row's dummy column), by mvmc_relink's own device code, as are the chains.
+ *   sig, ends: the first launch's outputs; frames (N,2) i32: first frame, last frame; seq (S,4) i32 and succ, head, pos, link_cost (the
+ *   z of the link taken), status: as for mvmc_relink
+ *   work: a sequence of more than 64 records keeps its z and cost matrices there: mvmc_reid_work_words(n) 8-byte words each (-1: n
+ *     outside the capacity MVMC_RELINK_MAX_RECORDS).
+ * min_poses >= 1; max_z, floor, reach, speed finite, >= 0 and below 1e6; 0 <= ratio <= 1; max_gap >= 0; else MVMC_ERR_ARG.  Argument
+ * errors return before any HIP call; nothing is allocated, freed or synchronised inside. ---- */
+#define MVMC_REID_MAX_POSES 65536
+#define MVMC_REID_LDS_POSES 512
+long long mvmc_reid_work_words(int n_records);
+int mvmc_reid_signature(const double* joints, const int32_t* rec, int n_poses, int n_records, int min_poses, double* sig, int32_t* cnt,
+                        double* ends, int32_t* status, double* work, long long work_words, mvmcStream_t stream);
+int mvmc_reid_link(const double* sig, const double* ends, const int32_t* frames, const int32_t* seq, int n_records, int n_seqs,
+                   int max_gap, double max_z, double ratio, double floor, double reach, double speed, int32_t* succ, int32_t* head,
+                   int32_t* pos, double* link_cost, int32_t* status, double* work, long long work_words, mvmcStream_t stream);
+
 /* ---- refinement of every sequence's camera rig from its tracked people (multiview_motion_capture_amd/rig_refine.py; restated in
  * tests/rig_refine_np.py).  No counterpart in the reference.  A bundle adjustment: the unknowns are the points (one per record frame
  * and keypoint) and, per free camera, a rotation increment (R <- exp([w]x) R) and a translation increment; the residual is the plain

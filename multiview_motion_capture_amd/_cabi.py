@@ -32,6 +32,7 @@ LIVE_LEN_STATE_DOUBLES, LIVE_LEN_INFO_DOUBLES = 103, 17                         
 SMOOTH_LOSS_NONE, SMOOTH_LOSS_HUBER, SMOOTH_LOSS_CAUCHY = 0, 1, 2                                     # MVMC_SMOOTH_LOSS_*
 SMOOTH_FOOT_L, SMOOTH_FOOT_R = 3, 6                                                                   # MVMC_SMOOTH_FOOT_*: the ankles
 RELINK_MAX_RECORDS, RELINK_REC_DOUBLES = 512, 120
+REID_MAX_POSES, REID_LDS_POSES = 65536, 512                                                            # MVMC_REID_*
 RIG_TILE, RIG_MAX_CAMS, RIG_MAX_ITER, RIG_CAM_DOUBLES, RIG_INFO_DOUBLES = 64, 8, 24, 21, 64
 LENS_DOUBLES, LENS_PINHOLE, LENS_BROWN, LENS_FISHEYE, LENS_MAX_ITER, LENS_FISHEYE_MAX_THETA = 16, 0, 1, 2, 12, 1.5
 RIGINIT_NORM_DOUBLES, RIGINIT_POSE_DOUBLES, RIGINIT_MAX_ROUNDS, RIGINIT_MAX_SAMPLE = 8, 32, 8, 32
@@ -46,6 +47,7 @@ SYMBOLS = (
     "mvmc_debug_trstep", "mvmc_ik_solve_stages", "mvmc_chain_run", "mvmc_svt_associate", "mvmc_debug_ik_solve_fd", "mvmc_debug_ik_model_step", "mvmc_ingest_dlt", "mvmc_ingest_dlt_f32", "mvmc_pack_message_words", "mvmc_pack_work_words", "mvmc_stitch_work_words", "mvmc_pack_tracks", "mvmc_stitch_chains",
     "mvmc_chain_run_rigs", "mvmc_chain_run_sessions", "mvmc_body_observe", "mvmc_body_lengths", "mvmc_ik_solve_stages_rigs",
     "mvmc_smooth_blocks", "mvmc_smooth_step", "mvmc_smooth_cov", "mvmc_smooth_window_work_doubles", "mvmc_smooth_window", "mvmc_relink_work_words", "mvmc_relink",
+    "mvmc_reid_work_words", "mvmc_reid_signature", "mvmc_reid_link",
     "mvmc_smooth_blocks_robust", "mvmc_smooth_obs_weights", "mvmc_smooth_window_robust",
     "mvmc_smooth_blocks_contact", "mvmc_smooth_contact_anchors",
     "mvmc_smooth_blocks_floor", "mvmc_smooth_floor_anchors",
@@ -191,6 +193,9 @@ def load():
         "mvmc_live_lengths_update": [SK, vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, i32, i32, f64, i32, vp, vp, vp],
         "mvmc_relink_work_words": [i32],
         "mvmc_relink": [vp, vp, vp, i32, i32, i32, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
+        "mvmc_reid_work_words": [i32],
+        "mvmc_reid_signature": [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_longlong, vp],
+        "mvmc_reid_link": [vp, vp, vp, vp, i32, i32, i32, f64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, C.c_longlong, vp],
         "mvmc_rig_part_doubles": [i32],
         "mvmc_rig_red_doubles": [i32],
         "mvmc_rig_start": [vp, vp, vp, i32, i32, i32, f64, vp, vp, vp],
@@ -214,6 +219,7 @@ def load():
     restypes = {"mvmc_status_string": C.c_char_p, "mvmc_pack_message_words": C.c_longlong, "mvmc_pack_work_words": C.c_longlong,
                 "mvmc_stitch_work_words": C.c_longlong, "mvmc_smooth_window_work_doubles": C.c_longlong,
                 "mvmc_smooth_window_cov_work_doubles": C.c_longlong, "mvmc_relink_work_words": C.c_longlong,
+                "mvmc_reid_work_words": C.c_longlong,
                 "mvmc_rig_part_doubles": C.c_longlong, "mvmc_rig_red_doubles": C.c_longlong,
                 "mvmc_rig_part_doubles_intr": C.c_longlong, "mvmc_rig_red_doubles_intr": C.c_longlong}
     # A build of another revision loaded through MVMC_LIB_PATH for a same-box A/B comparison (tools/lib_diff.py, tools/*_ab.sh) may

@@ -486,14 +486,16 @@ def run_main(video_dir: Optional[Path], pose_dir: Path, out_dir: Path, n_test: i
     return all_tlets
 
 
-def run_main_batched(pose_dirs: List[Path], out_dirs: List[Path], n_test: int = 300, chain_len: int = 16, relink: bool = False):
+def run_main_batched(pose_dirs: List[Path], out_dirs: List[Path], n_test: int = 300, chain_len: int = 16, relink: bool = False,
+                     reidentify: bool = False):
     """run_main for several sequences in one call, through the batched path (sequences.track_sequences): for every pose_dir the same
     frames as run_main (the per-frame pickles frm_idx = 1 .. n_test), filter_bad_pose(0.01, 4, 5), then ONE chain-kernel launch per
     camera count for all sequences, each with its own calibration (the first selected frame's).  Each sequence's tracklets -- longest
     first -- go to its out_dir/tracklets.pkl as {"tracklets": [...]}; returns the lists.  These are the batched semantics (chains of
     chain_len frames that cold-start, identities carried across chain boundaries by the stitch), not frame-by-frame update_4d:
     INTEGRATION.md, section C.  relink=True joins the records of one person per sequence afterwards (relinking.relink_sequences,
-    INTEGRATION.md section C.6); off by default."""
+    INTEGRATION.md section C.6); reidentify=True then joins them across long holes by their bone lengths
+    (relinking.reidentify_sequences); both off by default."""
     from .sequences import track_sequences
     if len(pose_dirs) != len(out_dirs):
         raise ValueError("run_main_batched: one out_dir per pose_dir")
@@ -520,7 +522,7 @@ def run_main_batched(pose_dirs: List[Path], out_dirs: List[Path], n_test: int = 
                     kps[f, c, k, :, :2] = pose.keypoints
                     kps[f, c, k, :, 2] = np.asarray(pose.keypoints_score).ravel()
         seqs.append((kps, cnt, [frm.calib for frm in frames[0]]))
-    results = track_sequences(seqs, chain_len=chain_len, frame_idx0=1, relink=relink)
+    results = track_sequences(seqs, chain_len=chain_len, frame_idx0=1, relink=relink, reidentify=reidentify)
     for out_dir, tlets in zip(out_dirs, results):
         os.makedirs(out_dir, exist_ok=True)
         with open(f'{out_dir}/tracklets.pkl', 'wb') as fh:

@@ -360,7 +360,7 @@ def tables_to_tracklets(meta: np.ndarray, n_tracks: np.ndarray, params: np.ndarr
 
 def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_max: Optional[int] = None,
                     max_dist: float = parallel.MAX_DIST, frame_idx0: int = 0, device="cuda:0", timings: Optional[dict] = None,
-                    tables: Optional[list] = None, relink: bool = False):
+                    tables: Optional[list] = None, relink: bool = False, reidentify: bool = False):
     """Track every sequence -- (kps25 (F_s,C,P_s,25,3), counts (F_s,C), calibs: one Calib per camera), what
     motion_capture.load_openpose_sequence returns -- and return, per sequence, its MvTracklet records (longest first).
 
@@ -372,7 +372,9 @@ def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_m
     tables: a list that receives, per sequence, its stitched tables as host arrays (padded frames included): dict(params, joints,
     meta, n_tracks, gid (its chains, parallel.ID_CAP), match, n_frames).
     relink: join the records of one person per sequence afterwards (relinking.relink_sequences with its defaults, max_dist as here;
-    the tables stay the tracker's own).  Off by default: the records are then the stitch's, as before."""
+    the tables stay the tracker's own).  Off by default: the records are then the stitch's, as before.
+    reidentify: afterwards (after relink when both are asked for) join the records of one person across long holes by their bone
+    lengths (relinking.reidentify_sequences with its defaults).  Off by default."""
     import time
 
     import torch
@@ -428,6 +430,11 @@ def track_sequences(sequences: Sequence[SequenceInput], chain_len: int = 16, t_m
         t0 = time.perf_counter()
         result = relink_sequences(result, max_dist=max_dist, device=device)
         tm["relink"] = time.perf_counter() - t0
+    if reidentify:
+        from .relinking import reidentify_sequences
+        t0 = time.perf_counter()
+        result = reidentify_sequences(result, device=device)
+        tm["reidentify"] = time.perf_counter() - t0
     if timings is not None:
         timings.update(tm)
     if tables is not None:
