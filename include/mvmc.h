@@ -116,7 +116,9 @@ int mvmc_closure_labels(const uint8_t* x_bin, const int32_t* n_nodes, int n_fram
  *   alpha, lambda, mu, tol, max_iter, dual_stochastic: the reference's keyword arguments (0.1, 50, 64, 5e-4, 20, 1)
  *   work         (F,3,N,N) f64 device workspace (Y and the two projection states)
  *   x_bin        (F,N,N) u8 out: (X + X^T) / 2 > 0.5;  x_out (F,N,N) f64 out or NULL: X itself
- *   iters        (F) i32 out: SVD-equivalent decompositions run (info['iter'] + 1 when the tolerance was met, else max_iter)
+ *   iters        (F) i32 out: SVD-equivalent decompositions run (info['iter'] + 1 when the tolerance was met, else max_iter);
+ *                -1 for a refused row: a negative count, a count above the launch's group width (8 when g_max <= 8, else 16),
+ *                or counts that sum beyond N.  Such a row gets zero x_bin / x_out and leaves its work slice untouched
  * Arithmetic is float64 for either input type.  Follow with mvmc_closure_labels for match_mat / cluster labels. */
 int mvmc_svt_associate(const void* S, int s_dtype, const int32_t* group_counts, int n_frames, int n_groups, int n_max,
                        int g_max, double alpha, double lambda, double mu, double tol, int max_iter, int dual_stochastic,

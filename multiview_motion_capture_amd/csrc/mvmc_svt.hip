@@ -73,12 +73,31 @@ svt_kernel(const TS* __restrict__ Sg, const int32_t* __restrict__ gcounts, int G
     __shared__ double red[4];
     const int tid = threadIdx.x, f = blockIdx.x;
     if (tid == 0) {
-        int acc = 0;
+        // a row this launch cannot hold is refused: a negative count, a count beyond the y[GM] registers, more nodes than ldw
+        // (LDS and the workspace slice are sized from ldw)
+        int acc = 0, bad = 0;
         dimg[0] = 0;
-        for (int g = 0; g < G; ++g) { acc += gcounts[(size_t)f * G + g]; dimg[g + 1] = acc; }
+        for (int g = 0; g < G; ++g) {
+            const int c = gcounts[(size_t)f * G + g];
+            if (c < 0 || c > GM) bad = 1;
+            else acc += c;
+            dimg[g + 1] = acc;
+        }
+        s_flag = bad || acc > ldw;
     }
     __syncthreads();
     const int n = dimg[G];
+    if (n == 0 || s_flag) {
+        // an empty graph: no iteration and no pair (its outputs are zero, as outside every graph's n x n block).  A refused row
+        // writes the same and nothing else (iters = -1; the workspace is not touched)
+        const int refused = s_flag;
+        for (int e = tid; e < ldw * ldw; e += SVT_NT) {
+            x_bin[(size_t)f * ldw * ldw + e] = 0;
+            if (x_out) x_out[(size_t)f * ldw * ldw + e] = 0.0;
+        }
+        if (tid == 0) iters_out[f] = refused ? -1 : 0;
+        return;   // (uniform)
+    }
     const int m = (n + 1) & ~1;   // even size for the Jacobi pairing (the pad row / column is zero: an eigenvalue 0, untouched)
     double* X = lds;
     double* A = lds + m * m;
@@ -101,14 +120,6 @@ svt_kernel(const TS* __restrict__ Sg, const int32_t* __restrict__ gcounts, int G
         if (in) Yg[i * ldw + j] = 0.0;
     }
     __syncthreads();
-    if (n == 0) {   // an empty graph: no iteration and no pair (its outputs are zero, as outside every graph's n x n block)
-        for (int e = tid; e < ldw * ldw; e += SVT_NT) {
-            x_bin[(size_t)f * ldw * ldw + e] = 0;
-            if (x_out) x_out[(size_t)f * ldw * ldw + e] = 0.0;
-        }
-        if (tid == 0) iters_out[f] = 0;
-        return;   // (uniform)
-    }
     double mu = mu0;
     int n_run = max_iter;
     constexpr int EPT = SVT_NMAX * SVT_NMAX / SVT_NT;   // matrix entries per thread

@@ -192,7 +192,8 @@ def svt_associate(S: torch.Tensor, group_counts: torch.Tensor, g_max: int, alpha
     check(_cabi.load().mvmc_svt_associate(_p(S), dt, _p(group_counts), F, G, N, int(g_max), C.c_double(alpha), C.c_double(lam),
                                           C.c_double(mu), C.c_double(tol), int(max_iter), int(bool(dual_stochastic)), _p(work),
                                           _p(xb), _p(xo), _p(iters), _stream()), "mvmc_svt_associate")
-    n_nodes = group_counts.sum(dim=1).to(torch.int32)
+    # a row the kernel refused (iters = -1: a count below 0 or above the launch's g_max, or more than N nodes) gets labels -1 and no cluster
+    n_nodes = torch.where(iters < 0, 0, group_counts.sum(dim=1)).to(torch.int32)
     mm, labels, ncl = closure_labels(xb, n_nodes)
     return dict(x_bin=xb, match_mat=mm, labels=labels, n_clusters=ncl, iters=iters, X=xo)
 
